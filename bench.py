@@ -16,6 +16,11 @@ Other BASELINE.json configurations through flags (not the headline line; same JS
   --mode infer --batch 128                                                  config 5: eval forward + 10 sampled scanpaths/head
   --precision f16x1                                                         throughput mode (single fp16 plane, 1 MFMA product):
                                                                             separately labelled, NOT the fp32-faithful headline
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else it can measure -- the roofline of the timed
+GEMMs, the host enqueue time on an idle device, the dense-backward, length-law and drop-in legs, the CPU baseline, the replica check
+of N > 1 -- runs only under --full (each leg can still be switched off there with its --no-* flag).
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -157,6 +162,11 @@ def parse():
                          "print it as one JSON line and exit -- the line is committed as profiles/r06_cpu_thread_sweep.json")
     ap.add_argument("--no-length-leg", action="store_true",
                     help="do not time the step on the second scanpath-length law (L ~ U{T/2..T}) after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: GEMM roofline (HIP events around the big launches), host enqueue "
+                         "time on an idle device, the dense-backward / length-law / drop-in legs, the CPU baseline, the N > 1 replica check")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     return ap.parse_args()
 
 
@@ -263,6 +273,45 @@ def cpu_sweep(args):
             "protocol": "oracle train step (fwd+loss+bwd+clip+Adam), 1 warm-up + 1 timed step per thread count", "host": host_info()}
 
 
+DUMP_MAX_BYTES = 64 * 2 ** 20
+DUMP_SAMPLE = 1 << 21          # elements written of an output that has more (a fixed, seeded sample)
+
+
+def dump_outputs(path, outputs):
+    """name -> tensor  ->  path/<name>.npy; float64 stays float64, every other dtype is written as float32.  An output of more than
+    DUMP_SAMPLE elements is written as the DUMP_SAMPLE elements of its flattened form at the sorted indices
+    numpy.random.default_rng(0).choice(numel, DUMP_SAMPLE, replace=False) -- the same sample for every run of the same arguments."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        arrays[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total / 2 ** 20:.1f} MB (limit {DUMP_MAX_BYTES / 2 ** 20:.0f} MB)")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(model, res, loss):
+    """what a caller of the timed step receives: the loss and the model outputs of the step, and for a training step the updated
+    parameters and their gradients (all parameters in model.parameters() order, flattened)"""
+    out = {"loss": loss.reshape(1)}
+    for k, v in res.items():
+        if torch.is_tensor(v):
+            out[k] = v
+    if model.training:
+        ps = list(model.parameters())
+        out["parameters"] = torch.cat([p.detach().reshape(-1) for p in ps])
+        out["gradients"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in ps])
+    return out
+
+
 def build_model(args, dev):
     from scanpaths_amd.procedural import fill_module
     Hm, Wm = args.height // 8, args.width // 8
@@ -287,11 +336,11 @@ def call_model(model, args, b, training):
     return model(b["images"], b["attention_maps"], b["tasks"])
 
 
-def dropin_step(args, model, b):
+def dropin_step(args, model, b, keep=None):
     """The reference's own supervised iteration on the HIP model, call for call (AiR/train.py:116-117 optimizer, :156-167 LambdaLR,
     :188-205 the iteration; OSIE/train.py and COCO_Search18/train.py have the same shape): stock torch.optim.Adam, the two separate loss
     calls summed by autograd, torch.nn.utils.clip_grad_norm_, LambdaLR.step.  Only the tensorboard scalars of :206-210 are left out
-    (logging is outside SURVEY 8's path).  Returns the step function."""
+    (logging is outside SURVEY 8's path).  Returns the step function; with ``keep`` (a dict) every step leaves its model outputs there."""
     from scanpaths_amd.models.loss import CrossEntropyLoss, MLPLogNormalDistribution
     optimizer = torch.optim.Adam(model.parameters(), lr=1e-4, betas=(0.9, 0.999), eps=1e-08,
                                  weight_decay=5e-5 if args.task == "air" else 5e-4)
@@ -311,6 +360,8 @@ def dropin_step(args, model, b):
     def step():
         optimizer.zero_grad()
         predicts = call_model(model, args, b, True)
+        if keep is not None:
+            keep["pred"] = predicts
         loss_actions = CrossEntropyLoss(predicts["actions" if "actions" in predicts else "all_actions_prob"], scanpaths, action_masks)
         loss_duration = MLPLogNormalDistribution(predicts["log_normal_mu"], predicts["log_normal_sigma2"], durations, duration_masks)
         loss = loss_actions + lambda_1 * loss_duration
@@ -347,6 +398,8 @@ def launch_ranks(args) -> int:
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if args.cpu_sweep:
         print(json.dumps(cpu_sweep(args)))
         return
@@ -402,12 +455,13 @@ def main():
     if args.dense_backward:
         sp_config.set(row_sparsity=False)            # tagged in config.non_default_switches
     sparse_on = sp_config.settings["row_sparsity"]
+    keep = {} if args.dump_outputs else None          # --dump-outputs: the model outputs of the latest step
     if args.mode == "train" and args.dropin:
         if world != 1:
             raise SystemExit("bench.py: --dropin times the reference's single-process call sequence (its DataParallel has no counterpart "
                              "here; the multi-GPU path is FlatAdam's bucketed all-reduce)")
         model.train()
-        step = dropin_step(args, model, b)
+        step = dropin_step(args, model, b, keep)
     elif args.mode == "train":
         model.train()
         if world > 1:
@@ -424,6 +478,8 @@ def main():
             b = cur["b"]
             opt.zero_grad()
             pred = call_model(model, args, b, True)
+            if keep is not None:
+                keep["pred"] = pred
             mask_sums = None
             if world > 1:   # loss normalised by the GLOBAL mask sums, as DataParallel's gathered loss (AiR/train.py:190-197)
                 from scanpaths_amd.ddp import global_mask_normaliser
@@ -445,11 +501,16 @@ def main():
             with torch.no_grad():
                 pred = call_model(model, args, b, False)
                 last = None
+                samples = {}
                 for hd in heads:
                     pre = hd + "_" if hd else ""
-                    for _ in range(10):
+                    for i in range(10):
                         last = sampler.random_sample(pred[pre + "all_actions_prob"], pred[pre + "log_normal_mu"],
                                                      pred[pre + "log_normal_sigma2"])
+                        if keep is not None:
+                            samples.update({f"{pre}sample{i}_{k}": v for k, v in last.items()})
+                if keep is not None:
+                    keep["pred"] = {**pred, **samples}
             return last["durations"].sum()
 
     dist_info = None
@@ -483,7 +544,8 @@ def main():
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    hip.TIMER = hip.KernelTimer(min_flops=2e11 * args.batch / 32)    # bracket only the dominant GEMM launches with HIP events
+    if args.full:
+        hip.TIMER = hip.KernelTimer(min_flops=2e11 * args.batch / 32)    # bracket only the dominant GEMM launches with HIP events
     sync()
     t0 = time.perf_counter()
     host_s = 0.0
@@ -494,15 +556,17 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     timer, hip.TIMER = hip.TIMER, None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_outputs(model, keep["pred"], loss))
     # host time to enqueue ONE step onto an idle device (outside the timed region): inside the timed loop the host is held back by the
     # device's queue once it is far enough ahead, so host_s / steps tends to the device time of a step however fast the host is
     host_idle = []
-    for _ in range(2):
+    for _ in range(2 if args.full else 0):
         th = time.perf_counter()
         step()
         host_idle.append(time.perf_counter() - th)
         sync()
-    if world > 1 and args.mode == "train":
+    if args.full and world > 1 and args.mode == "train":
         # after W + K optimiser steps every rank must hold the same parameters (same reduced gradients, same Adam state): a drifted
         # replica means a collective was skipped or mis-ordered on some rank
         from scanpaths_amd.ddp import assert_replicas_identical
@@ -518,7 +582,7 @@ def main():
             last = rows_tok.rc.last
             Tn = args.T
             act_frac = float((last.view(-1, 1) >= torch.arange(1, Tn, device=last.device).view(1, -1)).float().mean()) if Tn > 1 else 1.0
-    if args.mode == "train" and world == 1 and sparse_on and not args.no_dense_leg:
+    if args.full and args.mode == "train" and world == 1 and sparse_on and not args.no_dense_leg:
         # the same step with the dense backward pass (what the reference computes), same process, after the timed region
         sp_config.set(row_sparsity=False)
         step()
@@ -540,7 +604,8 @@ def main():
                             "(tests/test_model_gpu.py::test_masked_step_sparsity...); forward, loss, clip and Adam are unchanged; synthetic "
                             "scanpath lengths are uniform in 1..T (SURVEY.md 8d), real length distributions skip less or more; "
                             "`--dense-backward` makes the dense form the line"}
-    if args.mode == "train" and world == 1 and sparse_on and not args.dropin and not args.no_length_leg and not args.force_bucketer:
+    if (args.full and args.mode == "train" and world == 1 and sparse_on and not args.dropin and not args.no_length_leg
+            and not args.force_bucketer):
         # sensitivity of the line to the synthetic length law (the sparsity of the backward pass is the only thing that depends on it):
         # the same step on L ~ U{ceil(T/2)..T} -- every other tensor of the batch is identical -- same process, after the timed region
         b2 = {k: v.to(dev) for k, v in make_batch(task, args.batch, args.height, args.width, args.T, seed=0, rank=rank,
@@ -561,7 +626,7 @@ def main():
         length_leg = {"length_law": "L ~ U{ceil(T/2)..T} (every other draw of the batch unchanged)", "ms_per_step": round(l_ms, 2),
                       "images_per_s": round(args.batch * 1e3 / l_ms, 3),
                       "active_fraction_of_sample_steps": round(l_frac, 4) if l_frac is not None else None}
-    if args.mode == "train" and world == 1 and not args.dropin and not args.no_dropin_leg and not args.force_bucketer:
+    if args.full and args.mode == "train" and world == 1 and not args.dropin and not args.no_dropin_leg and not args.force_bucketer:
         # the reference's literal call sequence on a second, identically initialised model (the first one's parameters live in FlatAdam's
         # flat buffers): same process, same box, after the timed region
         model2 = build_model(args, dev).train()
@@ -594,7 +659,7 @@ def main():
 
     ms_per_step = dt / args.steps * 1e3
     value = args.batch * world * args.steps / dt
-    summ = timer.summary()
+    summ = timer.summary() if timer is not None else {}
     # launches that skip samples behind their last masked-in step ("_rows" keys) EXECUTE only the active fraction of the dense FLOPs
     # their key was priced with: the roofline below counts the executed ones
     if args.mode == "train" and act_frac is not None:
@@ -714,7 +779,7 @@ def main():
                       "loss": round(float(loss.detach()), 5) if args.mode == "train" else None,
                       "peak_hbm_gib": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
                       "host_enqueue_ms_per_step": round(host_s / args.steps * 1e3, 2),
-                      "host_enqueue_ms_one_step_on_idle_device": round(min(host_idle) * 1e3, 2),
+                      "host_enqueue_ms_one_step_on_idle_device": round(min(host_idle) * 1e3, 2) if host_idle else None,
                       "arithmetic": arith,
                       # switches that differ from the package defaults (scanpaths_amd.config; environment variables are honoured
                       # only under SP_ALLOW_ENV_TUNING=1): {} for the headline line
@@ -744,7 +809,7 @@ def main():
     if ddp_info is not None:
         out["ddp"] = ddp_info
         out["metric"] = metric + " [--force-bucketer: RCCL world of one, NOT the headline line]"
-    if world == 1 and not args.no_cpu_baseline and args.mode == "train":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "train":
         out["cpu_baseline"] = cpu_baseline(args)
     if world > 1 or args.force_bucketer:
         torch.distributed.destroy_process_group()

@@ -26,6 +26,8 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+from helpers import save_npz  # noqa: E402
 from scanpaths_amd.procedural import fill_module  # noqa: E402
 from scanpaths_amd.synth import make_batch  # noqa: E402
 
@@ -149,7 +151,7 @@ def run_case(name, task, arch, B, T, seed, mode, with_step, family="default"):
                   "resnet.7.0.bn2.running_var"):
             if k in sd:
                 out[f"{tag}/bn/{k}"] = sd[k].clone().numpy()
-    np.savez_compressed(os.path.join(HERE, name + ".npz"), **out)
+    save_npz(os.path.join(HERE, name + ".npz"), out)      # <name>.npz + <name>.partN.npz shards (tests/helpers.py:load_npz)
     with open(os.path.join(HERE, name + ".json"), "w") as f:
         json.dump(meta, f, indent=1)
     print("wrote", name, {k: v.shape for k, v in list(out.items())[:4]})

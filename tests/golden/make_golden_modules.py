@@ -32,6 +32,7 @@ from scanpaths_amd.procedural import procedural_state_dict  # noqa: E402
 
 sys.path.insert(0, os.path.join(REPO, "tests"))
 from module_cases import MODULE_CASES, case_inputs, cotangents  # noqa: E402  (shapes + seeds shared with the tests)
+from helpers import save_npz  # noqa: E402
 
 
 def _ref_modules():
@@ -139,8 +140,8 @@ def main():
         final[k] = v.astype(np.float32) if (rest.startswith("d_") or rest.startswith("dparam/")) else v
     store = final
     path = os.path.join(HERE, "modules.npz")
-    np.savez_compressed(path, **store)
-    print(f"wrote {path}: {len(store)} arrays, {os.path.getsize(path) / 2 ** 20:.1f} MiB")
+    save_npz(path, store)            # modules.npz + modules.partN.npz shards (tests/helpers.py:load_npz reads them together)
+    print(f"wrote {path}: {len(store)} arrays")
 
 
 if __name__ == "__main__":

@@ -6,12 +6,65 @@ import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SHARD_BYTES = 900 * 1024      # a golden .npz is split into shards below this size (no committed file over 1 MiB)
+
+
+class GoldenArrays(dict):
+    """name -> array of one golden fixture; ``files`` lists the names like numpy's NpzFile does"""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def _shards(path):
+    """<stem>.npz, <stem>.part1.npz, <stem>.part2.npz, ... as far as they exist"""
+    stem, out, k = path[:-len(".npz")], [path], 1
+    while os.path.exists(f"{stem}.part{k}.npz"):
+        out.append(f"{stem}.part{k}.npz")
+        k += 1
+    return out
+
+
+def load_npz(path):
+    """a golden .npz fixture together with its .partN.npz shards"""
+    data = GoldenArrays()
+    for p in _shards(path):
+        with np.load(p) as z:
+            data.update({k: z[k] for k in z.files})
+    return data
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed into <stem>.npz + <stem>.partN.npz shards of at most SHARD_BYTES compressed each; stale shards are removed"""
+    import io
+    for p in _shards(path)[1:]:
+        os.remove(p)
+    blobs = {}
+    for k, v in arrays.items():
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: v})
+        blobs[k] = buf.getbuffer().nbytes
+    groups, cur, size = [], {}, 0
+    for k, v in arrays.items():
+        if cur and size + blobs[k] > SHARD_BYTES:
+            groups.append(cur)
+            cur, size = {}, 0
+        cur[k] = v
+        size += blobs[k]
+    groups.append(cur)
+    stem = path[:-len(".npz")]
+    for i, g in enumerate(groups):
+        p = path if i == 0 else f"{stem}.part{i}.npz"
+        np.savez_compressed(p, **g)
+        if len(g) > 1 and os.path.getsize(p) > 1024 * 1024:
+            raise RuntimeError(f"{p}: shard over 1 MiB")
 
 
 def load_golden(name):
     with open(os.path.join(GOLDEN, name + ".json")) as f:
         meta = json.load(f)
-    data = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+    data = load_npz(os.path.join(GOLDEN, name + ".npz"))
     return meta, data
 
 

@@ -221,7 +221,7 @@ def _start_bench(extra, env_extra=None):
 
 
 _SMALL = ["--task", "osie", "--arch", "resnet18", "--T", "2", "--batch", "2", "--height", "240", "--width", "320", "--steps", "2",
-          "--warmup", "1", "--no-cpu-baseline"]
+          "--warmup", "1", "--no-cpu-baseline", "--full"]
 
 
 def _run_bench_gpus():
@@ -254,3 +254,21 @@ def test_bench_gpus_n_launches_n_ranks_or_fails_loudly(request):
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["config"]["global_batch"] == 4 and two["scaling"] == "weak"
     assert abs(two["value"] - 2 * two["value_per_gpu"]) < 1e-2 * two["value"]
 
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` (plain run): the loss, model outputs, parameters and gradients of the last timed step as float32
+    .npy files within the 64 MB budget; the dumped loss is the one the JSON line reports"""
+    import json
+    import numpy as np
+    small = [a for a in _SMALL if a != "--full"]
+    p = _start_bench(["--gpus", "1"] + small + ["--dump-outputs", str(tmp_path)])
+    so, se = p.communicate(timeout=900)
+    assert p.returncode == 0, se[-2000:]
+    line = json.loads(so.strip().splitlines()[-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["roofline"] is None and "cpu_baseline" not in line
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert {"loss", "actions", "log_normal_mu", "log_normal_sigma2", "parameters", "gradients"} <= set(files), sorted(files)
+    assert all(a.dtype == np.float32 for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 * 2 ** 20
+    assert abs(float(files["loss"][0]) - line["config"]["loss"]) <= 1e-5 * max(1.0, abs(line["config"]["loss"]))
+    assert np.isfinite(files["parameters"]).all() and np.abs(files["gradients"]).max() > 0

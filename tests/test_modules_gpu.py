@@ -12,11 +12,12 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import load_npz
 from module_cases import MODULE_CASES, case_inputs, cotangents
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "modules.npz"))
+G = load_npz(os.path.join(os.path.dirname(__file__), "golden", "modules.npz"))
 
 
 def _params(name, spec):

@@ -3,7 +3,7 @@
 # recurrence is the critical path (tools/trace_bwd_steps.py), gap analysis.
 O=gpurun_out/r06a; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o p -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-dense-leg --no-dropin-leg > $O/bench_prof.json 2> $O/bench_prof.err
 f=$(find $O/prof -name "p_kernel_trace.csv" | head -1)
 python3 tools/trace_bwd_steps.py "$f" > $O/bwd_steps.log 2>&1

@@ -9,6 +9,6 @@ python3 -m pytest tests/test_modules_gpu.py -x -q -m gpu > $O/pytest_modules.log
 python3 -m pytest tests/test_model_gpu.py -x -q -m gpu -k "side_stream or full_batch or sparsity_of_the_backward" -s > $O/pytest_model_sel.log 2>&1
 python3 -m pytest tests/test_ops_gpu.py tests/test_ddp_gpu.py tests/test_optim_gpu.py -x -q -m gpu > $O/pytest_ops.log 2>&1
 wait $SWEEP
-python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
-python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --force-bucketer --no-dense-leg > $O/bench_bucketer.json 2> $O/bench_bucketer.err
+python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+python3 bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --force-bucketer --no-dense-leg > $O/bench_bucketer.json 2> $O/bench_bucketer.err
 tail -3 $O/pytest_modules.log $O/pytest_model_sel.log $O/pytest_ops.log; cat $O/cpu_sweep.json; tail -2 $O/cpu_sweep.err
