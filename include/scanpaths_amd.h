@@ -564,6 +564,12 @@ int sp_scanmatch_align(const int* A, int n, const int* B, int m, const double* s
 int sp_scan_max_fixations(void);
 int sp_scan_sed_stde(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, int height,
                      int width, int ngrid, double max_dim, int* sed, double* stde, void* stream);
+/* Time-delay-embedding distances and the Euclidean distance of scanpath pairs (visual_attention_metrics.py:205-218, :332-388,
+ * :444-476), same fixation layout as sp_scan_sed_stde.  k >= 1: time_delay_embedding_distance at k ('Mean', or 'Hausdorff' when
+ * hausdorff != 0), NaN where the reference returns False; k == 0: scaled_time_delay_embedding_distance (coordinates / max_dim, mean
+ * over every k), NaN where it returns None.  eucl (may be NULL): euclidean_distance of the unscaled pair, NaN where it returns False. */
+int sp_scan_tde(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, int k, int hausdorff,
+                double max_dim, double* tde, double* eucl, void* stream);
 /* MultiMatch (the five similarities the reference obtains per pair from multimatch_gaze.docomparison, AiR/utils/evaluation.py:7,44-45,213;
  * multimatch_gaze==0.1.2 is not vendored: the published algorithm, restated on the host in utils/evaltools/multimatch.py, is this
  * kernel's checker): fix [total][ncol >= 3] = (x, y, duration), scanpaths of at most sp_scan_max_fixations() fixations; out [npairs][5]
@@ -600,6 +606,43 @@ int sp_collate_targets(const float* X, const float* Y, const float* T_start, con
  * scipy.ndimage.gaussian_filter(one-hot map, sigma) (mode reflect, truncate 4) divided by its sum; terminate rows are untouched.
  * float32 results agree with scipy to ~1 ulp (the normaliser is summed in a different order). */
 int sp_blur_targets(float* target, int rows, int map_h, int map_w, double sigma, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Attention-map losses (AiR/models/loss.py:16-25, 47-170), csrc/salmaps.hip.  fp32, contiguous rows of P elements; one launch
+ * writes the value(s) and coef = d value / d prediction (already divided by the row count of a mean), so the backward pass is
+ * sp_scale_by / sp_rowscale / sp_rowscale_idx with grad_output.  ticket: a device word that is 0 on entry and 0 again when the
+ * launch ends (the last workgroup takes the mean over rows in row order: deterministic, no float atomics).
+ * ---------------------------------------------------------------------------------------------- */
+/* DurationSmoothL1Loss(x, gt, mask) / MLPRayleighDistribution(sigma2, gt, mask) over n elements: out[0], coef [n] */
+int sp_smooth_l1_loss(const float* x, const float* gt, const float* mask, int64_t n, float* out, float* coef, void* stream);
+int sp_rayleigh_loss(const float* sigma2, const float* gt, const float* mask, int64_t n, float* out, float* coef, void* stream);
+/* CC_MatchLoss: out[0] = mean |a - b| over n elements, coef_a = sign(a - b) / n, coef_b = -coef_a */
+int sp_abs_diff_mean(const float* a, const float* b, int64_t n, float* out, float* coef_a, float* coef_b, void* stream);
+/* NSS / CC / KLD of R rows: out[0] = mean over rows, row_val [R], coef [R][P].  sp_kld_loss with out == NULL is KLD_items: the row
+ * values are the result and coef is not divided by R (ticket may then be NULL). */
+int sp_nss_loss(const float* x, const float* fix, int R, int P, float* out, float* row_val, float* coef, unsigned* ticket, void* stream);
+int sp_cc_loss(const float* x, const float* y, int R, int P, float* out, float* row_val, float* coef, unsigned* ticket, void* stream);
+int sp_kld_loss(const float* x, const float* y, int R, int P, float* out, float* row_val, float* coef, unsigned* ticket, void* stream);
+/* CC_terms: the rows b with sum(good[b][:T]) > 0 and sum(poor[b][:T]) > 0, in row order: out[idx[b]] = CC of row b (idx[b] = -1 and a
+ * zero coef row for the others), count[0] = how many */
+int sp_cc_terms(const float* x, const float* y, const float* good, const float* poor, int R, int P, int T, float* out, int* idx,
+                int* count, float* coef, void* stream);
+/* KLD_visual_linguistic_alignment: z [B][P] logits; boxes channel-last qpos [B][P][Mq], apos [B][P][Ma], masks [B][Mq], [B][Ma] */
+int sp_kld_box_alignment(const float* z, const float* qpos, const float* qmask, int Mq, const float* apos, const float* amask, int Ma,
+                         int B, int P, float* out, float* row_val, float* coef, unsigned* ticket, void* stream);
+/* KLD_question_aligment: z [B][T][P] logits, qpos [B][P][M], qmask [B][M], dmask [B][T]; npairs[0] = the number of (sample, object)
+ * pairs (0: out is NaN, the caller raises), sample_sum [B] scratch, coef [B][T][P].  M <= 64, T * M <= 1024. */
+int sp_kld_question_alignment(const float* z, const float* qpos, const float* qmask, const float* dmask, int B, int T, int P, int M,
+                              float* out, int* npairs, float* sample_sum, float* coef, unsigned* ticket, void* stream);
+/* out[r][i] = coef[r][i] * g[idx[r]], 0 where idx[r] < 0 */
+int sp_rowscale_idx(const float* coef, const float* g, const int* idx, int R, int P, float* out, void* stream);
+/* Saliency-map metrics of N map pairs of P pixels, float64 (visual_attention_metrics.py:41-192): auc / nss / kld [N] = AUC_Judd (with
+ * jitter [N][P] added when non-NULL), NSS, KLdiv.  A map with more than sp_saliency_metrics_lds_fixations() fixated pixels (F > 0)
+ * keeps its thresholds in scratch + scratch_off[n] (bytes; scratch_off has N + 1 entries, slice n holds at least
+ * 8 * next_pow2(Nfix) + 4 * Nfix bytes, offsets multiples of 8); its AUC is NaN if the slice is too small. */
+int sp_saliency_metrics_lds_fixations(void);
+int sp_saliency_metrics(const double* sal, const double* fix, const double* jitter, int N, int P, const int64_t* scratch_off,
+                        void* scratch, double* auc, double* nss, double* kld, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * clip_grad_norm_ + Adam (L2 folded into the gradient) over one flat fp32 buffer.  AiR/train.py:116-117,200-202.

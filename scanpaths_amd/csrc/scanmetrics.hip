@@ -204,6 +204,63 @@ __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict
     o[4] = 1 - mm_median(dur, cnt);
 }
 
+// ---- time-delay-embedding distances and the Euclidean distance (visual_attention_metrics.py:205-218, :332-388, :444-476) ----
+// One thread per pair, numpy's float64 evaluation order as in sed_stde_kernel.  k >= 1: time_delay_embedding_distance at that k
+// ('Mean' or, with hausdorff, 'Hausdorff'), NaN where the reference returns False (a scanpath shorter than k); k == 0:
+// scaled_time_delay_embedding_distance, the mean of the 'Mean' distances over k = 1..min(nh, ns), NaN where it returns None.
+// Coordinates are divided by max_dim first (1.0: unscaled).  eucl: euclidean_distance of the unscaled pair, NaN where the reference
+// returns False (lengths differ).
+__global__ __launch_bounds__(64) void tde_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
+                                                 const int* __restrict__ count, const int* __restrict__ pairs, int npairs, int k,
+                                                 int hausdorff, double max_dim, double* __restrict__ tde, double* __restrict__ eucl) {
+    const int p = blockIdx.x * 64 + threadIdx.x;
+    if (p >= npairs) return;
+    const int ih = pairs[2 * p], is = pairs[2 * p + 1];
+    const int nh = count[ih], ns = count[is];
+    const double* fh = fix + start[ih] * ncol;
+    const double* fs = fix + start[is] * ncol;
+    if (eucl) {
+        eucl[p] = nh != ns ? NAN : numpy_sum(nh, [&](int i) {
+            const double dx = fh[i * ncol] - fs[i * ncol], dy = fh[i * ncol + 1] - fs[i * ncol + 1];
+            return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+        });
+    }
+    if (!tde) return;
+    double hx[MAXFIX], hy[MAXFIX], sx[MAXFIX], sy[MAXFIX];
+    for (int i = 0; i < nh; ++i) { hx[i] = fh[i * ncol] / max_dim; hy[i] = fh[i * ncol + 1] / max_dim; }
+    for (int i = 0; i < ns; ++i) { sx[i] = fs[i * ncol] / max_dim; sy[i] = fs[i * ncol + 1] / max_dim; }
+    auto dist_k = [&](int kk, bool haus) {        // time_delay_embedding_distance(h, s, kk)
+        double acc = 0.0, worst = -INFINITY;
+        const int nsw = ns - kk + 1, nhw = nh - kk + 1;
+        for (int s0 = 0; s0 < nsw; ++s0) {
+            double best = INFINITY;
+            for (int h0 = 0; h0 < nhw; ++h0) {
+                const double d = numpy_sum(kk, [&](int i) {
+                    const double dx = sx[s0 + i] - hx[h0 + i], dy = sy[s0 + i] - hy[h0 + i];
+                    return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+                });
+                best = d < best ? d : best;
+            }
+            const double v = best / (double)kk;
+            acc = __dadd_rn(acc, v);
+            worst = v > worst ? v : worst;
+        }
+        return haus ? worst : acc / (double)nsw;
+    };
+    if (k > 0) {
+        tde[p] = (nh < k || ns < k) ? NAN : dist_k(k, hausdorff != 0);
+        return;
+    }
+    const int kmax = min(nh, ns);
+    if (kmax == 0) {
+        tde[p] = NAN;
+        return;
+    }
+    double sum = 0.0;
+    for (int kk = 1; kk <= kmax; ++kk) sum = __dadd_rn(sum, dist_k(kk, false));
+    tde[p] = sum / (double)kmax;
+}
+
 }  // namespace
 
 extern "C" int sp_scan_max_fixations(void) { return MAXFIX; }
@@ -226,6 +283,18 @@ extern "C" int sp_scan_multimatch(const double* fix, int ncol, const int64_t* st
     if (npairs < 1 || ncol < 3 || !(screen_w > 0) || !(screen_h > 0)) return SP_EINVAL;
     hipLaunchKernelGGL(multimatch_kernel, dim3((npairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, fix, ncol, start, count, pairs,
                        npairs, screen_w, screen_h, out);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+// time-delay-embedding distance at one k (k >= 1, 'Mean' / 'Hausdorff') or the scaled distance over all k (k == 0), and / or the
+// Euclidean distance, of npairs scanpath pairs (tde_kernel)
+extern "C" int sp_scan_tde(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, int k,
+                           int hausdorff, double max_dim, double* tde, double* eucl, void* stream) {
+    if (!fix || !start || !count || !pairs || (!tde && !eucl)) return SP_ENULL;
+    if (npairs < 1 || ncol < 2 || k < 0 || k > MAXFIX || !(max_dim > 0)) return SP_EINVAL;
+    hipLaunchKernelGGL(tde_kernel, dim3((npairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, fix, ncol, start, count, pairs, npairs, k,
+                       hausdorff, max_dim, tde, eucl);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

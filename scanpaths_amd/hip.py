@@ -164,6 +164,7 @@ SIGNATURES = {
     "sp_scanmatch_align": (_I, [_P, _I, _P, _I, _P, _I, _P, C.c_double, _P, _P, _P, _P, _P, _P]),
     "sp_scan_max_fixations": (_I, []),
     "sp_scan_sed_stde": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, C.c_double, _P, _P, _P]),
+    "sp_scan_tde": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _P, _P, _P]),
     "sp_scan_multimatch": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _P, _P]),
     "sp_sample_actions": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, _P, _P]),
     "sp_generate_scanpath": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
@@ -183,6 +184,18 @@ SIGNATURES = {
     "sp_sumsq_workspace": (_L, [_L]),
     "sp_sum": (_I, [_P, _L, _P, _P, _P]),
     "sp_sumsq": (_I, [_P, _L, _P, _P, _P]),
+    "sp_smooth_l1_loss": (_I, [_P, _P, _P, _L, _P, _P, _P]),
+    "sp_rayleigh_loss": (_I, [_P, _P, _P, _L, _P, _P, _P]),
+    "sp_abs_diff_mean": (_I, [_P, _P, _L, _P, _P, _P, _P]),
+    "sp_nss_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_cc_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_kld_loss": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_cc_terms": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_kld_box_alignment": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_kld_question_alignment": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "sp_rowscale_idx": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "sp_saliency_metrics_lds_fixations": (_I, []),
+    "sp_saliency_metrics": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sp_clip_adam": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P]),
 }
 
