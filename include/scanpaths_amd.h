@@ -645,6 +645,30 @@ int sp_saliency_metrics(const double* sal, const double* fix, const double* jitt
                         void* scratch, double* auc, double* nss, double* kld, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Dataset transforms of one batch (csrc/transforms.hip): what every task's Dataset.__getitem__ does per sample before collate_func.
+ * ---------------------------------------------------------------------------------------------- */
+/* transforms.Resize((H, W)) (Pillow 8-bit BILINEAR) -> ToTensor() -> Normalize(mean, std) of a ragged batch of RGB uint8 HWC images
+ * (AiR/train.py:43-46, OSIE/train.py:41-45, COCO_Search18/train.py:41-45): image b starts at byte src_off[b] of src.  meta (int32):
+ * [B][4] = (H_b, W_b, horizontal table, vertical table), tables at those word offsets of meta: [ksize][out x (min, n)][out x ksize
+ * coefficients], Pillow's 22-bit fixed-point weights (scanpaths_amd/transforms.py builds them).  out float32 [B][3][H][W]. */
+int sp_resize_normalize_images(const uint8_t* src, const int64_t* src_off, const int* meta, int B, int H, int W, float mean0,
+                               float mean1, float mean2, float std0, float std1, float std2, float* out, void* stream);
+/* skimage 0.17.2 resize(map, (h, w)) defaults (anti-aliasing Gaussian, mode 'reflect', bilinear, clip) of a ragged batch of maps
+ * [h_b][w_b][C] (float32, or uint8 when src_u8: its values as float32), then norm 0: none, 1: / max (AiR/dataset/dataset.py:153),
+ * 2: / (max + eps) (COCO_Search18/dataset/dataset.py:159), in float64.  Map b starts at element src_off[b]; dims [B][2] = (h_b, w_b);
+ * filt [B][4] = (R0, w0 offset, R1, w1 offset): half Gaussian kernels wts[off + j], j = 0..R, of axis 0 and axis 1 (R = 0, w = 1: no
+ * filter); wmax >= every w_b.  out [B][h][w][C] float32, or float64 when out_f64; workspace >= sp_resize_maps_workspace(B, h, w, C,
+ * wmax) bytes. */
+int64_t sp_resize_maps_workspace(int B, int h, int w, int C, int wmax);
+int sp_resize_maps(const void* src, int src_u8, const int64_t* src_off, const int* dims, const int* filt, const double* wts, int B,
+                   int C, int h, int w, int wmax, int norm, double eps, int out_f64, void* workspace, void* out, void* stream);
+/* Binary box maps: map b ([dims[b][0]][dims[b][1]][C] uint8 at byte dst_off[b] of dst, max_elems >= its element count) is 1 inside
+ * the boxes box_start[b] .. box_start[b + 1] - 1 of its channel, 0 elsewhere; boxes [n][5] = (y0, y1, x0, x1, channel), half-open,
+ * clipped to the map (COCO_Search18/dataset/dataset.py:150-158, AiR/dataset/dataset.py:80-90).  boxes may be NULL when n = 0. */
+int sp_rasterize_boxes(const int* boxes, const int* box_start, const int64_t* dst_off, const int* dims, int B, int C, int max_elems,
+                       uint8_t* dst, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * clip_grad_norm_ + Adam (L2 folded into the gradient) over one flat fp32 buffer.  AiR/train.py:116-117,200-202.
  * g_eff = g*gscale (gscale = 1/world_size after a sum all-reduce); total_norm = sqrt(*sumsq)*gscale;
  * coef = min(1, clip/(total_norm+1e-6)) (clip <= 0: no clipping); bc1 = 1-beta1^t, bc2 = 1-beta2^t from the host.

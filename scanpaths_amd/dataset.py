@@ -1,8 +1,11 @@
 """Dataset-side targets on the device: what ``AiR.__getitem__`` + ``collate_func`` build per batch
 (AiR/dataset/dataset.py:100-211) from the fixation records -- soft one-hot action targets ``scanpaths`` [B,T,1+Hm*Wm], ``durations``,
 ``action_masks``, ``duration_masks`` -- by ONE kernel launch over the ragged fixation lists (csrc/sampling.hip ``collate_kernel``)
-instead of B python loops over T.  Image decoding / transforms and the attention-box resize (skimage) stay on the host: they need
-the data files and libraries that are absent here; the attention map's ``/= max`` normalisation is offered (``normalise_attention``).
+instead of B python loops over T.  The rest of ``__getitem__`` runs on the device as well (``scanpaths_amd.transforms``,
+csrc/transforms.hip): the image Resize / ToTensor / Normalize (bit-identical to Pillow + torchvision 0.7), the skimage resize of
+the attention box maps with the ``/= max`` (AiR) or ``/= max + 1e-7`` (COCO) normalisation, the COCO detector-box and AiR
+scene-graph box maps drawn from integer boxes; ``collate_raw`` assembles a batch from decoded images, box maps and fixation
+records.  Only image decoding stays on the host.
 
 Round 3 adds the rest of the reference's dataset surface that does not need image files or skimage:
   * ``blur_sigma`` targets (gaussian_filter of every target map + renormalisation, :144-147) by a second launch (``sp_blur_targets``);
@@ -12,7 +15,8 @@ Round 3 adds the rest of the reference's dataset surface that does not need imag
     AiR/dataset/dataset.py:258-343, 390-473; the COCO and OSIE evaluation sets likewise): ragged host-side lists of the reference's
     structured fixation arrays -- they feed host-side consumers (utils/evaluation.py, the RL reward), so they stay on the host;
   * the COCO detector-box attention map before its skimage resize (COCO_Search18/dataset/dataset.py:150-160) and the
-    normalisations behind the resize (AiR ``/= max``, COCO ``/= max + 1e-7``)."""
+    normalisations behind the resize (AiR ``/= max``, COCO ``/= max + 1e-7``); ``transforms.attention_maps_from_detections`` does
+    the whole of it on the device."""
 from __future__ import annotations
 
 from typing import Dict, List, Sequence
@@ -181,6 +185,38 @@ def collate_func(samples: List[dict], max_length: int = 16, action_map=(30, 40),
     data = dict(t)
     data["images"] = torch.stack([s["image"] for s in samples]).to(dev)
     data["attention_maps"] = torch.stack([torch.as_tensor(s["attention_map"], dtype=torch.float32) for s in samples]).to(dev)
+    data["img_names"] = [s["img_name"] for s in samples]
+    data["question_ids"] = [s["question_id"] for s in samples]
+    data["performances"] = torch.tensor([(s["fixation"]["subject_answer"] == s["fixation"]["answer"]
+                                          and s["fixation"]["subject_answer"] != "faild") for s in samples], device=dev)
+    return data
+
+
+def collate_raw(samples: List[dict], max_length: int = 16, action_map=(30, 40), size=(240, 320), mean=None, std=None, device=None,
+                f64_div: bool = True, blur_sigma=None) -> Dict[str, object]:
+    """collate_func's batch (AiR/dataset/dataset.py:168-211) straight from raw samples, every transform on the device: each sample holds
+    "image" (decoded RGB uint8 [H, W, 3] array / tensor, or a PIL image), "fixation" (the record), "img_name", "question_id", and
+    either "box_map" (AiR's attention box map at any size, float32 or uint8: resize + ``/= max``, :151-154) or "detections" + "task" +
+    "det_size" (COCO-Search18's detector boxes: drawn, resized, ``/= max + 1e-7``, COCO_Search18/dataset/dataset.py:150-160).
+    Images: Resize(size) -> ToTensor -> Normalize(mean, std) (ImageNet statistics by default, AiR/train.py:43-46)."""
+    from . import transforms as T
+    if not samples:
+        raise ValueError("empty batch")
+    coco = "box_map" not in samples[0]
+    if any(("box_map" in s) == coco for s in samples):
+        raise ValueError("every sample needs a box_map (AiR), or detections + task + det_size (COCO-Search18)")
+    images = T.resize_normalise_images([s["image"] for s in samples], size, mean if mean is not None else T.IMAGENET_MEAN,
+                                       std if std is not None else T.IMAGENET_STD, device)
+    dev = images.device
+    if coco:
+        att = T.attention_maps_from_detections([s["detections"] for s in samples], [s["task"] for s in samples],
+                                               [s["det_size"] for s in samples], action_map, 1e-7, device=dev)
+    else:
+        att = T.attention_maps([s["box_map"] for s in samples], action_map, 0.0, device=dev)
+    t = collate_targets([s["fixation"] for s in samples], max_length, action_map, dev, f64_div, blur_sigma)
+    data = dict(t)
+    data["images"] = images
+    data["attention_maps"] = att
     data["img_names"] = [s["img_name"] for s in samples]
     data["question_ids"] = [s["question_id"] for s in samples]
     data["performances"] = torch.tensor([(s["fixation"]["subject_answer"] == s["fixation"]["answer"]

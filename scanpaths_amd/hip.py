@@ -196,6 +196,10 @@ SIGNATURES = {
     "sp_rowscale_idx": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "sp_saliency_metrics_lds_fixations": (_I, []),
     "sp_saliency_metrics": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "sp_resize_normalize_images": (_I, [_P, _P, _P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _P, _P]),
+    "sp_resize_maps_workspace": (_L, [_I, _I, _I, _I, _I]),
+    "sp_resize_maps": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_double, _I, _P, _P, _P]),
+    "sp_rasterize_boxes": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "sp_clip_adam": (_I, [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F, _F, _F, _F, _P]),
 }
 
