@@ -28,7 +28,7 @@ extern "C" {
 #define SP_EINVAL (-1)   /* unsupported shape / alignment */
 #define SP_ENULL (-2)    /* required pointer is NULL */
 
-#define SP_ABI_VERSION 3
+#define SP_ABI_VERSION 4
 int sp_abi_version(void);
 
 /* The ONE piece of process-wide state in the product library: sp_set_tuning("amax_reset", 1) tells the launchers that the caller
@@ -146,23 +146,22 @@ int sp_split2_f16(const float* x, int64_t n, void* out, float* scale_amax,
                   int have_amax /* scale_amax[1] already holds max|x| as float bits (fused into the producer: *_amax outputs) */,
                   void* stream);
 int sp_split2_f16_wT(const float* w, int Co, int taps, int Ci, void* out, float* scale_amax, void* stream);
-/* Scale VECTORS (round 4).  The per-tensor scale keeps 22 bits only within 2^-17 of the tensor's maximum; an output row / column whose
+/* Scale VECTORS.  The per-tensor scale keeps 22 bits only within 2^-17 of the tensor's maximum; an output row / column whose
  * contributions ALL come from a far smaller slice of an operand (forward: output channel <- weight row; data gradient: input channel <-
  * weight column; weight gradient: dW row <- dY channel, dW column <- X channel) carried that slice's error undiluted.  Power-of-two
  * scales along a non-contracted dimension factor out exactly; a per-channel scale of an activation that IS contracted (forward / data
  * gradient) is absorbed exactly by the weight operand it meets (x * s_c times w / s_c):
  *   sp_split2_f16_rows     weights [rows][K] (K = taps * Kc, K % 16 == 0) -> planes of w[r][tap][c] / absorb[c] (absorb [Kc] nullable) with
  *                          one scale per row, row_scale [rows]               (forward operand of F.conv2d: AiR/models/resnet.py:57-93)
- *   sp_split2_f16_wT_rows  w [Co][taps][Ci] -> rows ci, k = (tap, co), value w / absorb[co], one scale per row ci (data-gradient operand)
+ *   sp_split2_f16_wT_rows  w [Co][taps][Ci] -> rows ci, k = (tap, co), value w / absorb[co], one scale per row ci (data-gradient operand);
+ *                          nbatch such matrices one behind the other -> nbatch * Ci rows (item-major), one scale per row (nbatch > 1: the
+ *                          rank-1 filters wc)
  *   sp_split2_f16_cols     activations / gradients x [rows][C] (C % 16 == 0) -> planes of x * s_c, col_scale [C]; scratch:
  *                          sp_split2_f16_cols_workspace(rows, C) bytes (partial column maxima, two stages, no atomics)
  * Consumers: sp_conv_desc.w_scale_rows, sp_wgrad_desc.x_scale_vec / y_scale_vec; an activation split by _cols enters the igemm with
  * x_scale -> a device 1.0f and a weight operand split with absorb = its col_scale. */
 int sp_split2_f16_rows(const float* w, int64_t rows, int64_t K, int Kc, const float* absorb, void* out, float* row_scale, void* stream);
-int sp_split2_f16_wT_rows(const float* w, int Co, int taps, int Ci, const float* absorb, void* out, float* row_scale, void* stream);
-/* nbatch matrices [Co][taps][Ci] one behind the other -> nbatch * Ci rows (item-major), one scale per row (round 6: the rank-1 filters wc) */
-int sp_split2_f16_wT_rows_batched(const float* w, int nbatch, int Co, int taps, int Ci, const float* absorb, void* out, float* row_scale,
-                                  void* stream);
+int sp_split2_f16_wT_rows(const float* w, int nbatch, int Co, int taps, int Ci, const float* absorb, void* out, float* row_scale, void* stream);
 int64_t sp_split2_f16_cols_workspace(int64_t rows, int C);
 int sp_split2_f16_cols(const float* x, int64_t rows, int C, void* out, float* col_scale, void* scratch, void* stream);
 int sp_conv_igemm_f16x2(const sp_conv_desc* d, const void* Xsplit, const float* x_scale, const void* Wsplit, const float* w_scale,
@@ -274,39 +273,31 @@ int sp_bn_bwd_split(const float* dy, const float* x, const unsigned long long* m
                     const float* gamma, const float* ext, int64_t M, int C, float* dx, float* dres, void* planes, float* dx_scale,
                     unsigned* bound, float* dgamma, float* dbeta, void* workspace, void* stream);
 
-/* MaxPool2d(3, stride 2, pad 0, ceil_mode=True), NHWC.  models/resnet.py:104. */
-int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, int Ho, int Wo, void* stream);
-int sp_maxpool3s2_bwd(const float* dy, const float* x, const float* y, int N, int H, int W, int C, float* dx, int Ho,
-                      int Wo, void* stream);
-/* the same with the window position (ky*3 + kx) of the first maximum saved by the forward pass (one byte per output element):
- * the backward pass reads neither x nor y and makes no value comparisons */
-int sp_maxpool3s2_fwd_idx(const float* x, int N, int H, int W, int C, float* y, unsigned char* argmax /* nullable */, int Ho, int Wo,
-                          void* stream);
-int sp_maxpool3s2_bwd_idx(const float* dy, const unsigned char* argmax, int N, int H, int W, int C, float* dx, int Ho, int Wo,
-                          void* stream);
+/* MaxPool2d(3, stride 2, pad 0, ceil_mode=True), NHWC.  models/resnet.py:104.  argmax (nullable in the forward pass): the window position
+ * (ky*3 + kx) of the first maximum, one byte per output element; the backward pass reads it instead of x and y and makes no value
+ * comparisons.  C % 4 == 0. */
+int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* argmax /* nullable */, int Ho, int Wo,
+                      void* stream);
+int sp_maxpool3s2_bwd(const float* dy, const unsigned char* argmax, int N, int H, int W, int C, float* dx, int Ho, int Wo, void* stream);
 /* NCHW [N,C,H,W] -> NHWC [N,H,W,Cp] (Cp >= C, extra channels zero) and generic last-dim pad/crop copy */
 int sp_nchw_to_nhwc_pad(const float* x, int N, int C, int H, int W, int Cp, float* y, void* stream);
 int sp_pad_lastdim(const float* x, int64_t rows, int Cin, int Cout, float* y, void* stream);
 /* dx = dy * (y > 0)  (ReLU fused into a conv epilogue, e.g. F.relu(sal_conv(x)) baseline_attention.py:270) */
 /* out = inputs[0] + ... + inputs[count-1] in list order (count <= 32 host array of device pointers, n % 4 == 0): the gradient
- * fan-in of a tensor consumed by every decode step (x-gate pre-activations), one pass instead of count-1 adds */
-int sp_sum_n(const float* const* inputs, int count, int64_t n, float* out,
-             unsigned* out_amax /* nullable: float bits of max|out|, as sp_bn_apply's y_amax */, void* stream);
-/* ... with the masked-step sparsity of the backward pass (as sp_sum_n_mixed_rows below): term k belongs to decode step steps[k] (HOST
- * array; -1: never skipped) and is exactly zero, hence not read, for a sample b (n / nsamples contiguous elements, a multiple of 4) with
- * row_last[b] < steps[k] (row_last: device array [nsamples]); both NULL: sp_sum_n. */
-int sp_sum_n_rows(const float* const* inputs, int count, int64_t n, float* out, unsigned* out_amax, const int* row_last, const int* steps,
-                  int nsamples, void* stream);
+ * fan-in of a tensor consumed by every decode step (x-gate pre-activations), one pass instead of count-1 adds.
+ * out_amax (nullable): float bits of max|out|, as sp_bn_apply's y_amax.
+ * row_last / steps (both or neither, else SP_ENULL): the masked-step sparsity of the backward pass (AiR/models/loss.py:10-14,27-32: the loss
+ * multiplies by the masks): term k belongs to decode step steps[k] (HOST array [count]; -1: not tied to a step, never skipped) and is exactly
+ * zero, hence not read, for a sample b (n / nsamples contiguous elements, a multiple of 4) with row_last[b] < steps[k] (row_last: device
+ * array [nsamples]). */
+int sp_sum_n(const float* const* inputs, int count, int64_t n, float* out, unsigned* out_amax, const int* row_last, const int* steps,
+             int nsamples, void* stream);
 /* the same fan-in when some contributions exist only as 2xfp16 split operands (the gate gradient of a ConvLSTM step whose fp32 form
- * was left unwritten, sp_lstm_pointwise_bwd_split with dpre == NULL): inputs[k] != NULL -> fp32 term, else planes[k] / scales[k]
- * (sp_split2_f16 layout, device scale) -> the exact value of the split operand.  n % 16 == 0. */
+ * was left unwritten, sp_lstm_pointwise_bwd with dpre == NULL): inputs[k] != NULL -> fp32 term, else planes[k] / scales[k]
+ * (sp_split2_f16 layout, device scale) -> the exact value of the split operand.  n % 16 == 0; out_amax, row_last, steps, nsamples as for
+ * sp_sum_n with n / nsamples a multiple of 16. */
 int sp_sum_n_mixed(const float* const* inputs, const void* const* planes, const float* const* scales, int count, int64_t n, float* out,
-                   unsigned* out_amax, void* stream);
-/* ... with the masked-step sparsity of the backward pass (AiR/models/loss.py:10-14,27-32: the loss multiplies by the masks): term k is
- * the gate gradient of decode step steps[k] (-1: not tied to a step); for a sample b (n / nsamples contiguous elements each, a multiple of
- * 16) with row_last[b] < steps[k] the term is exactly zero and is not read.  row_last: device array [nsamples], steps: HOST array [count]; both or neither. */
-int sp_sum_n_mixed_rows(const float* const* inputs, const void* const* planes, const float* const* scales, int count, int64_t n, float* out,
-                        unsigned* out_amax, const int* row_last, const int* steps, int nsamples, void* stream);
+                   unsigned* out_amax, const int* row_last, const int* steps, int nsamples, void* stream);
 int sp_relu_bwd(const float* dy, const float* y, int64_t n, float* dx, void* stream);
 /* out = a + b (residual joins in backward), n elements */
 int sp_add(const float* a, const float* b, float* out, int64_t n, void* stream);
@@ -319,7 +310,6 @@ int sp_add(const float* a, const float* b, float* out, int64_t n, void* stream);
  * gates[rows][4C] keeps the activated gates for backward. */
 int sp_lstm_pointwise_fwd(const float* xg, const float* hg, const float* c_prev, int64_t rows, int C, float* gates,
                           float* c_out, float* h_out, void* stream);
-/* dpre[rows][4C], dc_prev[rows][C] from dh, dc (either may be NULL = 0) */
 /* the same cell with the rank-1 gate terms fused in: pre[b,p,g*C+c] += sum_k spcol[b,p,k] * wc[b,g*C+c,k] for the gates
  * g = i,f,o (spcol [B][P][KP] 9-tap im2col of the spatial memories, wc [B][3C][KP] per-sample contracted filters;
  * baseline_attention.py:40-50).  xg/hg/gates [B*P][4C]; C % 64 == 0, KP <= 64. */
@@ -333,47 +323,35 @@ int sp_rank1_dwc(const float* dpre, const float* spcol, int B, int P, int ld, in
                  void* stream);
 /* get_channel_semantic + ReLU (baseline_attention.py:246-250,284,324): out [B][S][C] = relu(alpha * sum_p a[s][b][p] * vf[b][p][c])
  * with alpha = 1/P (S <= 2 attention streams, C <= 512); backward returns d a [S][B][P] and d vf [B][P][C] in one pass over vf
- * (dout is masked by out > 0 inside).  workspace >= sp_sempool_workspace bytes (chunk partials, fixed-order reduce). */
+ * (dout is masked by out > 0 inside).  workspace >= sp_sempool_workspace bytes (chunk partials, fixed-order reduce).
+ * sbc != 0: the pooled rows / their gradient lie [S][B][C] (what the embedding behind them reads) instead of [B][S][C]: no transposed copy.
+ * row_last (nullable): samples b with row_last[b] < row_step have an exactly-zero dout (masked-step sparsity of the backward pass): their
+ * da / dvf rows are written as zeros, vf is not read. */
 int64_t sp_sempool_workspace(int S, int B, int P, int C);
-int sp_sempool_fwd(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace, float* out,
+int sp_sempool_fwd(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace, float* out, int sbc,
                    void* stream);
 int sp_sempool_bwd(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C, float alpha,
-                   float* da, float* dvf, void* stream);
-/* ... row_last != NULL: samples b with row_last[b] < row_step have an exactly-zero dout (masked-step sparsity of the backward pass): their
- * da / dvf rows are written as zeros, vf is not read */
-int sp_sempool_bwd_rows(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C, float alpha,
-                        float* da, float* dvf, const int* row_last, int row_step, void* stream);
-/* round 6: sbc != 0: the pooled rows / their gradient lie [S][B][C] (what the embedding behind them reads) instead of [B][S][C]: no transposed copy */
-int sp_sempool_fwd_sbc(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace, float* out, int sbc, void* stream);
-int sp_sempool_bwd_rows_sbc(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C, float alpha,
-                            float* da, float* dvf, const int* row_last, int row_step, int sbc, void* stream);
-int sp_lstm_pointwise_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev,
-                          const float* c_out, int64_t rows, int C, float* dpre, float* dc_prev,
-                          unsigned* dpre_amax /* nullable, as y_amax */, void* stream);
-/* as above, and (planes != NULL) dpre also as the 2xfp16 split operand of the h-gate conv's backward GEMMs, scale from the bound
+                   float* da, float* dvf, const int* row_last, int row_step, int sbc, void* stream);
+/* Backward of sp_lstm_pointwise_fwd / sp_lstm_rank1_fwd: dpre[rows][4C], dc_prev[rows][C] from dh, dc (either may be NULL = 0).
+ * dpre_amax / dcp_amax (nullable, as y_amax) receive max|dpre| / max|dc_prev|.
+ * planes != NULL: dpre also as the 2xfp16 split operand of the h-gate conv's backward GEMMs, scale from the bound
  * max(D, max|dh| * c_bound / 4, D * cprev_bound / 4), D = max|dh| + max|dc|  (dh_amax / dc_amax: device words with the float bits
- * of (bounds of) the maxima; c_bound >= max|c_out|, cprev_bound >= max|c_prev|: t + 1 and t after t + 1 steps).  dcp_amax
- * (nullable) receives max|dc_prev|.  planes: 2 * rows * 4C fp16 + 64 zero bytes; dpre_scale [2] = {scale, bound}.  C % 256 == 0.
- * dpre may be NULL when planes is given: the fp32 gate gradient is then not written (every consumer reads the split form). */
-int sp_lstm_pointwise_bwd_split(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c_out,
-                                int64_t rows, int C, float* dpre, float* dc_prev, unsigned* dpre_amax, unsigned* dcp_amax,
-                                const unsigned* dh_amax, const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
-                                float* dpre_scale, void* stream);
-/* the same with the row sparsity of sp_conv_desc.row_last: samples (rows_per_sample consecutive rows each) with row_last[sample] < row_step
- * get zero outputs without reading the inputs */
-int sp_lstm_pointwise_bwd_rows(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c_out,
-                               int64_t rows, int C, float* dpre, float* dc_prev, unsigned* dpre_amax, unsigned* dcp_amax,
-                               const unsigned* dh_amax, const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
-                               float* dpre_scale, const int* row_last, int row_step, int rows_per_sample, void* stream);
+ * of (bounds of) the maxima; c_bound >= max|c_out|, cprev_bound >= max|c_prev|: t + 1 and t after t + 1 steps).
+ * planes: 2 * rows * 4C fp16 + 64 zero bytes; dpre_scale [2] = {scale, bound}.  C % 256 == 0.
+ * dpre may be NULL when planes is given: the fp32 gate gradient is then not written (every consumer reads the split form).
+ * row_last (nullable): the row sparsity of sp_conv_desc.row_last: samples (rows_per_sample consecutive rows each) with
+ * row_last[sample] < row_step get zero outputs without reading the inputs. */
+int sp_lstm_pointwise_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c_out,
+                          int64_t rows, int C, float* dpre, float* dc_prev, unsigned* dpre_amax, unsigned* dcp_amax,
+                          const unsigned* dh_amax, const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
+                          float* dpre_scale, const int* row_last, int row_step, int rows_per_sample, void* stream);
 
-/* 3x3 zero-padded im2col of single-channel maps [R][H][W] into columns [koff,koff+9) of col[r][p][ldk], and adjoint.
+/* 3x3 zero-padded im2col of single-channel maps, all S streams in ONE launch: maps [S][R][H][W] -> col [R][H*W][ldk], stream s in columns
+ * [9 s, 9 s + 9), columns >= 9 S written as zeros (9 S <= ldk), and the adjoint dmaps [S][R][H][W].
  * Feeds the rank-1 gate convolutions conv3x3(W, spatial (x) semantic) (baseline_attention.py:40-50) and the
  * spatial attention score map (:111-124) as small GEMMs. */
-int sp_im2col3x3_1ch(const float* maps, int R, int H, int W, int koff, int ldk, float* col, void* stream);
-int sp_col2im3x3_1ch(const float* dcol, int R, int H, int W, int koff, int ldk, float* dmaps, void* stream);
-/* all S streams in ONE launch: maps [S][R][H][W] -> col [R][H*W][ldk] (columns >= 9 S written as zeros), and the adjoint dmaps [S][R][H][W] */
-int sp_im2col3x3_multi(const float* maps, int S, int R, int H, int W, int ldk, float* col, void* stream);
-int sp_col2im3x3_multi(const float* dcol, int S, int R, int H, int W, int ldk, float* dmaps, void* stream);
+int sp_im2col3x3_1ch(const float* maps, int S, int R, int H, int W, int ldk, float* col, void* stream);
+int sp_col2im3x3_1ch(const float* dcol, int S, int R, int H, int W, int ldk, float* dmaps, void* stream);
 
 /* attention over a growing memory list (semantic_att :77-88 / spatial_att :111-124 after removing the terms that are
  * constant along the softmax axis): score[t][r] = <L[t][r][:], u>; a = softmax_t; mem[r][:] = sum_t a[t][r]*L[t][r][:]
@@ -398,42 +376,30 @@ int sp_select_rows_bwd(const float* dout, const unsigned char* sel, int64_t rows
  *   col 0 terminate map (sal_layer_2 o 5x5), col 1 action map (sal_layer_3 o 5x5), cols 2..50 the 49 taps of
  *   drt_layer_1 o 5x5.  cb: composed biases [nheads][HC] (cb[.][51] = drt_layer_1.bias); w2/b2: drt_layer_2 [2][dh*dw],[2].
  * Outputs per head: logits [nheads][B][1+P] (col 0 = terminate; probabilities when softmax != 0, i.e. eval mode :161-162),
- * amap [nheads][B][P] (relu action map, always pre-softmax), mu/sigma2 [nheads][B], drt [nheads][B][dh*dw] (post-relu). */
+ * amap [nheads][B][P] (relu action map, always pre-softmax), mu/sigma2 [nheads][B], drt [nheads][B][dh*dw] (post-relu).
+ * parts selects the halves of the epilogue: bit 0 = the saliency half (terminate logit, action map, softmax: what the next memory update
+ * of the decode loop reads, AiR/models/baseline_attention.py:160-166,311-336), bit 1 = the duration half (mu, sigma2, :155-159: read by
+ * nothing inside the recurrence); 3 = both.  The decode loop runs parts = 1 per step and parts = 2 ONCE behind the loop over T x nheads
+ * virtual heads (head (t, i) of B rows; dpre = the sites of all steps from one sp_drt_direct_fwd launch over T x B rows).  Arguments of
+ * the half that is not asked for may be NULL. */
 int sp_head_finish_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb,
                        int cb_per_sample /* 1: cb is [B][nheads][HC] (COCO per-task heads) */, const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu,
                        float* sigma2, float* drt,
                        const float* dpre /* nullable: [nheads][B][dh*dw] duration-site sums incl. composed tap biases (sp_drt_direct_fwd);
-                                            then Z needs only the 2 map columns per head */,
-                       int zc /* Z columns per head (<= 0: HC) */, void* stream);
-/* dlogits is the gradient w.r.t. the `logits` output (probabilities if softmax).  dZ is fully written for the nheads*HC
- * columns.  Partials are per sample: dcb [B][nheads][HC], dw2 [B][nheads][2][dh*dw], db2 [B][nheads][2]. */
-int sp_head_finish_bwd(const float* dlogits, const float* damap /* nullable, [nheads][B][P] */, const float* dmu,
-                       const float* dsigma2, const float* logits,
-                       const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm, int ldz,
-                       int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
+                                            then Z needs only the 2 map columns per head; required when parts == 2 */,
+                       int zc /* Z columns per head (<= 0: HC) */, int parts, void* stream);
+/* dlogits is the gradient w.r.t. the `logits` output (probabilities if softmax); dlogits_ld = elements between its (head, sample) rows
+ * (0 = Hm*Wm + 1): a slice of the stacked outputs' gradient is read in place.  dZ is fully written for the nheads*HC
+ * columns.  Partials are per sample: dcb [B][nheads][HC], dw2 [B][nheads][2][dh*dw], db2 [B][nheads][2].  parts as in the forward pass:
+ * parts = 1 writes dcb[0], dcb[1] (others zero), parts = 2 writes dcb[51] (others zero).  live (nullable out, parts & 2):
+ * live[hd * B + b] = 1 iff slot hd of row b received a non-zero dmu or dsigma2 -- the duration sites' backward (sp_drt_direct_bwd_data /
+ * _weight) skips the others: their site gradients are exact zeros. */
+int sp_head_finish_bwd(const float* dlogits, int64_t dlogits_ld, const float* damap /* nullable, [nheads][B][P] */, const float* dmu,
+                       const float* dsigma2, const float* logits, const float* amap, const float* sigma2, const float* drt, int B, int Hm,
+                       int Wm, int ldz, int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
                        float* dw2_partial, float* db2_partial,
-                       float* ddpre /* nullable out, gradient of dpre; tap columns of dZ / dcb are then not produced */, int zc,
-                       void* stream);
-
-/* The two halves of the epilogue separately (round 6).  parts: bit 0 = the saliency half (terminate logit, action map, softmax: what the next
- * memory update of the decode loop reads, AiR/models/baseline_attention.py:160-166,311-336), bit 1 = the duration half (mu, sigma2, :155-159:
- * read by nothing inside the recurrence).  The decode loop runs parts = 1 per step and parts = 2 ONCE behind the loop over T x nheads virtual
- * heads (head (t, i) of B rows; dpre = the sites of all steps from one sp_drt_direct_fwd launch over T x B rows).  Arguments of the half that
- * is not asked for may be NULL; parts = 3 is sp_head_finish_fwd / _bwd.  parts = 1 writes dcb[0], dcb[1] (others zero), parts = 2 writes
- * dcb[51] (others zero).  live (nullable, parts & 2): live[hd * B + b] = 1 iff slot hd of row b received a non-zero dmu or dsigma2 -- the
- * duration sites' backward (sp_drt_direct_bwd_*_live) skips the others: their site gradients are exact zeros. */
-int sp_head_finish_parts_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb, int cb_per_sample,
-                             const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu, float* sigma2, float* drt,
-                             const float* dpre, int zc, int parts, void* stream);
-int sp_head_finish_parts_bwd(const float* dlogits, const float* damap, const float* dmu, const float* dsigma2, const float* logits,
-                             const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm, int ldz, int nheads, int HC,
-                             const float* w2, int softmax, float* dZ, float* dcb_partial, float* dw2_partial, float* db2_partial,
-                             float* ddpre, int zc, int parts, int* live, void* stream);
-/* round 6: dlogits_ld = elements between the (head, sample) rows of dlogits (0 = Hm*Wm + 1): a slice of the stacked outputs' gradient, read in place */
-int sp_head_finish_parts_bwd_ld(const float* dlogits, int64_t dlogits_ld, const float* damap, const float* dmu, const float* dsigma2,
-                                const float* logits, const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm, int ldz,
-                                int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial, float* dw2_partial,
-                                float* db2_partial, float* ddpre, int zc, int parts, int* live, void* stream);
+                       float* ddpre /* nullable out, gradient of dpre; tap columns of dZ / dcb are then not produced; required when parts == 2 */,
+                       int zc, int parts, int* live, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * predict_head without the dense 5x5 GEMM (models/baseline_attention.py:149-158), csrc/head_direct.hip.
@@ -452,29 +418,21 @@ int sp_head_compose11_fwd(const float* G, const float* cb, int nheads, int HC, i
 int sp_head_compose11_bwd(const float* dW11, const float* dcbsum, int nheads, int HC, int C, int Hm, int Wm, float* dG,
                           float* dcb, void* stream);
 int sp_sal_gather_fwd(const float* T, int B, int Hm, int Wm, int ldt, int nsel, const int* hmap, float* Z2, void* stream);
+/* row_last (nullable): samples b with row_last[b] < row_step have an exactly-zero dZ2: their dT rows are zeros, dZ2 is not read */
 int sp_sal_gather_bwd(const float* dZ2, int B, int Hm, int Wm, int ldt, int nsel, int nsrc, const int* hmap, float* dT,
-                      void* stream);
-/* ... row_last != NULL: samples b with row_last[b] < row_step have an exactly-zero dZ2: their dT rows are zeros, dZ2 is not read */
-int sp_sal_gather_bwd_rows(const float* dZ2, int B, int Hm, int Wm, int ldt, int nsel, int nsrc, const int* hmap, float* dT,
-                           const int* row_last, int row_step, void* stream);
+                      const int* row_last, int row_step, void* stream);
 int sp_drt_direct_fwd(const float* h, const float* W11, const float* cbsum, const int* hmap, int B, int Hm, int Wm, int C,
                       int nsel, float* Dpre, void* stream);
+/* Both gradients skip the (row, head slot) pairs whose gradient is exactly zero (bit-identical sums): live (nullable) [nsel][B] from
+ * sp_head_finish_bwd; row_last (nullable): row b -- decode step b / rowB of sample b % rowB when one launch covers several steps, rowB = B
+ * for a per-step launch -- is dead when row_last[b % rowB] < row_step + b / rowB (B % rowB == 0).  Dead rows of dh are written as zeros;
+ * the weight gradient's slabs of dead rows are zeros and h is not read for them.  workspace >= sp_drt_direct_bwd_weight_workspace bytes. */
 int sp_drt_direct_bwd_data(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C, int nsel,
-                           int accumulate, float* dh, void* stream);
-/* ... with the (row, head slot) pairs whose gradient is exactly zero skipped (bit-identical sums): live (nullable) [nsel][B] from
- * sp_head_finish_parts_bwd; row_last (nullable): row b -- decode step b / rowB of sample b % rowB when one launch covers several steps, rowB = B
- * for a per-step launch -- is dead when row_last[b % rowB] < row_step + b / rowB (B % rowB == 0).  Dead rows of dh are written as zeros. */
-int sp_drt_direct_bwd_data_live(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C, int nsel,
-                                int accumulate, float* dh, const int* live, const int* row_last, int row_step, int rowB, void* stream);
-int sp_drt_direct_bwd_weight_live(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C, int nsel, int nheads,
-                                  void* workspace, float* dW11, float* dcbsum, const int* live, const int* row_last, int row_step, int rowB,
-                                  void* stream);
+                           int accumulate, float* dh, const int* live, const int* row_last, int row_step, int rowB, void* stream);
 int64_t sp_drt_direct_bwd_weight_workspace(int B, int Hm, int Wm, int C, int nsel);
-int sp_drt_direct_bwd_weight(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C, int nsel,
-                             int nheads, void* workspace, float* dW11, float* dcbsum, void* stream);
-/* ... row_last != NULL: samples b with row_last[b] < row_step have an exactly-zero dDpre: their slabs are zeros, h is not read */
-int sp_drt_direct_bwd_weight_rows(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C, int nsel,
-                                  int nheads, void* workspace, float* dW11, float* dcbsum, const int* row_last, int row_step, void* stream);
+int sp_drt_direct_bwd_weight(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C, int nsel, int nheads,
+                             void* workspace, float* dW11, float* dcbsum, const int* live, const int* row_last, int row_step, int rowB,
+                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Skinny fp32 GEMM (round 5): C[M <= 64][N] = relu?(alpha * A[M][K] * op(B) + bias[N]) on fp32 MFMA, the weight matrix streamed once

@@ -729,41 +729,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* x, int N,
     }
 }
 
-// gather form (no atomics): each input element sums dy of the windows whose FIRST maximum it is.
-__global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* dy, const float* x, const float* y, int N, int H,
-                                                          int W, int C, float* dx, int Ho, int Wo) {
-    const int64_t total = (int64_t)N * H * W * C;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        int64_t r = i / C;
-        const int ix = (int)(r % W); r /= W;
-        const int iy = (int)(r % H);
-        const int n = (int)(r / H);
-        const float v = x[i];
-        float g = 0.f;
-        const int oy_lo = max(0, (iy - 1) / 2), oy_hi = min(Ho - 1, iy / 2);   // windows with 2*oy <= iy <= 2*oy+2
-        const int ox_lo = max(0, (ix - 1) / 2), ox_hi = min(Wo - 1, ix / 2);
-        for (int oy = oy_lo; oy <= oy_hi; ++oy) {
-            if (iy - 2 * oy > 2) continue;
-            for (int ox = ox_lo; ox <= ox_hi; ++ox) {
-                if (ix - 2 * ox > 2) continue;
-                const int64_t o = (((int64_t)n * Ho + oy) * Wo + ox) * C + c;
-                if (y[o] != v) continue;
-                // am I the first element equal to the max in this window (row-major scan, strict >)?
-                const int mine = (iy - 2 * oy) * 3 + (ix - 2 * ox);
-                bool first = true;
-                for (int q = 0; q < mine; ++q) {
-                    const int yy = oy * 2 + q / 3, xx = ox * 2 + q % 3;
-                    if (yy < H && xx < W && x[(((int64_t)n * H + yy) * W + xx) * C + c] == v) { first = false; break; }
-                }
-                if (first) g += dy[o];
-            }
-        }
-        dx[i] = g;
-    }
-}
-
-// the same with the forward's saved window positions: no value comparisons, no reads of x / y; float4 over the channels
+// gather form (no atomics): each input element sums dy of the windows whose FIRST maximum it is, known from the forward's saved window
+// positions: no value comparisons, no reads of x / y; float4 over the channels
 __global__ __launch_bounds__(256) void maxpool_bwd_idx_kernel(const float* dy, const unsigned char* amx, int N, int H, int W,
                                                               int C, float* dx, int Ho, int Wo) {
     const int C4 = C / 4;
@@ -1120,12 +1087,8 @@ extern "C" int sp_rowsum_bwd(const float* dout, int64_t M, int C, float scale, f
     return SP_OK;
 }
 
-extern "C" int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, int Ho, int Wo, void* stream) {
-    return sp_maxpool3s2_fwd_idx(x, N, H, W, C, y, nullptr, Ho, Wo, stream);
-}
-
-extern "C" int sp_maxpool3s2_fwd_idx(const float* x, int N, int H, int W, int C, float* y, unsigned char* argmax, int Ho, int Wo,
-                                     void* stream) {
+extern "C" int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* argmax, int Ho, int Wo,
+                                 void* stream) {
     if (!x || !y) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
     const int64_t total = (int64_t)N * Ho * Wo * (C / 4);
@@ -1135,22 +1098,12 @@ extern "C" int sp_maxpool3s2_fwd_idx(const float* x, int N, int H, int W, int C,
     return SP_OK;
 }
 
-extern "C" int sp_maxpool3s2_bwd_idx(const float* dy, const unsigned char* argmax, int N, int H, int W, int C, float* dx, int Ho,
-                                     int Wo, void* stream) {
+extern "C" int sp_maxpool3s2_bwd(const float* dy, const unsigned char* argmax, int N, int H, int W, int C, float* dx, int Ho,
+                                 int Wo, void* stream) {
     if (!dy || !argmax || !dx) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
     const int64_t total = (int64_t)N * H * W * (C / 4);
     hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(ew_blocks(total) * 4), dim3(256), 0, (hipStream_t)stream, dy, argmax, N, H, W,
-                       C, dx, Ho, Wo);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
-}
-
-extern "C" int sp_maxpool3s2_bwd(const float* dy, const float* x, const float* y, int N, int H, int W, int C, float* dx,
-                                 int Ho, int Wo, void* stream) {
-    if (!dy || !x || !y || !dx) return SP_ENULL;
-    const int64_t total = (int64_t)N * H * W * C;
-    hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_blocks(total) * 4), dim3(256), 0, (hipStream_t)stream, dy, x, y, N, H, W,
                        C, dx, Ho, Wo);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1187,8 +1140,8 @@ extern "C" int sp_add(const float* a, const float* b, float* out, int64_t n, voi
     return SP_OK;
 }
 
-extern "C" int sp_sum_n_rows(const float* const* inputs, int count, int64_t n, float* out, unsigned* out_amax, const int* row_last,
-                             const int* steps, int nsamples, void* stream) {
+extern "C" int sp_sum_n(const float* const* inputs, int count, int64_t n, float* out, unsigned* out_amax, const int* row_last,
+                        const int* steps, int nsamples, void* stream) {
     if (!inputs || !out) return SP_ENULL;
     if (count < 1 || count > 32 || n % 4) return SP_EINVAL;
     if ((row_last != nullptr) != (steps != nullptr)) return SP_ENULL;
@@ -1208,12 +1161,9 @@ extern "C" int sp_sum_n_rows(const float* const* inputs, int count, int64_t n, f
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
-extern "C" int sp_sum_n(const float* const* inputs, int count, int64_t n, float* out, unsigned* out_amax, void* stream) {
-    return sp_sum_n_rows(inputs, count, n, out, out_amax, nullptr, nullptr, 0, stream);
-}
 
-extern "C" int sp_sum_n_mixed_rows(const float* const* inputs, const void* const* planes, const float* const* scales, int count, int64_t n,
-                                   float* out, unsigned* out_amax, const int* row_last, const int* steps, int nsamples, void* stream) {
+extern "C" int sp_sum_n_mixed(const float* const* inputs, const void* const* planes, const float* const* scales, int count, int64_t n,
+                              float* out, unsigned* out_amax, const int* row_last, const int* steps, int nsamples, void* stream) {
     if (!inputs || !planes || !scales || !out) return SP_ENULL;
     if (count < 1 || count > 32 || n % 16) return SP_EINVAL;
     if ((row_last != nullptr) != (steps != nullptr)) return SP_ENULL;
@@ -1234,10 +1184,6 @@ extern "C" int sp_sum_n_mixed_rows(const float* const* inputs, const void* const
     hipLaunchKernelGGL(sum_n_mixed_kernel, dim3(ew_blocks(n / 16)), dim3(256), 0, (hipStream_t)stream, l, out, n / 16, out_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
-}
-extern "C" int sp_sum_n_mixed(const float* const* inputs, const void* const* planes, const float* const* scales, int count, int64_t n,
-                              float* out, unsigned* out_amax, void* stream) {
-    return sp_sum_n_mixed_rows(inputs, planes, scales, count, n, out, out_amax, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int sp_relu_bwd(const float* dy, const float* y, int64_t n, float* dx, void* stream) {

@@ -2066,18 +2066,12 @@ extern "C" int sp_split2_f16_rows(const float* w, int64_t rows, int64_t K, int K
     return SP_OK;
 }
 
-extern "C" int sp_split2_f16_wT_rows_batched(const float* w, int nbatch, int Co, int taps, int Ci, const float* absorb, void* out,
-                                             float* row_scale, void* stream);
 // w [Co][taps][Ci] -> rows ci, k = (tap, co): the data gradient's weight operand with one scale per row (input channel);
-// absorb [Co] nullable: the channel scales of the gradient operand it meets
-extern "C" int sp_split2_f16_wT_rows(const float* w, int Co, int taps, int Ci, const float* absorb, void* out, float* row_scale,
-                                     void* stream) {
-    return sp_split2_f16_wT_rows_batched(w, 1, Co, taps, Ci, absorb, out, row_scale, stream);
-}
+// absorb [Co] nullable: the channel scales of the gradient operand it meets.
 // nbatch matrices [Co][taps][Ci] one behind the other -> nbatch * Ci rows (item-major), one scale per row: the rank-1 filters wc [B][3C][KP]
 // as the B operand [B*KP][3C] of their data gradient in ONE launch (a transposed copy + sp_split2_f16_rows before)
-extern "C" int sp_split2_f16_wT_rows_batched(const float* w, int nbatch, int Co, int taps, int Ci, const float* absorb, void* out,
-                                             float* row_scale, void* stream) {
+extern "C" int sp_split2_f16_wT_rows(const float* w, int nbatch, int Co, int taps, int Ci, const float* absorb, void* out,
+                                     float* row_scale, void* stream) {
     if (!w || !out || !row_scale) return SP_ENULL;
     if (nbatch < 1 || nbatch > 65535 || ((int64_t)taps * Co) % 16 || Ci % 4 || Ci < 4 || ((uintptr_t)w & 15)) return SP_EINVAL;
     hipLaunchKernelGGL(split2_wT_rows_kernel, dim3(Ci / 4, nbatch), dim3(256), 0, (hipStream_t)stream, w, Co, taps, Ci, absorb, (uint16_t*)out,

@@ -407,24 +407,9 @@ __global__ __launch_bounds__(256) void lstm_bwd_kernel(const float* dh, const fl
 }
 
 // ------------------------------------------------------------------------------------------------
-// 3x3 zero-padded im2col of 1-channel maps into columns [koff, koff+9) of col[r][p][ldk], and adjoint.
+// 3x3 zero-padded im2col of 1-channel maps, all S streams in one launch: maps [S][R][H][W] -> col [R][H*W][ldk], stream s in columns
+// [9 s, 9 s + 9), columns >= 9 S zero; and its adjoint dmaps [S][R][H][W].
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void im2col1_kernel(const float* maps, int R, int H, int W, int koff, int ldk, float* col) {
-    const int64_t total = (int64_t)R * H * W * 9;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int tap = (int)(i % 9);
-        int64_t q = i / 9;
-        const int x = (int)(q % W); q /= W;
-        const int y = (int)(q % H);
-        const int r = (int)(q / H);
-        const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-        float v = 0.f;
-        if ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) v = maps[((int64_t)r * H + yy) * W + xx];
-        col[(((int64_t)r * H + y) * W + x) * ldk + koff + tap] = v;
-    }
-}
-// all S streams in one launch: maps [S][R][H][W] -> col [R][H*W][ldk], stream s in columns [9 s, 9 s + 9), columns >= 9 S zero (the decode
-// loop ran a zero-fill and one launch per stream per step); and its adjoint dmaps [S][R][H][W]
 __global__ __launch_bounds__(256) void im2col1_multi_kernel(const float* __restrict__ maps, int S, int R, int H, int W, int ldk, float* __restrict__ col) {
     const int64_t total = (int64_t)R * H * W * ldk;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
@@ -452,30 +437,13 @@ __global__ __launch_bounds__(256) void col2im1_multi_kernel(const float* __restr
         const int s = (int)(q / R);
         float acc = 0.f;
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {          // same order as col2im1_kernel: identical sums
+        for (int tap = 0; tap < 9; ++tap) {
+            // col[(y0,x0)][tap] = map[y0+ky-1][x0+kx-1]  ->  (y0,x0) = (y-ky+1, x-kx+1)
             const int y0 = y - (tap / 3 - 1), x0 = x - (tap % 3 - 1);
             if ((unsigned)y0 < (unsigned)H && (unsigned)x0 < (unsigned)W)
                 acc += dcol[(((int64_t)r * H + y0) * W + x0) * ldk + 9 * s + tap];
         }
         dmaps[i] = acc;
-    }
-}
-__global__ __launch_bounds__(256) void col2im1_kernel(const float* dcol, int R, int H, int W, int koff, int ldk, float* dmaps) {
-    const int64_t total = (int64_t)R * H * W;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        int64_t q = i;
-        const int x = (int)(q % W); q /= W;
-        const int y = (int)(q % H);
-        const int r = (int)(q / H);
-        float s = 0.f;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            // col[(y0,x0)][tap] = map[y0+ky-1][x0+kx-1]  ->  (y0,x0) = (y-ky+1, x-kx+1)
-            const int y0 = y - (tap / 3 - 1), x0 = x - (tap % 3 - 1);
-            if ((unsigned)y0 < (unsigned)H && (unsigned)x0 < (unsigned)W)
-                s += dcol[(((int64_t)r * H + y0) * W + x0) * ldk + koff + tap];
-        }
-        dmaps[i] = s;
     }
 }
 
@@ -850,20 +818,12 @@ extern "C" int sp_rank1_dwc(const float* dpre, const float* spcol, int B, int P,
     return SP_OK;
 }
 
-extern "C" int sp_sempool_fwd_sbc(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace, float* out, int sbc,
-                                  void* stream);
-extern "C" int sp_sempool_bwd_rows_sbc(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C, float alpha,
-                                       float* da, float* dvf, const int* row_last, int row_step, int sbc, void* stream);
 extern "C" int64_t sp_sempool_workspace(int S, int B, int P, int C) {
     return (int64_t)((P + SP_PCH - 1) / SP_PCH) * B * S * C * (int64_t)sizeof(float);
 }
 
 extern "C" int sp_sempool_fwd(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace,
-                              float* out, void* stream) {
-    return sp_sempool_fwd_sbc(a, vf, S, B, P, C, alpha, workspace, out, 0, stream);
-}
-extern "C" int sp_sempool_fwd_sbc(const float* a, const float* vf, int S, int B, int P, int C, float alpha, void* workspace,
-                                  float* out, int sbc, void* stream) {
+                              float* out, int sbc, void* stream) {
     if (!a || !vf || !workspace || !out) return SP_ENULL;
     if (S < 1 || S > 2 || B < 1 || P < 1 || C % 4 || C > 512) return SP_EINVAL;
     const int64_t osb = sbc ? C : (int64_t)S * C, oss = sbc ? (int64_t)B * C : C;
@@ -877,12 +837,8 @@ extern "C" int sp_sempool_fwd_sbc(const float* a, const float* vf, int S, int B,
     return SP_OK;
 }
 
-extern "C" int sp_sempool_bwd_rows(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C,
-                                   float alpha, float* da, float* dvf, const int* row_last, int row_step, void* stream) {
-    return sp_sempool_bwd_rows_sbc(dout, out, a, vf, S, B, P, C, alpha, da, dvf, row_last, row_step, 0, stream);
-}
-extern "C" int sp_sempool_bwd_rows_sbc(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C,
-                                       float alpha, float* da, float* dvf, const int* row_last, int row_step, int sbc, void* stream) {
+extern "C" int sp_sempool_bwd(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C,
+                              float alpha, float* da, float* dvf, const int* row_last, int row_step, int sbc, void* stream) {
     if (!dout || !out || !a || !vf || !da || !dvf) return SP_ENULL;
     if (S < 1 || S > 2 || B < 1 || P < 1 || C % 4) return SP_EINVAL;
     const int64_t zsb = sbc ? C : (int64_t)S * C, zss = sbc ? (int64_t)B * C : C;
@@ -891,23 +847,12 @@ extern "C" int sp_sempool_bwd_rows_sbc(const float* dout, const float* out, cons
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
-extern "C" int sp_sempool_bwd(const float* dout, const float* out, const float* a, const float* vf, int S, int B, int P, int C,
-                              float alpha, float* da, float* dvf, void* stream) {
-    return sp_sempool_bwd_rows(dout, out, a, vf, S, B, P, C, alpha, da, dvf, nullptr, 0, stream);
-}
 
 extern "C" int sp_lstm_pointwise_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev,
-                                     const float* c_out, int64_t rows, int C, float* dpre, float* dc_prev, unsigned* dpre_amax,
-                                     void* stream) {
-    return sp_lstm_pointwise_bwd_split(dh, dc, gates, c_prev, c_out, rows, C, dpre, dc_prev, dpre_amax, nullptr, nullptr, nullptr,
-                                       0.f, 0.f, nullptr, nullptr, stream);
-}
-
-extern "C" int sp_lstm_pointwise_bwd_rows(const float* dh, const float* dc, const float* gates, const float* c_prev,
-                                          const float* c_out, int64_t rows, int C, float* dpre, float* dc_prev,
-                                          unsigned* dpre_amax, unsigned* dcp_amax, const unsigned* dh_amax,
-                                          const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
-                                          float* dpre_scale, const int* row_last, int row_step, int rows_per_sample, void* stream) {
+                                     const float* c_out, int64_t rows, int C, float* dpre, float* dc_prev,
+                                     unsigned* dpre_amax, unsigned* dcp_amax, const unsigned* dh_amax,
+                                     const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
+                                     float* dpre_scale, const int* row_last, int row_step, int rows_per_sample, void* stream) {
     if (!gates || !c_out || (!dpre && !planes) || !dc_prev) return SP_ENULL;      // dpre may be NULL when the split form is written
     if (C % 4) return SP_EINVAL;
     if (planes && (!dpre_scale || C % 256 || ((uintptr_t)planes & 15) || (dh && !dh_amax) || (dc && !dc_amax))) return SP_EINVAL;
@@ -921,44 +866,17 @@ extern "C" int sp_lstm_pointwise_bwd_rows(const float* dh, const float* dc, cons
     return SP_OK;
 }
 
-extern "C" int sp_lstm_pointwise_bwd_split(const float* dh, const float* dc, const float* gates, const float* c_prev,
-                                           const float* c_out, int64_t rows, int C, float* dpre, float* dc_prev,
-                                           unsigned* dpre_amax, unsigned* dcp_amax, const unsigned* dh_amax,
-                                           const unsigned* dc_amax, float c_bound, float cprev_bound, void* planes,
-                                           float* dpre_scale, void* stream) {
-    return sp_lstm_pointwise_bwd_rows(dh, dc, gates, c_prev, c_out, rows, C, dpre, dc_prev, dpre_amax, dcp_amax, dh_amax, dc_amax, c_bound,
-                                      cprev_bound, planes, dpre_scale, nullptr, 0, 1, stream);
-}
-
-extern "C" int sp_im2col3x3_1ch(const float* maps, int R, int H, int W, int koff, int ldk, float* col, void* stream) {
-    if (!maps || !col) return SP_ENULL;
-    if (koff + 9 > ldk) return SP_EINVAL;
-    hipLaunchKernelGGL(im2col1_kernel, dim3(ew_blocks((int64_t)R * H * W * 9)), dim3(256), 0, (hipStream_t)stream, maps, R, H,
-                       W, koff, ldk, col);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
-}
-
-extern "C" int sp_im2col3x3_multi(const float* maps, int S, int R, int H, int W, int ldk, float* col, void* stream) {
+extern "C" int sp_im2col3x3_1ch(const float* maps, int S, int R, int H, int W, int ldk, float* col, void* stream) {
     if (!maps || !col) return SP_ENULL;
     if (S < 1 || 9 * S > ldk) return SP_EINVAL;
     hipLaunchKernelGGL(im2col1_multi_kernel, dim3(ew_blocks((int64_t)R * H * W * ldk)), dim3(256), 0, (hipStream_t)stream, maps, S, R, H, W, ldk, col);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
-extern "C" int sp_col2im3x3_multi(const float* dcol, int S, int R, int H, int W, int ldk, float* dmaps, void* stream) {
+extern "C" int sp_col2im3x3_1ch(const float* dcol, int S, int R, int H, int W, int ldk, float* dmaps, void* stream) {
     if (!dcol || !dmaps) return SP_ENULL;
     if (S < 1 || 9 * S > ldk) return SP_EINVAL;
     hipLaunchKernelGGL(col2im1_multi_kernel, dim3(ew_blocks((int64_t)S * R * H * W)), dim3(256), 0, (hipStream_t)stream, dcol, S, R, H, W, ldk, dmaps);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
-}
-
-extern "C" int sp_col2im3x3_1ch(const float* dcol, int R, int H, int W, int koff, int ldk, float* dmaps, void* stream) {
-    if (!dcol || !dmaps) return SP_ENULL;
-    if (koff + 9 > ldk) return SP_EINVAL;
-    hipLaunchKernelGGL(col2im1_kernel, dim3(ew_blocks((int64_t)R * H * W)), dim3(256), 0, (hipStream_t)stream, dcol, R, H, W,
-                       koff, ldk, dmaps);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1015,9 +933,9 @@ extern "C" int sp_select_rows_bwd(const float* dout, const unsigned char* sel, i
     return SP_OK;
 }
 
-extern "C" int sp_head_finish_parts_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb,
-                                        int cb_per_sample, const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu,
-                                        float* sigma2, float* drt, const float* dpre, int zc, int parts, void* stream) {
+extern "C" int sp_head_finish_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb,
+                                  int cb_per_sample, const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu,
+                                  float* sigma2, float* drt, const float* dpre, int zc, int parts, void* stream) {
     if (parts < 1 || parts > 3 || B < 1 || nheads < 1) return SP_EINVAL;
     if (!cb) return SP_ENULL;
     if ((parts & 1) && (!Z || !logits || !amap)) return SP_ENULL;
@@ -1033,29 +951,11 @@ extern "C" int sp_head_finish_parts_fwd(const float* Z, int B, int Hm, int Wm, i
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
-extern "C" int sp_head_finish_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb,
-                                  int cb_per_sample, const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu,
-                                  float* sigma2, float* drt, const float* dpre, int zc, void* stream) {
-    return sp_head_finish_parts_fwd(Z, B, Hm, Wm, ldz, nheads, HC, cb, cb_per_sample, w2, b2, softmax, logits, amap, mu, sigma2, drt, dpre, zc, 3,
-                                    stream);
-}
 
-extern "C" int sp_head_finish_parts_bwd_ld(const float* dlogits, int64_t dlogits_ld, const float* damap, const float* dmu, const float* dsigma2,
-                                           const float* logits, const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm,
-                                           int ldz, int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
-                                           float* dw2_partial, float* db2_partial, float* ddpre, int zc, int parts, int* live, void* stream);
-extern "C" int sp_head_finish_parts_bwd(const float* dlogits, const float* damap, const float* dmu, const float* dsigma2,
-                                        const float* logits,
-                                        const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm, int ldz,
-                                        int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
-                                        float* dw2_partial, float* db2_partial, float* ddpre, int zc, int parts, int* live, void* stream) {
-    return sp_head_finish_parts_bwd_ld(dlogits, 0, damap, dmu, dsigma2, logits, amap, sigma2, drt, B, Hm, Wm, ldz, nheads, HC, w2, softmax, dZ,
-                                       dcb_partial, dw2_partial, db2_partial, ddpre, zc, parts, live, stream);
-}
-extern "C" int sp_head_finish_parts_bwd_ld(const float* dlogits, int64_t dlogits_ld, const float* damap, const float* dmu, const float* dsigma2,
-                                           const float* logits, const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm,
-                                           int ldz, int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
-                                           float* dw2_partial, float* db2_partial, float* ddpre, int zc, int parts, int* live, void* stream) {
+extern "C" int sp_head_finish_bwd(const float* dlogits, int64_t dlogits_ld, const float* damap, const float* dmu, const float* dsigma2,
+                                  const float* logits, const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm,
+                                  int ldz, int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
+                                  float* dw2_partial, float* db2_partial, float* ddpre, int zc, int parts, int* live, void* stream) {
     if (parts < 1 || parts > 3 || B < 1 || nheads < 1) return SP_EINVAL;
     if (dlogits_ld == 0) dlogits_ld = (int64_t)Hm * Wm + 1;
     if (dlogits_ld < (int64_t)Hm * Wm + 1) return SP_EINVAL;
@@ -1073,12 +973,4 @@ extern "C" int sp_head_finish_parts_bwd_ld(const float* dlogits, int64_t dlogits
                        dlogits_ld);
     SP_LAUNCH_CHECK();
     return SP_OK;
-}
-extern "C" int sp_head_finish_bwd(const float* dlogits, const float* damap, const float* dmu, const float* dsigma2,
-                                  const float* logits,
-                                  const float* amap, const float* sigma2, const float* drt, int B, int Hm, int Wm, int ldz,
-                                  int nheads, int HC, const float* w2, int softmax, float* dZ, float* dcb_partial,
-                                  float* dw2_partial, float* db2_partial, float* ddpre, int zc, void* stream) {
-    return sp_head_finish_parts_bwd(dlogits, damap, dmu, dsigma2, logits, amap, sigma2, drt, B, Hm, Wm, ldz, nheads, HC, w2, softmax, dZ,
-                                    dcb_partial, dw2_partial, db2_partial, ddpre, zc, 3, nullptr, stream);
 }

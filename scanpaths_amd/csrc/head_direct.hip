@@ -261,7 +261,7 @@ __global__ __launch_bounds__(256) void drt_fwd_kernel(const float* __restrict__ 
 // one launch behind the decode loop, B = T x batch "virtual" rows, row b = decode step b / rowB of sample b % rowB):
 //   row_last (nullable): the sample's last decode step with any loss gradient (functional._OutputGate) -- row b is DEAD when
 //                        row_last[b % rowB] < row_step + b / rowB (per-step launches: rowB = B, i.e. the old row_last[b] < row_step);
-//   live (nullable):     live[i * B + b] = 0 when slot i of row b received dmu == 0 and dsigma2 == 0 exactly (sp_head_finish_parts_bwd):
+//   live (nullable):     live[i * B + b] = 0 when slot i of row b received dmu == 0 and dsigma2 == 0 exactly (sp_head_finish_bwd):
 //                        AiR's unselected head, the step right at a scanpath's end (action mask on, duration mask off).
 // Skipping them leaves every sum bit-identical (their terms are exact zeros; the reduce order of the others does not change).
 __device__ __forceinline__ bool drt_row_dead(const int* __restrict__ row_last, int row_step, int rowB, int b) {
@@ -487,18 +487,14 @@ extern "C" int sp_sal_gather_fwd(const float* T, int B, int Hm, int Wm, int ldt,
     return SP_OK;
 }
 
-extern "C" int sp_sal_gather_bwd_rows(const float* dZ2, int B, int Hm, int Wm, int ldt, int nsel, int nsrc, const int* hmap,
-                                      float* dT, const int* row_last, int row_step, void* stream) {
+extern "C" int sp_sal_gather_bwd(const float* dZ2, int B, int Hm, int Wm, int ldt, int nsel, int nsrc, const int* hmap,
+                                 float* dT, const int* row_last, int row_step, void* stream) {
     if (!dZ2 || !hmap || !dT) return SP_ENULL;
     if (B < 1 || nsel < 1 || nsrc < 1 || ldt < nsrc * 50) return SP_EINVAL;
     hipLaunchKernelGGL(sal_gather_bwd_kernel, dim3(ew_grid((int64_t)B * Hm * Wm * ldt)), dim3(256), 0, (hipStream_t)stream, dZ2,
                        B, Hm, Wm, ldt, nsel, nsrc, hmap, dT, row_last, row_step);
     SP_LAUNCH_CHECK();
     return SP_OK;
-}
-extern "C" int sp_sal_gather_bwd(const float* dZ2, int B, int Hm, int Wm, int ldt, int nsel, int nsrc, const int* hmap,
-                                 float* dT, void* stream) {
-    return sp_sal_gather_bwd_rows(dZ2, B, Hm, Wm, ldt, nsel, nsrc, hmap, dT, nullptr, 0, stream);
 }
 
 extern "C" int sp_drt_direct_fwd(const float* h, const float* W11, const float* cbsum, const int* hmap, int B, int Hm, int Wm,
@@ -512,9 +508,9 @@ extern "C" int sp_drt_direct_fwd(const float* h, const float* W11, const float* 
     return SP_OK;
 }
 
-extern "C" int sp_drt_direct_bwd_data_live(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C,
-                                           int nsel, int accumulate, float* dh, const int* live, const int* row_last, int row_step, int rowB,
-                                           void* stream) {
+extern "C" int sp_drt_direct_bwd_data(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C,
+                                      int nsel, int accumulate, float* dh, const int* live, const int* row_last, int row_step, int rowB,
+                                      void* stream) {
     if (!dDpre || !W11 || !hmap || !dh) return SP_ENULL;
     AxisCls ay, ax;
     if (C % 4 || B < 1 || nsel < 1 || !make_axis(Hm, ay) || !make_axis(Wm, ax)) return SP_EINVAL;
@@ -524,10 +520,6 @@ extern "C" int sp_drt_direct_bwd_data_live(const float* dDpre, const float* W11,
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
-extern "C" int sp_drt_direct_bwd_data(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C,
-                                      int nsel, int accumulate, float* dh, void* stream) {
-    return sp_drt_direct_bwd_data_live(dDpre, W11, hmap, B, Hm, Wm, C, nsel, accumulate, dh, nullptr, nullptr, 0, B, stream);
-}
 
 extern "C" int64_t sp_drt_direct_bwd_weight_workspace(int B, int Hm, int Wm, int C, int nsel) {
     AxisCls ay, ax;
@@ -535,9 +527,9 @@ extern "C" int64_t sp_drt_direct_bwd_weight_workspace(int B, int Hm, int Wm, int
     return (int64_t)B * nsel * ay.ncls * ax.ncls * NV * C * (int64_t)sizeof(float);
 }
 
-extern "C" int sp_drt_direct_bwd_weight_live(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C,
-                                             int nsel, int nheads, void* workspace, float* dW11, float* dcbsum, const int* live,
-                                             const int* row_last, int row_step, int rowB, void* stream) {
+extern "C" int sp_drt_direct_bwd_weight(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C,
+                                        int nsel, int nheads, void* workspace, float* dW11, float* dcbsum, const int* live,
+                                        const int* row_last, int row_step, int rowB, void* stream) {
     if (!dDpre || !h || !hmap || !workspace || !dW11 || !dcbsum) return SP_ENULL;
     AxisCls ay, ax;
     if (C % 4 || B < 1 || nsel < 1 || nheads < 1 || !make_axis(Hm, ay) || !make_axis(Wm, ax)) return SP_EINVAL;
@@ -555,13 +547,4 @@ extern "C" int sp_drt_direct_bwd_weight_live(const float* dDpre, const float* h,
                        dcbsum);
     SP_LAUNCH_CHECK();
     return SP_OK;
-}
-extern "C" int sp_drt_direct_bwd_weight_rows(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C,
-                                             int nsel, int nheads, void* workspace, float* dW11, float* dcbsum, const int* row_last,
-                                             int row_step, void* stream) {
-    return sp_drt_direct_bwd_weight_live(dDpre, h, hmap, B, Hm, Wm, C, nsel, nheads, workspace, dW11, dcbsum, nullptr, row_last, row_step, B, stream);
-}
-extern "C" int sp_drt_direct_bwd_weight(const float* dDpre, const float* h, const int* hmap, int B, int Hm, int Wm, int C,
-                                        int nsel, int nheads, void* workspace, float* dW11, float* dcbsum, void* stream) {
-    return sp_drt_direct_bwd_weight_rows(dDpre, h, hmap, B, Hm, Wm, C, nsel, nheads, workspace, dW11, dcbsum, nullptr, 0, stream);
 }

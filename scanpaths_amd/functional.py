@@ -29,6 +29,14 @@ from .hip import ConvDesc, WgradDesc, check, ptr
 _KSPLIT_MIN_NKT, _KSPLIT_KT = 8, 4
 
 
+def _timed(key_flops, launch):
+    """launch(), bracketed by HIP events when a hip.KernelTimer is installed (bench.py's roofline leg); key_flops() -> (key, algorithmic
+    FLOPs) is only evaluated then, so the default path builds no key"""
+    if hip.TIMER is None:
+        return launch()
+    return hip.TIMER.bracket(*key_flops(), launch)
+
+
 def _igemm(X, W, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, ldw, KH=1, KW=1, stride=1, pad=0, dil=1,
            mode=0, alpha=1.0, beta=0, relu=0, nbatch=1, sX=0, sW=0, sC=0):
     # a handful of rows against a large weight matrix (the dense layers of the decode loop and their data gradients): the skinny kernel
@@ -44,9 +52,7 @@ def _igemm(X, W, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, ldw, K
             check(L.sp_gemm_skinny(ptr(X), ptr(W), ptr(bias), ptr(out), M_, Nout, Kc, ldx, ldw, ldc, int(mode), float(alpha), int(relu),
                                    ptr(ws), hip.stream()), "sp_gemm_skinny")
         FUSION_COUNTS["skinny_gemm"] += 1
-        if hip.TIMER is None:
-            return launch_sk()
-        return hip.TIMER.bracket(("skinny_fwd" if mode == 0 else "skinny_dgrad", M_, Nout, Kc, "1x1", 1), 2.0 * M_ * Nout * Kc, launch_sk)
+        return _timed(lambda: (("skinny_fwd" if mode == 0 else "skinny_dgrad", M_, Nout, Kc, "1x1", 1), 2.0 * M_ * Nout * Kc), launch_sk)
     # split-K when a pure GEMM has too few output tiles to fill 256 CUs (e.g. M = batch rows, K = 13824)
     ksplit, ws = 0, None
     if KH * KW == 1 and nbatch == 1:
@@ -60,12 +66,8 @@ def _igemm(X, W, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, ldw, K
 
     def launch():
         check(hip.lib().sp_conv_igemm(C.byref(d), ptr(X), ptr(W), ptr(bias), ptr(out), hip.stream()), "sp_conv_igemm")
-    if hip.TIMER is None:
-        return launch()
-    M = N_img * Ho * Wo
-    K = KH * KW * Kc
-    key = ("igemm_fwd" if mode == 0 else "igemm_dgrad", M, Nout, K, f"{KH}x{KW}", nbatch)
-    hip.TIMER.bracket(key, 2.0 * M * Nout * K * nbatch, launch)
+    _timed(lambda: (("igemm_fwd" if mode == 0 else "igemm_dgrad", M_, Nout, KH * KW * Kc, f"{KH}x{KW}", nbatch),
+                    2.0 * M_ * Nout * KH * KW * Kc * nbatch), launch)
 
 
 def _wgrad(X, dY, dW, *, N_img, Hi, Wi, Ci, ldx, Ho, Wo, Co, ldy, ldo, KH=1, KW=1, stride=1, pad=0, dil=1, beta=0,
@@ -76,11 +78,7 @@ def _wgrad(X, dY, dW, *, N_img, Hi, Wi, Ci, ldx, Ho, Wo, Co, ldy, ldo, KH=1, KW=
     ws = hip.workspace(L.sp_conv_wgrad_workspace(C.byref(d)), X.device, slot=0)
     def launch():
         check(L.sp_conv_wgrad(C.byref(d), ptr(X), ptr(dY), ptr(dW), ptr(ws), hip.stream()), "sp_conv_wgrad")
-    if hip.TIMER is None:
-        return launch()
-    M = N_img * Ho * Wo
-    key = ("wgrad", M, Co, KH * KW * Ci, f"{KH}x{KW}", nbatch)
-    hip.TIMER.bracket(key, 2.0 * M * Co * KH * KW * Ci * nbatch, launch)
+    _timed(lambda: (("wgrad", N_img * Ho * Wo, Co, KH * KW * Ci, f"{KH}x{KW}", nbatch), 2.0 * N_img * Ho * Wo * Co * KH * KW * Ci * nbatch), launch)
 
 
 # ---- fp32-faithful GEMMs on the 16-bit matrix pipe (csrc/conv_f16x2.hip, csrc/conv_bf16x3.hip) ---------------------
@@ -300,7 +298,7 @@ def _amax_hint(device) -> Optional[torch.Tensor]:
     back-end is not in use."""
     if not USE_BF16X3 or SPLIT_SCHEME != "f16x2" or not FUSED_AMAX:
         return None
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = hip.device_index(device)
     pool = _HINT_POOL.get(key)
     # A pool created while a stream is being captured is zero-filled by a graph node: EVERY replay re-zeroes all of it.  Such a pool
     # may therefore only serve captures (whose launchers reset each slot in stream order, sp_set_tuning("amax_reset")); eager
@@ -321,7 +319,7 @@ def _reserve_hints(device, n: int) -> None:
     before work is enqueued on another stream that may draw slots, so that no pool is ever created there"""
     if not _amax_hint_active():
         return
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = hip.device_index(device)
     pool = _HINT_POOL.get(key)
     capturing = torch.cuda.is_current_stream_capturing()
     if pool is None or pool[1] + n > pool[0].shape[0] or (pool[2] and not capturing):
@@ -333,7 +331,7 @@ _ONES = {}
 
 def _one(device) -> torch.Tensor:
     """device scalar 1.0f: the x_scale of an operand whose (per-channel) scales were absorbed by the weight operand"""
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = hip.device_index(device)
     t = _ONES.get(key)
     if t is None:
         t = _ONES[key] = torch.ones(2, dtype=torch.float32, device=device)
@@ -429,7 +427,7 @@ def split_op_wT(wp: torch.Tensor, scheme: Optional[str] = None, absorb: Optional
     out = torch.empty(2 * wp.numel() + 32, dtype=torch.float16, device=wp.device)
     if Ci % 4 == 0:
         rscale = torch.empty(Ci, dtype=torch.float32, device=wp.device)
-        check(hip.lib().sp_split2_f16_wT_rows(ptr(wp), Co, KH * KW, Ci, ptr(absorb), ptr(out), ptr(rscale), hip.stream()),
+        check(hip.lib().sp_split2_f16_wT_rows(ptr(wp), 1, Co, KH * KW, Ci, ptr(absorb), ptr(out), ptr(rscale), hip.stream()),
               "sp_split2_f16_wT_rows")
         return SplitOperand(out, rscale, scheme, "rows", absorb)
     assert absorb is None
@@ -507,14 +505,14 @@ def _igemm_b3(Xs, Ws, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, l
         else:
             check(hip.lib().sp_conv_igemm_bf16x3(C.byref(d), ptr(Xs.buf), ptr(Ws.buf), ptr(bias), ptr(out), hip.stream()),
                   "sp_conv_igemm_bf16x3")
-    if hip.TIMER is None:
-        return launch()
-    M = N_img * Ho * Wo
-    K = KH * KW * Kc
-    pre = ("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3"
-    sparse = f16 and rows is not None and mode == 1      # "_rows": the launch skips samples without loss gradient (bench.py scales its FLOPs)
-    key = (pre + ("_fwd" if mode == 0 else "_dgrad") + ("_rows" if sparse else ""), M, Nout, K, f"{KH}x{KW}", 1)
-    hip.TIMER.bracket(key, 2.0 * M * Nout * K, launch)
+
+    def key_flops():
+        M = N_img * Ho * Wo
+        K = KH * KW * Kc
+        pre = ("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3"
+        sparse = f16 and rows is not None and mode == 1      # "_rows": the launch skips samples without loss gradient (bench.py scales its FLOPs)
+        return (pre + ("_fwd" if mode == 0 else "_dgrad") + ("_rows" if sparse else ""), M, Nout, K, f"{KH}x{KW}", 1), 2.0 * M * Nout * K
+    _timed(key_flops, launch)
 
 
 def _wgrad_scheme(Ci, Co) -> str:
@@ -567,9 +565,8 @@ def _wgrad_b3(Xs, dYs, dW, *, N_img, Hi, Wi, Ci, Ho, Wo, Co, ldo, KH=1, KW=1, st
         else:
             check(L.sp_conv_wgrad_bf16x3(C.byref(d), ptr(Xs.buf), ptr(dYs.buf), ptr(dW), ptr(ws), hip.stream()),
                   "sp_conv_wgrad_bf16x3")
-    if hip.TIMER is None:
-        return launch()
-    hip.TIMER.bracket(((("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3") + ("_wgrad_multi" if big > 0 else "_wgrad"), M, Co, KH * KW * Ci, f"{KH}x{KW}", 1), 2.0 * M * Co * KH * KW * Ci, launch)
+    _timed(lambda: (((("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3") + ("_wgrad_multi" if big > 0 else "_wgrad"), M, Co, KH * KW * Ci, f"{KH}x{KW}", 1),
+                    2.0 * M * Co * KH * KW * Ci), launch)
 
 
 def colsum(x2d: torch.Tensor, C_: int, ld: int, M: int) -> torch.Tensor:
@@ -676,8 +673,8 @@ class _FanOut(Function):
             rcs = [op.rows[0] for op in ops if op is not None and op.rows is not None]
             rc = rcs[0] if (rcs and all(r is rcs[0] for r in rcs) and (n // rcs[0].B) % 16 == 0 and n % rcs[0].B == 0) else None
             steps = (C.c_int * len(gs))(*[(op.rows[1] if (op is not None and op.rows is not None) else -1) for op in ops]) if rc else None
-            check(hip.lib().sp_sum_n_mixed_rows(f, pl, sc, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc.last) if rc else None, steps,
-                                                rc.B if rc else 0, hip.stream()), "sp_sum_n_mixed_rows")
+            check(hip.lib().sp_sum_n_mixed(f, pl, sc, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc.last) if rc else None, steps,
+                                           rc.B if rc else 0, hip.stream()), "sp_sum_n_mixed")
             if hint is not None:
                 out._sp_amax = hint
             return out, None, None, None, None
@@ -707,12 +704,11 @@ class _FanOut(Function):
                 steps = [int(ctx.step)] * len(gs)
             else:
                 steps = [int(m[1]) if (m is not None and m[0] is rc0) else -1 for m in marks]
-        if steps is not None and any(st >= 0 for st in steps):
+        sparse = steps is not None and any(st >= 0 for st in steps)
+        if sparse:
             FUSION_COUNTS["fan_in_rows"] += 1
-            check(hip.lib().sp_sum_n_rows(arr, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc0.last), (C.c_int * len(gs))(*steps), rc0.B,
-                                          hip.stream()), "sp_sum_n_rows")
-        else:
-            check(hip.lib().sp_sum_n(arr, len(gs), n, ptr(out), _hint_ptr(hint), hip.stream()), "sp_sum_n")
+        check(hip.lib().sp_sum_n(arr, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc0.last) if sparse else None,
+                                 (C.c_int * len(gs))(*steps) if sparse else None, rc0.B if sparse else 0, hip.stream()), "sp_sum_n")
         if hint is not None:
             out._sp_amax = hint
         return out, None, None, None, None
@@ -963,12 +959,8 @@ def _flush_deferred(defer, wp, geom):
             check(L.sp_conv_wgrad_f16x2_multi(C.byref(d), nseg, Xa, Sxa, Ya, Sya, ptr(dwp), ptr(ws), ptr(rc.last) if rc is not None else None,
                                               seg_steps, hip.stream()), "sp_conv_wgrad_f16x2_multi")
         FUSION_COUNTS["wgrad_multi"] += 1
-        if hip.TIMER is None:
-            launch()
-        else:
-            M = geom["N_img"] * geom["Ho"] * geom["Wo"]
-            hip.TIMER.bracket(("h2_wgrad_multi" + ("_rows" if rc is not None else ""), M * nseg, Co, KH * KW * Ci, f"{KH}x{KW}", nseg),
-                              2.0 * M * nseg * Co * KH * KW * Ci, launch)
+        _timed(lambda: (("h2_wgrad_multi" + ("_rows" if rc is not None else ""), geom["N_img"] * geom["Ho"] * geom["Wo"] * nseg, Co, KH * KW * Ci,
+                         f"{KH}x{KW}", nseg), 2.0 * geom["N_img"] * geom["Ho"] * geom["Wo"] * nseg * Co * KH * KW * Ci), launch)
     else:
         g2 = {k: v for k, v in geom.items() if k != "ldy"}
         for k, (x, y, _) in enumerate(items):
@@ -1404,7 +1396,7 @@ class _MaxPool(Function):
         y = torch.empty((N, Ho, Wo, Cc), dtype=torch.float32, device=x.device)
         # the window position of each maximum (1 byte per output) replaces x and y in the backward pass
         amx = torch.empty((N, Ho, Wo, Cc), dtype=torch.uint8, device=x.device) if ctx.needs_input_grad[0] else None
-        check(hip.lib().sp_maxpool3s2_fwd_idx(ptr(x), N, H, W_, Cc, ptr(y), ptr(amx), Ho, Wo, hip.stream()), "sp_maxpool3s2_fwd_idx")
+        check(hip.lib().sp_maxpool3s2_fwd(ptr(x), N, H, W_, Cc, ptr(y), ptr(amx), Ho, Wo, hip.stream()), "sp_maxpool3s2_fwd")
         ctx.shape = (N, H, W_, Cc, Ho, Wo)
         ctx.save_for_backward(amx)
         return y
@@ -1415,8 +1407,7 @@ class _MaxPool(Function):
         dy = dy.contiguous()
         N, H, W_, Cc, Ho, Wo = ctx.shape
         dx = torch.empty((N, H, W_, Cc), dtype=torch.float32, device=dy.device)
-        check(hip.lib().sp_maxpool3s2_bwd_idx(ptr(dy), ptr(amx), N, H, W_, Cc, ptr(dx), Ho, Wo, hip.stream()),
-              "sp_maxpool3s2_bwd_idx")
+        check(hip.lib().sp_maxpool3s2_bwd(ptr(dy), ptr(amx), N, H, W_, Cc, ptr(dx), Ho, Wo, hip.stream()), "sp_maxpool3s2_bwd")
         return dx
 
 
@@ -1536,7 +1527,8 @@ class _LstmCell(Function):
         dpre = torch.empty_like(gates)
         dcp = torch.empty_like(c)
         check(hip.lib().sp_lstm_pointwise_bwd(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, ptr(dpre),
-                                              ptr(dcp), None, hip.stream()), "sp_lstm_pointwise_bwd")
+                                              ptr(dcp), None, None, None, None, 0.0, 0.0, None, None, None, 0, 1, hip.stream()),
+              "sp_lstm_pointwise_bwd")
         has_hg, has_c = ctx.has
         return dpre, (dpre if has_hg else None), (dcp if has_c else None)
 
@@ -1607,8 +1599,7 @@ def _split_wcT(wc: torch.Tensor) -> SplitOperand:
     wc = wc.contiguous()
     out = torch.empty(2 * wc.numel() + 32, dtype=torch.float16, device=wc.device)
     rscale = torch.empty(B * KP, dtype=torch.float32, device=wc.device)
-    check(hip.lib().sp_split2_f16_wT_rows_batched(ptr(wc), B, N3, 1, KP, None, ptr(out), ptr(rscale), hip.stream()),
-          "sp_split2_f16_wT_rows_batched")
+    check(hip.lib().sp_split2_f16_wT_rows(ptr(wc), B, N3, 1, KP, None, ptr(out), ptr(rscale), hip.stream()), "sp_split2_f16_wT_rows")
     return SplitOperand(out, rscale, "f16x2", "rows", None)
 
 
@@ -1642,11 +1633,11 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
         if skip:
             FUSION_COUNTS["lstm_skip_dpre"] += 1
             dpre._sp_skipped = True          # guards every fp32 reader this process owns (_fp32_required); the fan-in reads the record
-        check(hip.lib().sp_lstm_pointwise_bwd_rows(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, None if skip else ptr(dpre), ptr(dcp),
-                                                   None, _hint_ptr(chint), _hint_ptr(dh_h), _hint_ptr(dc_h), float(cbounds[0]),
-                                                   float(cbounds[1]), ptr(planes), ptr(hint), ptr(rc.last) if rc is not None else None,
-                                                   int(step) if rc is not None else 0, P, hip.stream()),
-              "sp_lstm_pointwise_bwd_rows")
+        check(hip.lib().sp_lstm_pointwise_bwd(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, None if skip else ptr(dpre), ptr(dcp),
+                                              None, _hint_ptr(chint), _hint_ptr(dh_h), _hint_ptr(dc_h), float(cbounds[0]),
+                                              float(cbounds[1]), ptr(planes), ptr(hint), ptr(rc.last) if rc is not None else None,
+                                              int(step) if rc is not None else 0, P, hip.stream()),
+              "sp_lstm_pointwise_bwd")
         dpre._sp_amax = hint
         dpre._sp_cache = {"f16x2": SplitOperand(planes, hint, "f16x2")}
         if rc is not None:
@@ -1654,9 +1645,9 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
         if skip:
             fan[0][fan[1]] = dpre._sp_cache["f16x2"]      # xg's fan-in takes this contribution from the record, by alias index
     else:
-        check(hip.lib().sp_lstm_pointwise_bwd_split(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, ptr(dpre), ptr(dcp),
-                                                    _hint_ptr(hint), _hint_ptr(chint), None, None, 0.0, 0.0, None, None,
-                                                    hip.stream()), "sp_lstm_pointwise_bwd_split")
+        check(hip.lib().sp_lstm_pointwise_bwd(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, ptr(dpre), ptr(dcp),
+                                              _hint_ptr(hint), _hint_ptr(chint), None, None, 0.0, 0.0, None, None, None, 0, 1,
+                                              hip.stream()), "sp_lstm_pointwise_bwd")
         if hint is not None:
             dpre._sp_amax = hint
     if chint is not None:
@@ -1772,10 +1763,7 @@ class _GateConvLstm(Function):
                                                    ptr(hint) if hplanes is not None else None,
                                                    float(cbounds[0]) if hplanes is not None else 0.0, hip.stream()),
                   "sp_gateconv_lstm_f16x2")
-        if hip.TIMER is None:
-            launch()
-        else:
-            hip.TIMER.bracket(("h2_fwd", N * P, Co, KH * KW * Ci, f"{KH}x{KW}", 1), 2.0 * N * P * Co * KH * KW * Ci, launch)
+        _timed(lambda: (("h2_fwd", N * P, Co, KH * KW * Ci, f"{KH}x{KW}", 1), 2.0 * N * P * Co * KH * KW * Ci), launch)
         FUSION_COUNTS["gateconv_lstm"] += 1
         FUSION_COUNTS["gateconv_lstm_hplanes"] += int(hplanes is not None)
         if hint is not None:
@@ -1868,7 +1856,7 @@ class _Im2col(Function):
         maps = maps.contiguous()
         S, R, H, W_ = maps.shape
         col = torch.empty((R, H * W_, KP), dtype=torch.float32, device=maps.device)
-        check(hip.lib().sp_im2col3x3_multi(ptr(maps), S, R, H, W_, KP, ptr(col), hip.stream()), "sp_im2col3x3_multi")      # one launch, zero padding columns included
+        check(hip.lib().sp_im2col3x3_1ch(ptr(maps), S, R, H, W_, KP, ptr(col), hip.stream()), "sp_im2col3x3_1ch")      # one launch, zero padding columns included
         ctx.shape = (S, R, H, W_, KP)
         return col
 
@@ -1877,7 +1865,7 @@ class _Im2col(Function):
         S, R, H, W_, KP = ctx.shape
         dcol = dcol.contiguous()
         dm = torch.empty((S, R, H, W_), dtype=torch.float32, device=dcol.device)
-        check(hip.lib().sp_col2im3x3_multi(ptr(dcol), S, R, H, W_, KP, ptr(dm), hip.stream()), "sp_col2im3x3_multi")
+        check(hip.lib().sp_col2im3x3_1ch(ptr(dcol), S, R, H, W_, KP, ptr(dm), hip.stream()), "sp_col2im3x3_1ch")
         return dm, None
 
 
@@ -1957,7 +1945,7 @@ class _SemPool(Function):
         L = hip.lib()
         out = torch.empty((S, B, Cc) if sbc else (B, S, Cc), dtype=torch.float32, device=vf.device)
         ws = hip.workspace(L.sp_sempool_workspace(S, B, P, Cc), vf.device, slot=0)
-        check(L.sp_sempool_fwd_sbc(ptr(amaps), ptr(vf), S, B, P, Cc, 1.0 / P, ptr(ws), ptr(out), int(sbc), hip.stream()), "sp_sempool_fwd_sbc")
+        check(L.sp_sempool_fwd(ptr(amaps), ptr(vf), S, B, P, Cc, 1.0 / P, ptr(ws), ptr(out), int(sbc), hip.stream()), "sp_sempool_fwd")
         ctx.save_for_backward(amaps, vf, out)
         ctx.step, ctx.sbc = step, sbc
         return out
@@ -1969,9 +1957,9 @@ class _SemPool(Function):
         Cc = vf.shape[-1]
         da, dvf = torch.empty_like(amaps), torch.empty_like(vf)
         rc = rows_ctx(ctx.step, B)      # memory update `step` feeds decode steps >= step only: samples whose last loss step is earlier get zeros
-        check(hip.lib().sp_sempool_bwd_rows_sbc(ptr(dout.contiguous()), ptr(out), ptr(amaps), ptr(vf), S, B, P, Cc, 1.0 / P, ptr(da), ptr(dvf),
-                                                ptr(rc.last) if rc is not None else None, int(ctx.step) if rc is not None else 0, int(ctx.sbc),
-                                                hip.stream()), "sp_sempool_bwd_rows_sbc")
+        check(hip.lib().sp_sempool_bwd(ptr(dout.contiguous()), ptr(out), ptr(amaps), ptr(vf), S, B, P, Cc, 1.0 / P, ptr(da), ptr(dvf),
+                                       ptr(rc.last) if rc is not None else None, int(ctx.step) if rc is not None else 0, int(ctx.sbc),
+                                       hip.stream()), "sp_sempool_bwd")
         if rc is not None:
             dvf._sp_rows = (rc, int(ctx.step))      # hint for vf's gradient fan-in (dead samples' rows are exact zeros): F._FanOut
         return da, dvf, None, None
@@ -2058,7 +2046,7 @@ class _HeadFinish(Function):
         drt = torch.empty((nheads, B, dh * dw), dtype=torch.float32, device=dev)
         check(hip.lib().sp_head_finish_fwd(ptr(Z), B, Hm, Wm, ldz, nheads, HC, ptr(cb), int(per_sample), ptr(w2c), ptr(b2),
                                            int(softmax),
-                                           ptr(logits), ptr(amap), ptr(mu), ptr(s2), ptr(drt), ptr(dpre), zc, hip.stream()),
+                                           ptr(logits), ptr(amap), ptr(mu), ptr(s2), ptr(drt), ptr(dpre), zc, 3, hip.stream()),
               "sp_head_finish_fwd")
         ctx.cfg = (B, Hm, Wm, ldz, nheads, HC, softmax, dh, dw, tuple(w2.shape), per_sample, tuple(cb.shape), zc)
         ctx.save_for_backward(logits, amap, s2, drt, w2c)
@@ -2082,9 +2070,9 @@ class _HeadFinish(Function):
         dcbp = torch.empty((B, nheads * HC), dtype=torch.float32, device=dev)
         dw2p = torch.empty((B, nheads * 2 * S), dtype=torch.float32, device=dev)
         db2p = torch.empty((B, nheads * 2), dtype=torch.float32, device=dev)
-        check(hip.lib().sp_head_finish_bwd(ptr(dlogits), ptr(damap), ptr(dmu), ptr(ds2), ptr(logits), ptr(amap), ptr(s2),
+        check(hip.lib().sp_head_finish_bwd(ptr(dlogits), 0, ptr(damap), ptr(dmu), ptr(ds2), ptr(logits), ptr(amap), ptr(s2),
                                            ptr(drt), B, Hm, Wm, ldz, nheads, HC, ptr(w2c), int(softmax), ptr(dZ), ptr(dcbp),
-                                           ptr(dw2p), ptr(db2p), ptr(ddpre), zc, hip.stream()), "sp_head_finish_bwd")
+                                           ptr(dw2p), ptr(db2p), ptr(ddpre), zc, 3, None, hip.stream()), "sp_head_finish_bwd")
         dcb = dcbp.view(cbshape) if per_sample else _colsum_any(dcbp, nheads * HC).view(nheads, HC)
         dw2 = _colsum_any(dw2p, nheads * 2 * S).view(nheads, 2 * S)
         db2 = _colsum_any(db2p, nheads * 2).view(nheads, 2)
@@ -2100,7 +2088,7 @@ def head_finish(Z, cb, w2, b2, nheads, HC, softmax, per_sample=False, dpre=None)
 
 
 class _HeadSal(Function):
-    """The saliency part of predict_head alone (sp_head_finish_parts_*, parts = 1): Z2 [B,Hm,Wm,nh*2] -> logits [nh,B,1+P], amap [nh,B,P].
+    """The saliency part of predict_head alone (sp_head_finish_fwd / _bwd, parts = 1): Z2 [B,Hm,Wm,nh*2] -> logits [nh,B,1+P], amap [nh,B,P].
     The decode loop evaluates it per step -- the action map feeds the next memory update -- while the duration part (mu, sigma2), which
     nothing in the recurrence reads, is evaluated once for all T steps behind the loop (drt_heads_batched)."""
     @staticmethod
@@ -2111,8 +2099,8 @@ class _HeadSal(Function):
         P = Hm * Wm
         logits = torch.empty((nheads, B, P + 1), dtype=torch.float32, device=Z.device)
         amap = torch.empty((nheads, B, P), dtype=torch.float32, device=Z.device)
-        check(hip.lib().sp_head_finish_parts_fwd(ptr(Z), B, Hm, Wm, ldz, nheads, HC, ptr(cb), int(per_sample), None, None, int(softmax),
-                                                 ptr(logits), ptr(amap), None, None, None, None, 2, 1, hip.stream()), "sp_head_finish_parts_fwd")
+        check(hip.lib().sp_head_finish_fwd(ptr(Z), B, Hm, Wm, ldz, nheads, HC, ptr(cb), int(per_sample), None, None, int(softmax),
+                                           ptr(logits), ptr(amap), None, None, None, None, 2, 1, hip.stream()), "sp_head_finish_fwd (saliency)")
         ctx.cfg = (B, Hm, Wm, ldz, nheads, HC, softmax, per_sample, tuple(cb.shape))
         ctx.save_for_backward(logits, amap)
         return logits, amap
@@ -2132,9 +2120,9 @@ class _HeadSal(Function):
         if ldz != nheads * 2:
             dZ.zero_()
         dcbp = torch.empty((B, nheads * HC), dtype=torch.float32, device=logits.device)
-        check(hip.lib().sp_head_finish_parts_bwd_ld(ptr(dlogits), dlogits.stride(1), ptr(damap), None, None, ptr(logits), ptr(amap), None, None,
-                                                    B, Hm, Wm, ldz, nheads, HC, None, int(softmax), ptr(dZ), ptr(dcbp), None, None, None, 2, 1,
-                                                    None, hip.stream()), "sp_head_finish_parts_bwd_ld")
+        check(hip.lib().sp_head_finish_bwd(ptr(dlogits), dlogits.stride(1), ptr(damap), None, None, ptr(logits), ptr(amap), None, None,
+                                           B, Hm, Wm, ldz, nheads, HC, None, int(softmax), ptr(dZ), ptr(dcbp), None, None, None, 2, 1,
+                                           None, hip.stream()), "sp_head_finish_bwd (saliency)")
         dcb = dcbp.view(cbshape) if per_sample else _colsum_any(dcbp, nheads * HC).view(nheads, HC)
         return dZ, dcb, None, None, None, None
 
@@ -2203,8 +2191,8 @@ class _SalGather(Function):
         dZ2 = dZ2.contiguous()
         dT = torch.empty((B, Hm, Wm, ldt), dtype=torch.float32, device=dZ2.device)
         rc = rows_ctx(ctx.step, B)
-        check(hip.lib().sp_sal_gather_bwd_rows(ptr(dZ2), B, Hm, Wm, ldt, nsel, nsrc, ptr(hmap), ptr(dT), ptr(rc.last) if rc is not None else None,
-                                               int(ctx.step) if rc is not None else 0, hip.stream()), "sp_sal_gather_bwd_rows")
+        check(hip.lib().sp_sal_gather_bwd(ptr(dZ2), B, Hm, Wm, ldt, nsel, nsrc, ptr(hmap), ptr(dT), ptr(rc.last) if rc is not None else None,
+                                          int(ctx.step) if rc is not None else 0, hip.stream()), "sp_sal_gather_bwd")
         return dT, None, None, None, None
 
 
@@ -2249,14 +2237,14 @@ class _DrtDirect(Function):
         rl, rs = (ptr(rc.last), int(ctx.step)) if rc is not None else (None, 0)
         if ctx.needs_input_grad[0]:
             dh = torch.empty_like(h)
-            check(L.sp_drt_direct_bwd_data_live(ptr(dD), ptr(W11), ptr(hmap), B, Hm, Wm, C_, nsel, 0, ptr(dh), ptr(live), rl, rs, B,
-                                                hip.stream()), "sp_drt_direct_bwd_data_live")
+            check(L.sp_drt_direct_bwd_data(ptr(dD), ptr(W11), ptr(hmap), B, Hm, Wm, C_, nsel, 0, ptr(dh), ptr(live), rl, rs, B,
+                                           hip.stream()), "sp_drt_direct_bwd_data")
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             dW = torch.empty(wshape, dtype=torch.float32, device=h.device)
             dcs = torch.empty(cshape, dtype=torch.float32, device=h.device)
             ws = hip.workspace(L.sp_drt_direct_bwd_weight_workspace(B, Hm, Wm, C_, nsel), h.device, slot=0)
-            check(L.sp_drt_direct_bwd_weight_live(ptr(dD), ptr(h), ptr(hmap), B, Hm, Wm, C_, nsel, nheads, ptr(ws), ptr(dW), ptr(dcs),
-                                                  ptr(live), rl, rs, B, hip.stream()), "sp_drt_direct_bwd_weight_live")
+            check(L.sp_drt_direct_bwd_weight(ptr(dD), ptr(h), ptr(hmap), B, Hm, Wm, C_, nsel, nheads, ptr(ws), ptr(dW), ptr(dcs),
+                                             ptr(live), rl, rs, B, hip.stream()), "sp_drt_direct_bwd_weight")
         return dh, dW, dcs, None, None, None, None
 
 
@@ -2333,8 +2321,8 @@ class _DrtHeadsBatched(Function):
         mu = torch.empty((NH, B), dtype=torch.float32, device=dev)
         s2 = torch.empty((NH, B), dtype=torch.float32, device=dev)
         drt = torch.empty((NH, B, S), dtype=torch.float32, device=dev)
-        check(L.sp_head_finish_parts_fwd(None, B, Hm, Wm, 0, NH, HC, ptr(cb_all), int(per_sample), ptr(w2c), ptr(b2), 0, None, None, ptr(mu),
-                                         ptr(s2), ptr(drt), ptr(D), 2, 2, hip.stream()), "sp_head_finish_parts_fwd (duration)")
+        check(L.sp_head_finish_fwd(None, B, Hm, Wm, 0, NH, HC, ptr(cb_all), int(per_sample), ptr(w2c), ptr(b2), 0, None, None, ptr(mu),
+                                   ptr(s2), ptr(drt), ptr(D), 2, 2, hip.stream()), "sp_head_finish_fwd (duration)")
         ctx.batch = batch
         ctx.cfg = (Tn, nsel, B, Hm, Wm, S, HC, per_sample, tuple(w2.shape), tuple(cb.shape))
         ctx.save_for_backward(s2, drt, w2c)
@@ -2354,9 +2342,9 @@ class _DrtHeadsBatched(Function):
         dw2p = torch.empty((B, NH * 2 * S), dtype=torch.float32, device=dev)
         db2p = torch.empty((B, NH * 2), dtype=torch.float32, device=dev)
         live = torch.empty((NH * B,), dtype=torch.int32, device=dev)
-        check(hip.lib().sp_head_finish_parts_bwd(None, None, ptr(dmu), ptr(ds2), None, None, ptr(s2), ptr(drt), B, Hm, Wm, 0, NH, HC, ptr(w2c), 0,
-                                                 None, ptr(dcbp), ptr(dw2p), ptr(db2p), ptr(ddpre), 2, 2, ptr(live), hip.stream()),
-              "sp_head_finish_parts_bwd (duration)")
+        check(hip.lib().sp_head_finish_bwd(None, 0, None, ptr(dmu), ptr(ds2), None, None, ptr(s2), ptr(drt), B, Hm, Wm, 0, NH, HC, ptr(w2c), 0,
+                                           None, ptr(dcbp), ptr(dw2p), ptr(db2p), ptr(ddpre), 2, 2, ptr(live), hip.stream()),
+              "sp_head_finish_bwd (duration)")
         ctx.batch.live = live.view(Tn, nsel * B)          # row t: the flags [nsel][B] of decode step t's drt_direct node
         # partial sums over the samples (and the T steps): composed bias (only drt_layer_1.bias' entry is non-zero), drt_layer_2
         if per_sample:

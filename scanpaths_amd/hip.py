@@ -51,7 +51,7 @@ class WgradDesc(C.Structure):
 
 
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ABI_VERSION = 3      # = SP_ABI_VERSION of include/scanpaths_amd.h (held equal by tests/test_cpu_host.py)
+ABI_VERSION = 4      # = SP_ABI_VERSION of include/scanpaths_amd.h (held equal by tests/test_cpu_host.py)
 
 # name -> (restype, argtypes); must list every symbol include/scanpaths_amd.h declares
 SIGNATURES = {
@@ -64,8 +64,7 @@ SIGNATURES = {
     "sp_split2_f16": (_I, [_P, _L, _P, _P, _I, _P]),
     "sp_split2_f16_wT": (_I, [_P, _I, _I, _I, _P, _P, _P]),
     "sp_split2_f16_rows": (_I, [_P, _L, _L, _I, _P, _P, _P, _P]),
-    "sp_split2_f16_wT_rows": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
-    "sp_split2_f16_wT_rows_batched": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "sp_split2_f16_wT_rows": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "sp_split2_f16_cols_workspace": (_L, [_L, _I]),
     "sp_split2_f16_cols": (_I, [_P, _L, _I, _P, _P, _P, _P]),
     "sp_conv_wgrad_f16x2_multi_workspace": (_L, [_P, _I]),
@@ -99,15 +98,11 @@ SIGNATURES = {
     "sp_conv_stats_tiles": (_L, [C.POINTER(ConvDesc)]),
     "sp_conv_igemm_f16x2_stats": (_I, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P]),
     "sp_bn_bwd_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "sp_sum_n": (_I, [_P, _I, _L, _P, _P, _P]),
-    "sp_sum_n_rows": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P]),
-    "sp_sum_n_mixed": (_I, [_P, _P, _P, _I, _L, _P, _P, _P]),
-    "sp_sum_n_mixed_rows": (_I, [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P]),
+    "sp_sum_n": (_I, [_P, _I, _L, _P, _P, _P, _P, _I, _P]),
+    "sp_sum_n_mixed": (_I, [_P, _P, _P, _I, _L, _P, _P, _P, _P, _I, _P]),
     "sp_relu_bwd": (_I, [_P, _P, _L, _P, _P]),
-    "sp_maxpool3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "sp_maxpool3s2_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
-    "sp_maxpool3s2_fwd_idx": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
-    "sp_maxpool3s2_bwd_idx": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "sp_maxpool3s2_fwd": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P]),
+    "sp_maxpool3s2_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _I, _P]),
     "sp_nchw_to_nhwc_pad": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "sp_pad_lastdim": (_I, [_P, _L, _I, _I, _P, _P]),
     "sp_add": (_I, [_P, _P, _P, _L, _P]),
@@ -116,45 +111,29 @@ SIGNATURES = {
     "sp_rank1_dwc_workspace": (_L, [_I, _I, _I, _I]),
     "sp_rank1_dwc": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sp_sempool_workspace": (_L, [_I, _I, _I, _I]),
-    "sp_sempool_fwd": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "sp_sempool_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "sp_sempool_bwd_rows": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _P]),
-    "sp_sempool_fwd_sbc": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _P]),
-    "sp_sempool_bwd_rows_sbc": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _I, _P]),
-    "sp_lstm_pointwise_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P]),
-    "sp_lstm_pointwise_bwd_split": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P]),
-    "sp_lstm_pointwise_bwd_rows": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _I, _P]),
+    "sp_sempool_fwd": (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _I, _P]),
+    "sp_sempool_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _I, _I, _P]),
+    "sp_lstm_pointwise_bwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _I, _P]),
     "sp_im2col3x3_1ch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "sp_col2im3x3_1ch": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "sp_im2col3x3_multi": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "sp_col2im3x3_multi": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "sp_listatt_fwd": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "sp_listatt_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "sp_mulrelu_fwd": (_I, [_P, _P, _L, _L, _P, _P]),
     "sp_mulrelu_bwd": (_I, [_P, _P, _P, _P, _L, _L, _P, _P, _P]),
     "sp_select_rows": (_I, [_P, _P, _P, _L, _L, _P, _P]),
     "sp_select_rows_bwd": (_I, [_P, _P, _L, _L, _P, _P, _P]),
-    "sp_head_finish_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
-    "sp_head_finish_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I,
-                                _P]),
-    "sp_head_finish_parts_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
-    "sp_head_finish_parts_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I,
-                                      _I, _P, _P]),
-    "sp_head_finish_parts_bwd_ld": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I,
-                                      _I, _P, _P]),
+    "sp_head_finish_fwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sp_head_finish_bwd": (_I, [_P, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _I,
+                                _I, _P, _P]),
     "sp_head_num_classes": (_I, [_I, _I]),
     "sp_head_compose11_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sp_head_compose11_bwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "sp_sal_gather_fwd": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "sp_sal_gather_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "sp_sal_gather_bwd_rows": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
+    "sp_sal_gather_bwd": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "sp_drt_direct_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
-    "sp_drt_direct_bwd_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    "sp_drt_direct_bwd_data_live": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
-    "sp_drt_direct_bwd_weight_live": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "sp_drt_direct_bwd_data": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P]),
     "sp_drt_direct_bwd_weight_workspace": (_L, [_I, _I, _I, _I, _I]),
-    "sp_drt_direct_bwd_weight": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "sp_drt_direct_bwd_weight_rows": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "sp_drt_direct_bwd_weight": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _P]),
     "sp_scanmatch_max_len": (_I, []),
     "sp_scanmatch_submatrix": (_I, [_I, _I, C.c_double, _P, _P, _P]),
     "sp_scanmatch_sequences": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _P, _I, _P, _P, _P]),
@@ -258,6 +237,11 @@ def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def device_index(device) -> int:
+    """the ordinal of a torch device, the current one for a bare "cuda": the key of every per-device cache"""
+    return device.index if device.index is not None else torch.cuda.current_device()
+
+
 _side = {}
 
 
@@ -265,7 +249,7 @@ def side_stream(device) -> "torch.cuda.Stream":
     """one extra HIP stream per device: in the backward recurrence it carries the h-gate conv's data gradient of decode step t
     (functional._GateConvLstm.backward) beside the current stream's chain of small launches; the fan-in of h_{t-1}'s gradients
     (functional._FanOut.backward) waits for the event that launch leaves behind.  Deferred weight gradients run on the CURRENT stream."""
-    key = device.index if device.index is not None else torch.cuda.current_device()
+    key = device_index(device)
     s = _side.get(key)
     if s is None:
         # lowest priority the device offers (this pool's MI355X boxes: range (0, -1), i.e. normal): the side stream carries ONE long GEMM
@@ -288,7 +272,7 @@ def workspace(nbytes: int, device, slot: int = 0) -> Optional[torch.Tensor]:
     stream beside the current one -- each stream has its own scratch)."""
     if nbytes <= 0:
         return None
-    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream().cuda_stream, slot)
+    key = (device_index(device), torch.cuda.current_stream().cuda_stream, slot)
     cur = _ws.get(key)
     if cur is None or cur.numel() < nbytes:
         cur = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
@@ -316,7 +300,7 @@ class KernelTimer:
         # a launch enqueued on the side stream runs BESIDE the current stream's small launches: its time includes that contention and is
         # not comparable with a stand-alone launch of the same kernel -- the key says so ("+side"), bench.py reports it as `beside_chain`
         cur = torch.cuda.current_stream()
-        sd = _side.get(cur.device.index if cur.device.index is not None else torch.cuda.current_device())
+        sd = _side.get(device_index(cur.device))
         if sd is not None and cur.cuda_stream == sd.cuda_stream and isinstance(key, tuple) and key and isinstance(key[0], str):
             key = (key[0] + "+side",) + tuple(key[1:])
         self.pending.append((key, flops, s, e))

@@ -141,7 +141,7 @@ _tickets = {}
 
 def _ticket(dev):
     """a zeroed device word per (device, stream): the launch's last workgroup takes the mean over rows and puts the word back to 0"""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(dev).cuda_stream)
+    key = (F.hip.device_index(dev), torch.cuda.current_stream(dev).cuda_stream)
     t = _tickets.get(key)
     if t is None:
         t = _tickets[key] = torch.zeros(1, dtype=torch.int32, device=dev)

@@ -467,7 +467,7 @@ def test_backward_chain_kernels_fit_beside_a_resident_data_gradient_workgroup():
     chain = ("skinny_kernelILi0E", "skinny_kernelILi1E", "skinny_reduce_kernel", "listatt_bwd_kernel", "sempool_bwd_kernel",
              "mulrelu_bwd_kernel", "head_bwd_kernel", "drt_bwd_data_kernel", "drt_bwd_weight_kernel", "drt_slab_reduce_kernel",
              "drt_dcbsum_kernel", "sal_gather_bwd_kernel", "colsum_partial", "colsum_final", "sum_n_kernel", "add_kernel",
-             "col2im1_kernel", "colamax_partial_kernel", "colamax_final_kernel", "split2_cols_kernel")
+             "col2im1_multi_kernel", "colamax_partial_kernel", "colamax_final_kernel", "split2_cols_kernel")
     for want in chain:
         hits = {k: v for k, v in fp.items() if want in k}
         assert hits, want

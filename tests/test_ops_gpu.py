@@ -930,7 +930,7 @@ def test_batched_weight_gradient_with_padded_taps_on_wider_rows():
 
 def test_fan_in_of_split_only_gradients_and_cell_backward_without_fp32_output():
     """the x-gate fan-in when steps hand back their gate gradient as a split operand only (sp_sum_n_mixed; the fp32 tensor of such
-    a contribution is poisoned here and must not be read), and sp_lstm_pointwise_bwd_split with dpre == NULL writing the same
+    a contribution is poisoned here and must not be read), and sp_lstm_pointwise_bwd with dpre == NULL writing the same
     split operand as with it"""
     import ctypes as C
     from scanpaths_amd import functional as F, hip
@@ -946,14 +946,14 @@ def test_fan_in_of_split_only_gradients_and_cell_backward_without_fp32_output():
     out = torch.empty(n, device=dev)
     amax = torch.zeros(2, dtype=torch.int32, device=dev)
     L = hip.lib()
-    assert L.sp_sum_n_mixed(f, pl, sc, 3, n, hip.ptr(out), hip.ptr(amax), hip.stream()) == 0
+    assert L.sp_sum_n_mixed(f, pl, sc, 3, n, hip.ptr(out), hip.ptr(amax), None, None, 0, hip.stream()) == 0
     ref = ts[0].double() + ts[1].double() + ts[2].double()
     err = (out.double() - ref).abs().max().item()
     assert err <= 2e-6 * 30.0 * 5, err                         # split representation: 2^-22 of each tensor's maximum
     assert float(amax.view(torch.float32)[0]) == float(out.abs().max())                      # fused max|sum| (float bits)
-    assert L.sp_sum_n_mixed(f, pl, sc, 3, n - 8, hip.ptr(out), None, hip.stream()) == -1
+    assert L.sp_sum_n_mixed(f, pl, sc, 3, n - 8, hip.ptr(out), None, None, None, 0, hip.stream()) == -1
     del poison
-    # masked-step sparsity (sp_sum_n_mixed_rows): a term of decode step s is exactly zero for samples whose last loss step is < s and
+    # masked-step sparsity (row_last / steps): a term of decode step s is exactly zero for samples whose last loss step is < s and
     # is then not read -- same result, bit for bit, as the dense pass over terms whose dead samples hold zeros (4 samples here)
     nb = 4
     last = torch.tensor([0, 2, 1, -1], dtype=torch.int32, device=dev)
@@ -968,13 +968,13 @@ def test_fan_in_of_split_only_gradients_and_cell_backward_without_fp32_output():
     pl2 = (C.c_void_p * 3)(zops[0].buf.data_ptr(), None, zops[2].buf.data_ptr())
     sc2 = (C.c_void_p * 3)(zops[0].scale.data_ptr(), None, zops[2].scale.data_ptr())
     dense, sparse = torch.empty(n, device=dev), torch.empty(n, device=dev)
-    assert L.sp_sum_n_mixed(f2, pl2, sc2, 3, n, hip.ptr(dense), None, hip.stream()) == 0
+    assert L.sp_sum_n_mixed(f2, pl2, sc2, 3, n, hip.ptr(dense), None, None, None, 0, hip.stream()) == 0
     for z, st in zip(zs, steps):                               # dead samples now hold NaN: reading them would show
         z.view(nb, -1)[(last < st).nonzero().flatten()] = float("nan")
     st_arr = (C.c_int * 3)(*steps)
-    assert L.sp_sum_n_mixed_rows(f2, pl2, sc2, 3, n, hip.ptr(sparse), None, hip.ptr(last), st_arr, nb, hip.stream()) == 0
+    assert L.sp_sum_n_mixed(f2, pl2, sc2, 3, n, hip.ptr(sparse), None, hip.ptr(last), st_arr, nb, hip.stream()) == 0
     assert torch.equal(dense, sparse)
-    assert L.sp_sum_n_mixed_rows(f2, pl2, sc2, 3, n, hip.ptr(sparse), None, hip.ptr(last), None, nb, hip.stream()) == -2
+    assert L.sp_sum_n_mixed(f2, pl2, sc2, 3, n, hip.ptr(sparse), None, hip.ptr(last), None, nb, hip.stream()) == -2
     # cell backward: same planes with and without the fp32 output
     rows, Cc = 64, 256
     gates = torch.rand(rows, 4 * Cc, generator=g).to(dev)
@@ -987,9 +987,9 @@ def test_fan_in_of_split_only_gradients_and_cell_backward_without_fp32_output():
         planes = torch.empty(2 * gates.numel() + 32, dtype=torch.float16, device=dev)
         scale = torch.zeros(2, device=dev)
         dh_a, dc_a = am(dh), am(dc)
-        rc = L.sp_lstm_pointwise_bwd_split(hip.ptr(dh), hip.ptr(dc), hip.ptr(gates), hip.ptr(c_prev), hip.ptr(c), rows, Cc,
-                                           None if skip else hip.ptr(dpre), hip.ptr(dcp), None, None, hip.ptr(dh_a[1:]), hip.ptr(dc_a[1:]),
-                                           4.0, 3.0, hip.ptr(planes), hip.ptr(scale), hip.stream())
+        rc = L.sp_lstm_pointwise_bwd(hip.ptr(dh), hip.ptr(dc), hip.ptr(gates), hip.ptr(c_prev), hip.ptr(c), rows, Cc,
+                                     None if skip else hip.ptr(dpre), hip.ptr(dcp), None, None, hip.ptr(dh_a[1:]), hip.ptr(dc_a[1:]),
+                                     4.0, 3.0, hip.ptr(planes), hip.ptr(scale), None, 0, 1, hip.stream())
         assert rc == 0
         res.append((planes.clone(), dcp.clone(), scale.clone()))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1]) and torch.equal(res[0][2], res[1][2])
@@ -1061,7 +1061,7 @@ def test_c_abi_error_codes():
     assert L.sp_conv_igemm_f16x2(C.byref(d), None, hip.ptr(x), hip.ptr(x), hip.ptr(x), None, hip.ptr(x), st) == -2
     assert L.sp_lstm_rank1_fwd(hip.ptr(x), None, None, hip.ptr(x), hip.ptr(x), 1, 4, 48, 12, hip.ptr(x), hip.ptr(x), hip.ptr(x), None,
                                st) == -1                                                  # C % 64
-    assert L.sp_sempool_fwd(hip.ptr(x), hip.ptr(x), 3, 1, 4, 64, 1.0, hip.ptr(x), hip.ptr(x), st) == -1      # S > 2
+    assert L.sp_sempool_fwd(hip.ptr(x), hip.ptr(x), 3, 1, 4, 64, 1.0, hip.ptr(x), hip.ptr(x), 0, st) == -1      # S > 2
     assert L.sp_scanmatch_submatrix(0, 3, 3.5, hip.ptr(x), hip.ptr(x), st) == -1
     assert L.sp_head_num_classes(3, 3) >= 1 and L.sp_head_num_classes(100000, 8) == -1
     with pytest.raises(hip.HipError):

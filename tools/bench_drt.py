@@ -48,9 +48,10 @@ for ncls in (ncls_y * ncls_x,):
     dcs = torch.empty_like(cbsum)
     ws = hip.workspace(L.sp_drt_direct_bwd_weight_workspace(B, Hm, Wm, C, nsel), dev, slot=0)
     p = hip.ptr
-    res["bwd_data_us"] = round(timed(lambda: hip.check(L.sp_drt_direct_bwd_data(p(dD), p(W11), p(hmap), B, Hm, Wm, C, nsel, 0, p(dh), hip.stream()), "d")), 1)
+    res["bwd_data_us"] = round(timed(lambda: hip.check(L.sp_drt_direct_bwd_data(p(dD), p(W11), p(hmap), B, Hm, Wm, C, nsel, 0, p(dh), None, None, 0, B,
+                                                                               hip.stream()), "d")), 1)
     res["bwd_weight_us"] = round(timed(lambda: hip.check(L.sp_drt_direct_bwd_weight(p(dD), p(h), p(hmap), B, Hm, Wm, C, nsel, nheads, p(ws), p(dW), p(dcs),
-                                                                                   hip.stream()), "w")), 1)
+                                                                                   None, None, 0, B, hip.stream()), "w")), 1)
     torch.cuda.synchronize()
     res["sha_dW"] = hashlib.sha256(dW.detach().cpu().numpy().tobytes()).hexdigest()[:16]
     res["sha_dh"] = hashlib.sha256(dh.cpu().numpy().tobytes()).hexdigest()[:16]

@@ -80,9 +80,9 @@ def main():
             dcs = torch.empty(cshape, dtype=torch.float32, device=h.device)
             ws = F.hip.workspace(L.sp_drt_direct_bwd_weight_workspace(B, Hm, Wm, C_, nsel), h.device, slot=0)
             rc = F.rows_ctx(ctx.step, B)
-            F.check(L.sp_drt_direct_bwd_weight_rows(F.ptr(dD.contiguous()), F.ptr(h), F.ptr(hmap), B, Hm, Wm, C_, nsel, nheads, F.ptr(ws), F.ptr(dW),
-                                                    F.ptr(dcs), F.ptr(rc.last) if rc is not None else None, int(ctx.step) if rc is not None else 0,
-                                                    F.hip.stream()), "w")
+            F.check(L.sp_drt_direct_bwd_weight(F.ptr(dD.contiguous()), F.ptr(h), F.ptr(hmap), B, Hm, Wm, C_, nsel, nheads, F.ptr(ws), F.ptr(dW),
+                                               F.ptr(dcs), None, F.ptr(rc.last) if rc is not None else None, int(ctx.step) if rc is not None else 0,
+                                               B, F.hip.stream()), "w")
             return None, dW, dcs, None, None, None
         return patch(F._DrtDirect, bwd)
 
