@@ -9,6 +9,7 @@ implicit-GEMM kernels consume and the layout their weight gradients are produced
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import Optional
 
 import torch
@@ -37,48 +38,56 @@ def _timed(key_flops, launch):
     return hip.TIMER.bracket(*key_flops(), launch)
 
 
-def _igemm(X, W, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, ldw, KH=1, KW=1, stride=1, pad=0, dil=1,
-           mode=0, alpha=1.0, beta=0, relu=0, nbatch=1, sX=0, sW=0, sC=0):
+def _gemm_desc(M, Nout, Kc, *, ldx, ldw, ldc, mode=0, alpha=1.0, beta=0, relu=0, nbatch=1, sX=0, sW=0, sC=0):
+    """ConvDesc of a pure (batched) GEMM out[M, Nout] = X[M, Kc] x W: M one-pixel "images" under a 1 x 1 filter.  mode 0: W is [Nout][Kc]
+    rows, mode 1: [Kc][Nout]; convs get their descriptors from ConvGeom"""
+    return ConvDesc(N_img=M, Hi=1, Wi=1, Kc=Kc, ldx=ldx, Ho=1, Wo=1, Nout=Nout, ldc=ldc, KH=1, KW=1, stride=1, pad=0, dil=1, mode=mode,
+                    ldw=ldw, alpha=float(alpha), beta=int(beta), relu=int(relu), nbatch=nbatch, strideX=sX, strideW=sW, strideC=sC)
+
+
+def _gemm_wgrad_desc(M, Co, Ci, *, ldx, ldy, ldo, alpha=1.0, nbatch=1, sX=0, sY=0, sO=0):
+    """WgradDesc of a pure (batched) TN GEMM dW[Co, Ci] = dY[M, Co]^T x X[M, Ci]"""
+    return WgradDesc(N_img=M, Hi=1, Wi=1, Ci=Ci, ldx=ldx, Ho=1, Wo=1, Co=Co, ldy=ldy, KH=1, KW=1, stride=1, pad=0, dil=1, ldo=ldo,
+                     alpha=float(alpha), nbatch=nbatch, strideX=sX, strideY=sY, strideO=sO)
+
+
+def _igemm(d: ConvDesc, X, W, bias, out):
+    """the fp32-MFMA implicit GEMM that d describes (ksplit / workspace are chosen here), or the skinny kernel where that one applies"""
     # a handful of rows against a large weight matrix (the dense layers of the decode loop and their data gradients): the skinny kernel
     # streams the matrix once over ~512 workgroups (csrc/gemm_skinny.hip; 135-185 us per launch on the 128 x 128-tile kernel below)
-    M_ = N_img * Ho * Wo
+    M_, Nout, Kc, mode, taps, nbatch = d.N_img * d.Ho * d.Wo, d.Nout, d.Kc, d.mode, d.KH * d.KW, d.nbatch
     aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (X, W, out, bias))
-    if (SKINNY_GEMM and KH * KW == 1 and nbatch == 1 and M_ <= 64 and not beta and Hi == Ho and Wi == Wo and stride == 1 and pad == 0
-            and aligned and ldc % 4 == 0 and hip.lib().sp_gemm_skinny_applies(M_, Nout, Kc, ldx, ldw, ldc, int(mode))):
+    if (SKINNY_GEMM and taps == 1 and nbatch == 1 and M_ <= 64 and not d.beta and d.Hi == d.Ho and d.Wi == d.Wo and d.stride == 1
+            and d.pad == 0 and aligned and d.ldc % 4 == 0 and hip.lib().sp_gemm_skinny_applies(M_, Nout, Kc, d.ldx, d.ldw, d.ldc, mode)):
         L = hip.lib()
-        ws = hip.workspace(L.sp_gemm_skinny_workspace(M_, Nout, Kc, int(mode)), X.device, slot=2)
+        ws = hip.workspace(L.sp_gemm_skinny_workspace(M_, Nout, Kc, mode), X.device, slot=2)
 
         def launch_sk():
-            check(L.sp_gemm_skinny(ptr(X), ptr(W), ptr(bias), ptr(out), M_, Nout, Kc, ldx, ldw, ldc, int(mode), float(alpha), int(relu),
+            check(L.sp_gemm_skinny(ptr(X), ptr(W), ptr(bias), ptr(out), M_, Nout, Kc, d.ldx, d.ldw, d.ldc, mode, d.alpha, d.relu,
                                    ptr(ws), hip.stream()), "sp_gemm_skinny")
         FUSION_COUNTS["skinny_gemm"] += 1
         return _timed(lambda: (("skinny_fwd" if mode == 0 else "skinny_dgrad", M_, Nout, Kc, "1x1", 1), 2.0 * M_ * Nout * Kc), launch_sk)
     # split-K when a pure GEMM has too few output tiles to fill 256 CUs (e.g. M = batch rows, K = 13824)
-    ksplit, ws = 0, None
-    if KH * KW == 1 and nbatch == 1:
-        tiles = ((N_img * Ho * Wo + 127) // 128) * ((Nout + 127) // 128)
+    if taps == 1 and nbatch == 1:
+        tiles = ((M_ + 127) // 128) * ((Nout + 127) // 128)
         nkt = (Kc + 31) // 32
         if tiles <= 64 and nkt >= _KSPLIT_MIN_NKT:
-            ksplit = max(2, min(nkt // _KSPLIT_KT, 512 // tiles))
-            ws = hip.workspace(ksplit * N_img * Ho * Wo * Nout * 4, X.device, slot=2)
-    d = ConvDesc(N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, KH, KW, stride, pad, dil, mode, ldw, float(alpha), int(beta),
-                 int(relu), nbatch, sX, sW, sC, ksplit, ptr(ws))
+            d.ksplit = max(2, min(nkt // _KSPLIT_KT, 512 // tiles))
+            d.workspace = ptr(hip.workspace(d.ksplit * M_ * Nout * 4, X.device, slot=2))
 
     def launch():
         check(hip.lib().sp_conv_igemm(C.byref(d), ptr(X), ptr(W), ptr(bias), ptr(out), hip.stream()), "sp_conv_igemm")
-    _timed(lambda: (("igemm_fwd" if mode == 0 else "igemm_dgrad", M_, Nout, KH * KW * Kc, f"{KH}x{KW}", nbatch),
-                    2.0 * M_ * Nout * KH * KW * Kc * nbatch), launch)
+    _timed(lambda: (("igemm_fwd" if mode == 0 else "igemm_dgrad", M_, Nout, taps * Kc, f"{d.KH}x{d.KW}", nbatch),
+                    2.0 * M_ * Nout * taps * Kc * nbatch), launch)
 
 
-def _wgrad(X, dY, dW, *, N_img, Hi, Wi, Ci, ldx, Ho, Wo, Co, ldy, ldo, KH=1, KW=1, stride=1, pad=0, dil=1, beta=0,
-           alpha=1.0, nbatch=1, sX=0, sY=0, sO=0):
-    d = WgradDesc(N_img, Hi, Wi, Ci, ldx, Ho, Wo, Co, ldy, KH, KW, stride, pad, dil, ldo, int(beta), float(alpha), nbatch,
-                  sX, sY, sO)
+def _wgrad(d: WgradDesc, X, dY, dW):
     L = hip.lib()
     ws = hip.workspace(L.sp_conv_wgrad_workspace(C.byref(d)), X.device, slot=0)
     def launch():
         check(L.sp_conv_wgrad(C.byref(d), ptr(X), ptr(dY), ptr(dW), ptr(ws), hip.stream()), "sp_conv_wgrad")
-    _timed(lambda: (("wgrad", N_img * Ho * Wo, Co, KH * KW * Ci, f"{KH}x{KW}", nbatch), 2.0 * N_img * Ho * Wo * Co * KH * KW * Ci * nbatch), launch)
+    _timed(lambda: (("wgrad", d.N_img * d.Ho * d.Wo, d.Co, d.KH * d.KW * d.Ci, f"{d.KH}x{d.KW}", d.nbatch),
+                    2.0 * d.N_img * d.Ho * d.Wo * d.Co * d.KH * d.KW * d.Ci * d.nbatch), launch)
 
 
 # ---- fp32-faithful GEMMs on the 16-bit matrix pipe (csrc/conv_f16x2.hip, csrc/conv_bf16x3.hip) ---------------------
@@ -473,16 +482,12 @@ def _b3_pays(M, N, K, Kc, nbatch=1, a_elems=None, free_a=False):
     return flops * (1 / 1.1e14 - 1 / (4.0e14 if f16 else 2.5e14)) > split_bytes / 4e12 and flops > (1e9 if free_a else 2e9)
 
 
-def _igemm_b3(Xs, Ws, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, ldw, KH=1, KW=1, stride=1, pad=0, dil=1, mode=0,
-              alpha=1.0, beta=0, relu=0, stats=None, rows=None):
-    """implicit-GEMM conv / dgrad on split operands (SplitOperand, or a raw split-3 buffer)"""
-    if not isinstance(Xs, SplitOperand):
-        Xs, Ws = SplitOperand(Xs, None, "bf16x3"), SplitOperand(Ws, None, "bf16x3")
+def _igemm_b3(d: ConvDesc, Xs, Ws, bias, out, stats=None, rows=None):
+    """the implicit-GEMM conv / dgrad that d describes, on split operands"""
     assert Xs.scheme == Ws.scheme, (Xs.scheme, Ws.scheme)
-    d = ConvDesc(N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, KH, KW, stride, pad, dil, mode, ldw, float(alpha), int(beta),
-                 int(relu), 1, 0, 0, 0, 0, None)
     f16 = Xs.scheme == "f16x2"
     xscale = Xs.scale
+    mode = d.mode
     if f16 and rows is not None and mode == 1:      # (RowsCtx, step): zero tiles for samples without loss gradient at this decode step
         d.row_last, d.row_step = rows[0].last.data_ptr(), int(rows[1])
     if f16:
@@ -507,11 +512,11 @@ def _igemm_b3(Xs, Ws, bias, out, *, N_img, Hi, Wi, Kc, ldx, Ho, Wo, Nout, ldc, l
                   "sp_conv_igemm_bf16x3")
 
     def key_flops():
-        M = N_img * Ho * Wo
-        K = KH * KW * Kc
+        M = d.N_img * d.Ho * d.Wo
+        K = d.KH * d.KW * d.Kc
         pre = ("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3"
         sparse = f16 and rows is not None and mode == 1      # "_rows": the launch skips samples without loss gradient (bench.py scales its FLOPs)
-        return (pre + ("_fwd" if mode == 0 else "_dgrad") + ("_rows" if sparse else ""), M, Nout, K, f"{KH}x{KW}", 1), 2.0 * M * Nout * K
+        return (pre + ("_fwd" if mode == 0 else "_dgrad") + ("_rows" if sparse else ""), M, d.Nout, K, f"{d.KH}x{d.KW}", 1), 2.0 * M * d.Nout * K
     _timed(key_flops, launch)
 
 
@@ -535,22 +540,19 @@ def _w3_pays(M, Co, K, Ci, nbatch=1, free_splits=False):
 HW2_SINGLE_MIN_FLOPS = 9e10      # smallest single weight gradient routed to hw2_kernel (256 x 256 tiles, single-level accumulation over <= 20480 pixels): the x-gate conv, sal_conv and -- round 4, tools/encoder_census.py --hw2-min-flops: -2.0 ms per step -- the encoder's layer-3 / layer-4 weight gradients from Co x K = 256 x 2304 on (below that the 256 KB slab tiles cost more than the larger tile saves)
 
 
-def _wgrad_b3(Xs, dYs, dW, *, N_img, Hi, Wi, Ci, Ho, Wo, Co, ldo, KH=1, KW=1, stride=1, pad=0, dil=1, beta=0, alpha=1.0,
-              ws_slot=0):
-    if not isinstance(Xs, SplitOperand):
-        Xs, dYs = SplitOperand(Xs, None, "bf16x3"), SplitOperand(dYs, None, "bf16x3")
+def _wgrad_b3(d: WgradDesc, Xs, dYs, dW):
+    """the weight-gradient GEMM that d describes, on split operands"""
     assert Xs.scheme == dYs.scheme, (Xs.scheme, dYs.scheme)
-    d = WgradDesc(N_img, Hi, Wi, Ci, Ci, Ho, Wo, Co, Co, KH, KW, stride, pad, dil, ldo, int(beta), float(alpha), 1, 0, 0, 0)
     L = hip.lib()
     f16 = Xs.scheme == "f16x2"
     if f16:      # K = pixels: per-channel scales of either operand factor out in the epilogue / slab reduce
         d.x_scale_vec, d.y_scale_vec = int(Xs.kind == "cols"), int(dYs.kind == "cols")
-    M = N_img * Ho * Wo
+    M, Co, K = d.N_img * d.Ho * d.Wo, d.Co, d.KH * d.KW * d.Ci
     # large single weight gradients whose shape fits the 256 x 256-tile kernel (x-gate conv, sal_conv): hw2_kernel with one segment
     big = L.sp_conv_wgrad_f16x2_multi_workspace(C.byref(d), 1) if (f16 and HW2_SINGLE and not THROUGHPUT_MODE
-                                                                   and 2.0 * M * COST_M_SCALE * Co * KH * KW * Ci >= HW2_SINGLE_MIN_FLOPS) else 0
+                                                                   and 2.0 * M * COST_M_SCALE * Co * K >= HW2_SINGLE_MIN_FLOPS) else 0
     ws = hip.workspace(big if big > 0 else (L.sp_conv_wgrad_f16x2_workspace if f16 else L.sp_conv_wgrad_bf16x3_workspace)(C.byref(d)),
-                       dW.device, slot=ws_slot)
+                       dW.device, slot=0)
 
     def launch():
         if big > 0:
@@ -565,8 +567,110 @@ def _wgrad_b3(Xs, dYs, dW, *, N_img, Hi, Wi, Ci, Ho, Wo, Co, ldo, KH=1, KW=1, st
         else:
             check(L.sp_conv_wgrad_bf16x3(C.byref(d), ptr(Xs.buf), ptr(dYs.buf), ptr(dW), ptr(ws), hip.stream()),
                   "sp_conv_wgrad_bf16x3")
-    _timed(lambda: (((("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3") + ("_wgrad_multi" if big > 0 else "_wgrad"), M, Co, KH * KW * Ci, f"{KH}x{KW}", 1),
-                    2.0 * M * Co * KH * KW * Ci), launch)
+    _timed(lambda: (((("h1" if THROUGHPUT_MODE else "h2") if f16 else "b3") + ("_wgrad_multi" if big > 0 else "_wgrad"), M, Co, K, f"{d.KH}x{d.KW}", 1),
+                    2.0 * M * Co * K), launch)
+
+
+class ConvGeom(namedtuple("ConvGeom", "N H W Ci Co KH KW stride pad dil Ho Wo")):
+    """One application of a conv: x [N,H,W,Ci] (NHWC) against the physical weight [Co,KH,KW,Ci] -> y [N,Ho,Wo,Co].  The only place
+    that knows how its three GEMMs (forward, data gradient, weight gradient) fill their descriptors and how their cost models are asked;
+    a forward pass that predicts what its backward pass will decide asks the same methods the backward pass calls.  Immutable; built
+    with ConvGeom.of, which derives Ho and Wo."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, x_shape, Co, KH, KW, stride=1, pad=0, dil=1) -> "ConvGeom":
+        N, H, W, Ci = x_shape
+        return cls(N, H, W, Ci, Co, KH, KW, stride, pad, dil,
+                   (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1)
+
+    @property
+    def M(self) -> int:          # output pixels: rows of the forward GEMM, contraction length of the weight gradient
+        return self.N * self.Ho * self.Wo
+
+    @property
+    def K(self) -> int:          # contraction length of the forward GEMM = row length of the physical weight
+        return self.KH * self.KW * self.Ci
+
+    # ---- descriptors (kw: relu / beta) ----
+    def fwd_desc(self, **kw) -> ConvDesc:
+        return ConvDesc(N_img=self.N, Hi=self.H, Wi=self.W, Kc=self.Ci, ldx=self.Ci, Ho=self.Ho, Wo=self.Wo, Nout=self.Co, ldc=self.Co,
+                        KH=self.KH, KW=self.KW, stride=self.stride, pad=self.pad, dil=self.dil, mode=0, ldw=self.K, alpha=1.0, nbatch=1, **kw)
+
+    def dgrad_desc(self, split: bool, **kw) -> ConvDesc:
+        """the data gradient is the same gather with input and output swapped (mode 1).  The fp32 kernel reads the physical weight as it
+        is (rows of Ci per tap and output channel: ldw = Ci), the split kernels read the transposed operand of split_op_wT, rows ci with
+        k = (tap, co): ldw = KH * KW * Co"""
+        return ConvDesc(N_img=self.N, Hi=self.Ho, Wi=self.Wo, Kc=self.Co, ldx=self.Co, Ho=self.H, Wo=self.W, Nout=self.Ci, ldc=self.Ci,
+                        KH=self.KH, KW=self.KW, stride=self.stride, pad=self.pad, dil=self.dil, mode=1,
+                        ldw=self.KH * self.KW * self.Co if split else self.Ci, alpha=1.0, nbatch=1, **kw)
+
+    def wgrad_desc(self, **kw) -> WgradDesc:
+        return WgradDesc(N_img=self.N, Hi=self.H, Wi=self.W, Ci=self.Ci, ldx=self.Ci, Ho=self.Ho, Wo=self.Wo, Co=self.Co, ldy=self.Co,
+                         KH=self.KH, KW=self.KW, stride=self.stride, pad=self.pad, dil=self.dil, ldo=self.K, alpha=1.0, nbatch=1, **kw)
+
+    # ---- cost models: does the GEMM run on the split path?  free_a / free_splits: its split activation-side operand(s) exist already;
+    # a_elems: elements of the activation-side tensor.  _b3_pays / _w3_pays are looked up at call time (tests and tools replace them) ----
+    def fwd_split(self, free_a=False, a_elems=None) -> bool:
+        return _b3_pays(self.M, self.Co, self.K, self.Ci, a_elems=a_elems, free_a=free_a)
+
+    def dgrad_split(self, free_a=False, a_elems=None) -> bool:
+        return _b3_pays(self.N * self.H * self.W, self.Ci, self.KH * self.KW * self.Co, self.Co, a_elems=a_elems, free_a=free_a)
+
+    @property
+    def wgrad_scheme(self) -> str:
+        return _wgrad_scheme(self.Ci, self.Co)
+
+    def wgrad_split(self, free_splits=False) -> Optional[str]:
+        """the scheme both operands of the weight-gradient GEMM must have when it runs on the split path, else None"""
+        return self.wgrad_scheme if _w3_pays(self.M, self.Co, self.K, self.Ci, free_splits=free_splits) else None
+
+
+def _conv_fwd(g: ConvGeom, x, wp, bias, y, *, relu=False, wcache=None, channel=False, free_a=False, a_elems=None, bn_stats=False):
+    """y = conv(x, wp) on the back-end the cost model picks -> (split x it ran from or None, BatchNorm statistics of y or None)"""
+    d = g.fwd_desc(relu=int(relu))
+    if not g.fwd_split(free_a, a_elems):
+        _igemm(d, x, wp, bias, y)
+        return None, None
+    xs = split_op(x, channel=channel)
+    wsplit = _weight_operand(wp, xs, wcache)
+    stats = None
+    if bn_stats and BN_SPLIT and xs.scheme == "f16x2" and not THROUGHPUT_MODE and bias is None and not relu:
+        # bn_stats: a train-mode BatchNorm follows -- the epilogue writes the first stage of its batch statistics
+        G = hip.lib().sp_conv_stats_tiles(C.byref(d))         # M-tiles of the kernel that will run this conv
+        stats = (torch.empty((G, 2, g.Co), dtype=torch.float64, device=x.device),
+                 torch.empty((G, 2, g.Co), dtype=torch.float32, device=x.device), G)
+    _igemm_b3(d, xs, wsplit, bias, y, stats=stats)
+    return xs, stats
+
+
+def _conv_dgrad(g: ConvGeom, dy, wp, dx, *, dys=None, wcache=None, channel=False, free_a=False, a_elems=None, beta=0, rows=None):
+    """dx (+= when beta) = data gradient of conv(x, wp) -> the split dy it ran from (dys when that has the right scheme) or None"""
+    if not g.dgrad_split(free_a, a_elems):
+        _fp32_required(dy, "the fp32 data-gradient GEMM")
+        _igemm(g.dgrad_desc(False, beta=beta), dy, wp, None, dx)
+        return None
+    if dys is None or dys.scheme != _scheme_for(g.Co):
+        dys = split_op(dy, channel=channel)
+    _igemm_b3(g.dgrad_desc(True, beta=beta), dys, _weight_operand(wp, dys, wcache, transposed=True), None, dx, rows=rows)
+    return dys
+
+
+def _conv_wgrad(g: ConvGeom, x, dy, dwp, *, xs=None, dys=None, channel=False):
+    """dwp [Co,KH,KW,Ci] = weight gradient of conv(x, wp); xs / dys: split operands that exist already (the forward's x, the data
+    gradient's dy), used when their scheme is the weight gradient's"""
+    wsch = g.wgrad_scheme
+    dy_cached = getattr(dy, "_sp_cache", None)       # the producer of dy (a BatchNorm / cell backward) already wrote its split form
+    if dys is None and dy_cached is not None and wsch in dy_cached:
+        dys = dy_cached[wsch]
+    if dys is not None and dys.scheme != wsch:
+        dys = None
+    if g.wgrad_split(free_splits=xs is not None and dys is not None):
+        _wgrad_b3(g.wgrad_desc(), xs if xs is not None else split_op(x, wsch, channel=channel),
+                  dys if dys is not None else split_op(dy, wsch, channel=channel), dwp)
+    else:
+        _fp32_required(dy, "the fp32 weight-gradient GEMM")
+        _wgrad(g.wgrad_desc(), x, dy, dwp)
 
 
 def colsum(x2d: torch.Tensor, C_: int, ld: int, M: int) -> torch.Tensor:
@@ -810,10 +914,6 @@ def _phys(w: torch.Tensor) -> torch.Tensor:
     return p if p.is_contiguous() else p.contiguous()
 
 
-def _out_hw(H, W, KH, KW, stride, pad, dil):
-    return (H + 2 * pad - dil * (KH - 1) - 1) // stride + 1, (W + 2 * pad - dil * (KW - 1) - 1) // stride + 1
-
-
 # ----------------------------------------------------------------------------------------------------
 # convolution
 # ----------------------------------------------------------------------------------------------------
@@ -830,61 +930,42 @@ class _Conv2d(Function):
         # wcache: dict shared by all applications of the SAME weight inside one forward/backward (the h-gate conv runs T times):
         # its split forms ("w": forward operand, "wT": data-gradient operand) are produced once instead of per step
         x = x.contiguous()
-        N, H, W_, Ci = x.shape
         wp = _phys(w.detach())
-        Co, KH, KW, Ciw = wp.shape
-        assert Ciw == Ci, (wp.shape, x.shape)
-        Ho, Wo = _out_hw(H, W_, KH, KW, stride, pad, dil)
-        y = torch.empty((N, Ho, Wo, Co), dtype=torch.float32, device=x.device)
-        xs = None
+        assert wp.shape[3] == x.shape[3], (wp.shape, x.shape)
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        g = ConvGeom.of(x.shape, *wp.shape[:3], stride, pad, dil)
+        y = torch.empty((g.N, g.Ho, g.Wo, g.Co), dtype=torch.float32, device=x.device)
         shared = getattr(x, "_sp_cache", None) is not None
-        if getattr(x, "_sp_uninit", False) and not conv_runs_from_split(x.shape, w, stride, pad, dil, ctx.needs_input_grad[1]):
+        if getattr(x, "_sp_uninit", False) and not conv_runs_from_split(x.shape, w, stride, pad, dil, need_dw):
             raise RuntimeError("scanpaths_amd: a BatchNorm left this input's fp32 form unwritten (skip_z) but this conv does not run "
                                "from the split operand alone; run with SP_BN_SKIP_DX=0")
-        if _b3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, a_elems=x.numel(), free_a=shared):
-            xs = split_op(x, channel=True)
-            wsplit = _weight_operand(wp, xs, wcache)
-            stats = None
-            if bn_stats and BN_SPLIT and xs.scheme == "f16x2" and not THROUGHPUT_MODE and bias is None and not relu:
-                # bn_stats: a train-mode BatchNorm follows -- the epilogue writes the first stage of its batch statistics
-                dd = ConvDesc(N, H, W_, Ci, Ci, Ho, Wo, Co, Co, KH, KW, stride, pad, dil, 0, KH * KW * Ci, 1.0, 0, 0, 1, 0, 0, 0, 0, None)
-                G = hip.lib().sp_conv_stats_tiles(C.byref(dd))         # M-tiles of the kernel that will run this conv
-                stats = (torch.empty((G, 2, Co), dtype=torch.float64, device=x.device),
-                         torch.empty((G, 2, Co), dtype=torch.float32, device=x.device), G)
-            _igemm_b3(xs, wsplit, bias, y, N_img=N, Hi=H, Wi=W_, Kc=Ci, ldx=Ci, Ho=Ho, Wo=Wo, Nout=Co, ldc=Co,
-                      ldw=KH * KW * Ci, KH=KH, KW=KW, stride=stride, pad=pad, dil=dil, mode=0, relu=relu, stats=stats)
+        xs, stats = _conv_fwd(g, x, wp, bias, y, relu=relu, wcache=wcache, channel=True, free_a=shared, a_elems=x.numel(), bn_stats=bn_stats)
+        if xs is not None:
             y._sp_from_split = xs.scheme == "f16x2"        # a BatchNorm behind this conv may emit the split gradient (bn_act)
             if stats is not None:
                 FUSION_COUNTS["conv_bn_stats"] += 1
                 y._sp_bnstats = stats
+            # the weight-gradient GEMM consumes the same split operand: keep it (6 B/element) instead of re-splitting x in
+            # backward (HBM pass of 10 B/element per conv); sized for 288 GB
+            keep = need_dw and g.wgrad_split(free_splits=True) == xs.scheme
             # Both backward GEMMs of this conv would read ONLY the split form of the output gradient: a BatchNorm behind it (the
             # single consumer of y, see bn_act skip_dx) may then leave the fp32 gradient unwritten.  The token lets this conv's
             # backward fail loudly if such a gradient ever arrives without its split form.
-            wsch = _wgrad_scheme(Ci, Co)
-            if (y._sp_from_split and wsch == "f16x2" and bias is None and not relu
-                    and (not ctx.needs_input_grad[1] or (xs.scheme == wsch and _w3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci,
-                                                                                          free_splits=True)))
-                    and (not ctx.needs_input_grad[0] or _b3_pays(N * H * W_, Ci, KH * KW * Co, Co, a_elems=y.numel(),
-                                                                  free_a=True))):
+            if (y._sp_from_split and g.wgrad_scheme == "f16x2" and bias is None and not relu and (not need_dw or keep)
+                    and (not need_dx or g.dgrad_split(free_a=True, a_elems=y.numel()))):
                 ctx.dy_token = y._sp_dy_token = {"skipped": False}
-            # the weight-gradient GEMM consumes the same split operand: keep it (6 B/element) instead of re-splitting x in
-            # backward (HBM pass of 10 B/element per conv); sized for 288 GB
-            if not (ctx.needs_input_grad[1] and _w3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, free_splits=True)
-                    and xs.scheme == _wgrad_scheme(Ci, Co)):
+            if not keep:
                 xs = None
-        else:
-            _igemm(x, wp, bias, y, N_img=N, Hi=H, Wi=W_, Kc=Ci, ldx=Ci, Ho=Ho, Wo=Wo, Nout=Co, ldc=Co, ldw=KH * KW * Ci,
-                   KH=KH, KW=KW, stride=stride, pad=pad, dil=dil, mode=0, relu=relu)
         ctx.xs_scheme = (xs.scheme, xs.kind) if xs is not None else None
         xs_buf, xs_scale = (xs.buf, xs.scale) if xs is not None else (None, None)
-        ctx.cfg = (stride, pad, dil, relu, bias is not None)
+        ctx.geom, ctx.cfg = g, (relu, bias is not None)
         ctx.wcache = wcache
         ctx.save_for_backward(x, wp, y if relu else None, xs_buf, xs_scale)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        stride, pad, dil, relu, has_bias = ctx.cfg
+        relu, has_bias = ctx.cfg
         x, wp, y, xs_buf, xs_scale = ctx.saved_tensors
         xs = SplitOperand(xs_buf, xs_scale, *ctx.xs_scheme) if xs_buf is not None else None
         if ctx.dy_token is not None and ctx.dy_token["skipped"] and getattr(dy, "_sp_cache", None) is None:
@@ -895,7 +976,7 @@ class _Conv2d(Function):
             dyr = torch.empty_like(dy)
             check(hip.lib().sp_relu_bwd(ptr(dy), ptr(y), dy.numel(), ptr(dyr), hip.stream()), "sp_relu_bwd")
             dy = dyr
-        dx, dw = _conv_backward(x, wp, dy, xs, stride, pad, dil, ctx.wcache, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+        dx, dw = _conv_backward(ctx.geom, x, wp, dy, xs, ctx.wcache, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                 accum=ctx.grad_accum, defer_final=ctx.defer_final, step=ctx.step, w_param=ctx.w_param)
         if ctx.grad_store is not None and dx is not None:
             ctx.grad_store.first = dx
@@ -923,7 +1004,7 @@ class DeferredWgrad:
         return first
 
 
-def _flush_deferred(defer, wp, geom):
+def _flush_deferred(defer, wp, g: ConvGeom):
     """dW of all recorded applications: one multi-application launch where the kernel's shape constraints hold, else one launch per
     application accumulating in place"""
     items, defer.items, defer.claimed = defer.items, [], False
@@ -933,17 +1014,14 @@ def _flush_deferred(defer, wp, geom):
         # first they leave a tail of short ones (latest-first ended the launch on its longest workgroups).  Dense and sparse launches
         # use the same order, so the fixed-order slab reduce keeps them bit-identical.
         items = sorted(items, key=lambda it: it[2])
-    Co, KH, KW, Ci = wp.shape
     dwp = torch.empty_like(wp)
     L = hip.lib()
     xs0, dys0, _ = items[0]
     same = all(x.kind == xs0.kind and y.kind == dys0.kind for x, y, _ in items)
     steps = [st for _, _, st in items]
     toks = [getattr(st, "rows", None) for st in steps]
-    rc = rows_ctx(steps[0], geom["N_img"]) if (toks and toks[0] is not None and all(tk is toks[0] for tk in toks)) else None
-    d = WgradDesc(geom["N_img"], geom["Hi"], geom["Wi"], Ci, Ci, geom["Ho"], geom["Wo"], Co, geom.get("ldy", Co), KH, KW, geom["stride"],
-                  geom["pad"], geom["dil"], KH * KW * Ci, 0, 1.0, 1, 0, 0, 0)
-    d.x_scale_vec, d.y_scale_vec = int(xs0.kind == "cols"), int(dys0.kind == "cols")
+    rc = rows_ctx(steps[0], g.N) if (toks and toks[0] is not None and all(tk is toks[0] for tk in toks)) else None
+    d = g.wgrad_desc(x_scale_vec=int(xs0.kind == "cols"), y_scale_vec=int(dys0.kind == "cols"))
     nseg = len(items)
     wsb = L.sp_conv_wgrad_f16x2_multi_workspace(C.byref(d), nseg) if (same and not THROUGHPUT_MODE and 1 < nseg <= 16) else 0
     if wsb > 0:
@@ -959,33 +1037,28 @@ def _flush_deferred(defer, wp, geom):
             check(L.sp_conv_wgrad_f16x2_multi(C.byref(d), nseg, Xa, Sxa, Ya, Sya, ptr(dwp), ptr(ws), ptr(rc.last) if rc is not None else None,
                                               seg_steps, hip.stream()), "sp_conv_wgrad_f16x2_multi")
         FUSION_COUNTS["wgrad_multi"] += 1
-        _timed(lambda: (("h2_wgrad_multi" + ("_rows" if rc is not None else ""), geom["N_img"] * geom["Ho"] * geom["Wo"] * nseg, Co, KH * KW * Ci,
-                         f"{KH}x{KW}", nseg), 2.0 * geom["N_img"] * geom["Ho"] * geom["Wo"] * nseg * Co * KH * KW * Ci), launch)
+        _timed(lambda: (("h2_wgrad_multi" + ("_rows" if rc is not None else ""), g.M * nseg, g.Co, g.K, f"{g.KH}x{g.KW}", nseg),
+                        2.0 * g.M * nseg * g.Co * g.K), launch)
     else:
-        g2 = {k: v for k, v in geom.items() if k != "ldy"}
         for k, (x, y, _) in enumerate(items):
-            _wgrad_b3(x, y, dwp, beta=int(k > 0), ldo=KH * KW * Ci, Ci=Ci, Co=Co, KH=KH, KW=KW, **g2)
+            _wgrad_b3(g.wgrad_desc(beta=int(k > 0)), x, y, dwp)
     return dwp.permute(0, 3, 1, 2)
 
 
-def _conv_backward(x, wp, dy, xs, stride, pad, dil, wcache, need_dx, need_dw, accum=None, defer_final=False, step=None, w_param=None):
+def _conv_backward(g: ConvGeom, x, wp, dy, xs, wcache, need_dx, need_dw, accum=None, defer_final=False, step=None, w_param=None):
     """data and weight gradient of y = conv(x, wp) (NHWC, physical weight [Co,KH,KW,Ci]); xs: the forward's split x or None;
     accum: GradMerge whose ``first`` (another consumer's gradient of x) the data gradient is added to in place"""
-    N, H, W_, Ci = x.shape
-    Co, KH, KW, _ = wp.shape
-    _, Ho, Wo, _ = dy.shape
     dx = dw = None
     dys = None
     dy_cached = getattr(dy, "_sp_cache", None)       # the producer of dy (a BatchNorm / cell backward) already wrote its split form
     defer = wcache.get("defer") if (DEFER_WGRAD and isinstance(wcache, dict)) else None
-    geom = dict(N_img=N, Hi=H, Wi=W_, Ho=Ho, Wo=Wo, stride=stride, pad=pad, dil=dil)
-    rc = rows_ctx(step, N)          # samples whose gradient rows are exactly zero at this decode step (loss masks)
+    rc = rows_ctx(step, g.N)          # samples whose gradient rows are exactly zero at this decode step (loss masks)
     deferred = False
     if need_dw and defer is not None:
-        wsch = _wgrad_scheme(Ci, Co)
-        if wsch == "f16x2" and xs is not None and xs.scheme == wsch and \
-                _w3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, free_splits=dy_cached is not None and wsch in dy_cached):
-            dys = dy_cached[wsch] if (dy_cached is not None and wsch in dy_cached) else split_op(dy, wsch, channel=True)
+        wsch = g.wgrad_scheme
+        have = dy_cached is not None and wsch in dy_cached
+        if wsch == "f16x2" and xs is not None and xs.scheme == wsch and g.wgrad_split(free_splits=have):
+            dys = dy_cached[wsch] if have else split_op(dy, wsch, channel=True)
             defer.items.append((xs, dys, step))
             deferred = True
     if need_dx:
@@ -995,35 +1068,15 @@ def _conv_backward(x, wp, dy, xs, stride, pad, dil, wcache, need_dx, need_dw, ac
             FUSION_COUNTS["grad_merge"] += 1
         else:
             dx = torch.empty_like(x)
-        if _b3_pays(N * H * W_, Ci, KH * KW * Co, Co, a_elems=dy.numel(), free_a=dy_cached is not None or dys is not None):
-            if dys is None or dys.scheme != _scheme_for(Co):
-                dys = split_op(dy, channel=True)
-            wT = _weight_operand(wp, dys, wcache, transposed=True)
-            _igemm_b3(dys, wT, None, dx, N_img=N, Hi=Ho, Wi=Wo, Kc=Co, ldx=Co, Ho=H, Wo=W_, Nout=Ci,
-                      ldc=Ci, ldw=KH * KW * Co, KH=KH, KW=KW, stride=stride, pad=pad, dil=dil, mode=1, beta=beta,
-                      rows=(rc, step) if rc is not None else None)
-        else:
-            _fp32_required(dy, "the fp32 data-gradient GEMM")
-            _igemm(dy, wp, None, dx, N_img=N, Hi=Ho, Wi=Wo, Kc=Co, ldx=Co, Ho=H, Wo=W_, Nout=Ci, ldc=Ci, ldw=Ci, KH=KH,
-                   KW=KW, stride=stride, pad=pad, dil=dil, mode=1, beta=beta)
+        dys = _conv_dgrad(g, dy, wp, dx, dys=dys, wcache=wcache, channel=True, free_a=dy_cached is not None or dys is not None,
+                          a_elems=dy.numel(), beta=beta, rows=(rc, step) if rc is not None else None) or dys
     slot = None
     if need_dw and not deferred:
         if defer is None:          # (a weight with deferred applications is summed by _flush_deferred: ordinary path)
             slot, dwp = _take_grad_view(w_param, (0, 2, 3, 1))
         if slot is None:
             dwp = torch.empty_like(wp)
-        wsch = _wgrad_scheme(Ci, Co)
-        if dys is None and dy_cached is not None and wsch in dy_cached:
-            dys = dy_cached[wsch]
-        free = xs is not None and (dys is not None and dys.scheme == wsch)
-        if _w3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, free_splits=free):
-            _wgrad_b3(xs if xs is not None else split_op(x, wsch, channel=True),
-                      dys if dys is not None and dys.scheme == wsch else split_op(dy, wsch, channel=True), dwp, N_img=N, Hi=H,
-                      Wi=W_, Ci=Ci, Ho=Ho, Wo=Wo, Co=Co, ldo=KH * KW * Ci, KH=KH, KW=KW, stride=stride, pad=pad, dil=dil)
-        else:
-            _fp32_required(dy, "the fp32 weight-gradient GEMM")
-            _wgrad(x, dy, dwp, N_img=N, Hi=H, Wi=W_, Ci=Ci, ldx=Ci, Ho=Ho, Wo=Wo, Co=Co, ldy=Co, ldo=KH * KW * Ci,
-                   KH=KH, KW=KW, stride=stride, pad=pad, dil=dil)
+        _conv_wgrad(g, x, dy, dwp, xs=xs, dys=dys, channel=True)
         if slot is not None:
             slot.done()            # written into the parameter's flat-buffer view: autograd gets None
         else:
@@ -1031,28 +1084,28 @@ def _conv_backward(x, wp, dy, xs, stride, pad, dil, wcache, need_dx, need_dw, ac
     if need_dw and defer is not None and defer_final and defer.items:
         # this application runs last in backward: the recorded applications (its own among them, unless it took the plain path) in
         # one launch
-        dsum = _flush_deferred(defer, wp, geom)
+        dsum = _flush_deferred(defer, wp, g)
         dw = dsum if dw is None else dw + dsum
     return dx, dw
 
 
+def _geom_of_logical(x_shape, w, stride=1, pad=0, dil=1) -> ConvGeom:
+    """the geometry of conv2d(x, w) from the LOGICAL (OIHW) weight, for questions asked before the conv runs"""
+    return ConvGeom.of(x_shape, w.shape[0], w.shape[2], w.shape[3], stride, pad, dil)
+
+
 def conv_takes_split(x_shape, w, stride=1, pad=0, dil=1) -> bool:
     """would conv2d(x, w) run on the 2xfp16 split path if x [N,H,W,Ci] arrived with its split operand attached (bn_act emit_split)"""
-    N, H, W_, Ci = x_shape
-    Co, _, KH, KW = w.shape
-    Ho, Wo = _out_hw(H, W_, KH, KW, stride, pad, dil)
-    return _scheme_for(Ci) == "f16x2" and _b3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, a_elems=N * H * W_ * Ci, free_a=True)
+    g = _geom_of_logical(x_shape, w, stride, pad, dil)
+    return _scheme_for(g.Ci) == "f16x2" and g.fwd_split(free_a=True, a_elems=g.N * g.H * g.W * g.Ci)
 
 
 def conv_runs_from_split(x_shape, w, stride=1, pad=0, dil=1, need_dw=True) -> bool:
     """conv2d(x, w) reads x only through its split operand: forward on the split path, and (if the weight needs a gradient) the
     weight-gradient GEMM from the split operand kept by the forward pass"""
-    N, H, W_, Ci = x_shape
-    Co, _, KH, KW = w.shape
-    Ho, Wo = _out_hw(H, W_, KH, KW, stride, pad, dil)
     if not conv_takes_split(x_shape, w, stride, pad, dil):
         return False
-    return (not need_dw) or (_wgrad_scheme(Ci, Co) == "f16x2" and _w3_pays(N * Ho * Wo, Co, KH * KW * Ci, Ci, free_splits=True))
+    return (not need_dw) or _geom_of_logical(x_shape, w, stride, pad, dil).wgrad_split(free_splits=True) == "f16x2"
 
 
 def conv2d(x, w, bias=None, stride=1, pad=0, dil=1, relu=False, wcache=None, bn_stats=False, grad_store=None, grad_accum=None, step=None):
@@ -1145,9 +1198,8 @@ class _Gemm(Function):
         out_shape = (M, Nn) if a.dim() == 2 else (nb, M, Nn)
         c = torch.empty(out_shape, dtype=torch.float32, device=a.device)
         sW = b.stride(0) if bb else 0
-        _igemm(a, b, bias, c, N_img=M, Hi=1, Wi=1, Kc=K, ldx=lda, Ho=1, Wo=1, Nout=Nn, ldc=Nn,
-               ldw=(K if layout == "nk" else Nn), mode=(0 if layout == "nk" else 1), alpha=alpha, relu=relu, nbatch=nb,
-               sX=sA, sW=sW, sC=M * Nn)
+        _igemm(_gemm_desc(M, Nn, K, ldx=lda, ldw=(K if layout == "nk" else Nn), ldc=Nn, mode=(0 if layout == "nk" else 1), alpha=alpha,
+                          relu=relu, nbatch=nb, sX=sA, sW=sW, sC=M * Nn), a, b, bias, c)
         ctx.cfg = (layout, alpha, relu, bias is not None)
         ctx.save_for_backward(a, b, c if relu else None)
         return c
@@ -1170,12 +1222,8 @@ class _Gemm(Function):
         if ctx.needs_input_grad[0]:
             da = torch.empty(a.shape, dtype=torch.float32, device=a.device)
             # dA[M,K] = alpha * dC[M,N] @ (B as [N,K] rows)   -> 'kn' on an [N][K] matrix, or 'nk' on a [K][N] one
-            if layout == "nk":
-                _igemm(dc, b, None, da, N_img=M, Hi=1, Wi=1, Kc=Nn, ldx=Nn, Ho=1, Wo=1, Nout=K, ldc=K, ldw=K, mode=1,
-                       alpha=alpha, nbatch=nb, sX=M * Nn, sW=sW, sC=M * K)
-            else:
-                _igemm(dc, b, None, da, N_img=M, Hi=1, Wi=1, Kc=Nn, ldx=Nn, Ho=1, Wo=1, Nout=K, ldc=K, ldw=Nn, mode=0,
-                       alpha=alpha, nbatch=nb, sX=M * Nn, sW=sW, sC=M * K)
+            _igemm(_gemm_desc(M, K, Nn, ldx=Nn, ldw=(K if layout == "nk" else Nn), ldc=K, mode=(1 if layout == "nk" else 0), alpha=alpha,
+                              nbatch=nb, sX=M * Nn, sW=sW, sC=M * K), dc, b, None, da)
         if ctx.needs_input_grad[1] and ctx.defer is not None:
             ctx.defer.items.append((a, dc))
             if ctx.defer_final:          # this application runs last in backward: one GEMM over the rows of all recorded applications
@@ -1185,8 +1233,8 @@ class _Gemm(Function):
                 ac = ac if ac.stride(-1) == 1 else ac.contiguous()
                 nbc, Mc, _, ldac, sAc = _rows(ac)
                 db = torch.empty(b.shape, dtype=torch.float32, device=b.device)
-                _wgrad(ac, dcc, db, N_img=Mc, Hi=1, Wi=1, Ci=K, ldx=ldac, Ho=1, Wo=1, Co=Nn, ldy=Nn, ldo=K, alpha=alpha,
-                       nbatch=nbc, sX=sAc, sY=Mc * Nn, sO=(b.stride(0) if bb else 0))
+                _wgrad(_gemm_wgrad_desc(Mc, Nn, K, ldx=ldac, ldy=Nn, ldo=K, alpha=alpha, nbatch=nbc, sX=sAc, sY=Mc * Nn,
+                                        sO=(b.stride(0) if bb else 0)), ac, dcc, db)
         elif ctx.needs_input_grad[1]:
             db = torch.empty(b.shape, dtype=torch.float32, device=b.device)
             if bb or nb == 1:
@@ -1195,11 +1243,9 @@ class _Gemm(Function):
                 assert sA == M * lda, "batched A with shared B must be contiguous over the batch"
                 rows, nbt, sAa, sCc, sO = nb * M, 1, 0, 0, 0
             if layout == "nk":    # dB[N,K] = alpha * dC^T A
-                _wgrad(a, dc, db, N_img=rows, Hi=1, Wi=1, Ci=K, ldx=lda, Ho=1, Wo=1, Co=Nn, ldy=Nn, ldo=K, alpha=alpha,
-                       nbatch=nbt, sX=sAa, sY=sCc, sO=sO)
+                _wgrad(_gemm_wgrad_desc(rows, Nn, K, ldx=lda, ldy=Nn, ldo=K, alpha=alpha, nbatch=nbt, sX=sAa, sY=sCc, sO=sO), a, dc, db)
             else:                 # dB[K,N] = alpha * A^T dC
-                _wgrad(dc, a, db, N_img=rows, Hi=1, Wi=1, Ci=Nn, ldx=Nn, Ho=1, Wo=1, Co=K, ldy=lda, ldo=Nn, alpha=alpha,
-                       nbatch=nbt, sX=sCc, sY=sAa, sO=sO)
+                _wgrad(_gemm_wgrad_desc(rows, K, Nn, ldx=Nn, ldy=lda, ldo=Nn, alpha=alpha, nbatch=nbt, sX=sCc, sY=sAa, sO=sO), dc, a, db)
         if has_bias and ctx.needs_input_grad[2]:
             dbias = _colsum_any(dc, Nn)
         return da, db, dbias, None, None, None, None
@@ -1433,19 +1479,12 @@ class _GateConv(Function):
         C4 = wp.shape[0]
         if h is not None:
             h = h.contiguous()
-            _, Hm, Wm, Cc = h.shape
-            hg = torch.empty((B, Hm, Wm, C4), dtype=torch.float32, device=spcol.device)
-            if _b3_pays(B * Hm * Wm, C4, 9 * Cc, Cc):
-                hs_ = split_op(h)
-                _igemm_b3(hs_, _weight_operand(wp, hs_, None), None, hg, N_img=B, Hi=Hm, Wi=Wm, Kc=Cc, ldx=Cc, Ho=Hm, Wo=Wm, Nout=C4,
-                          ldc=C4, ldw=9 * Cc, KH=3, KW=3, pad=1, mode=0)
-            else:
-                _igemm(h, wp, None, hg, N_img=B, Hi=Hm, Wi=Wm, Kc=Cc, ldx=Cc, Ho=Hm, Wo=Wm, Nout=C4, ldc=C4, ldw=9 * Cc,
-                       KH=3, KW=3, pad=1, mode=0)
+            g = ConvGeom.of((B,) + h.shape[1:], C4, 3, 3, pad=1)
+            hg = torch.empty((B, g.H, g.W, C4), dtype=torch.float32, device=spcol.device)
+            _conv_fwd(g, h, wp, None, hg)
         else:
             hg = torch.zeros((B, hw[0], hw[1], C4), dtype=torch.float32, device=spcol.device)
-        _igemm(spcol, wc, None, hg, N_img=P, Hi=1, Wi=1, Kc=KP, ldx=KP, Ho=1, Wo=1, Nout=N3, ldc=C4, ldw=KP, mode=0, beta=1,
-               nbatch=B, sX=P * KP, sW=N3 * KP, sC=P * C4)
+        _igemm(_gemm_desc(P, N3, KP, ldx=KP, ldw=KP, ldc=C4, beta=1, nbatch=B, sX=P * KP, sW=N3 * KP, sC=P * C4), spcol, wc, None, hg)
         ctx.has_h = h is not None
         ctx.save_for_backward(h, wp, spcol, wc)
         return hg
@@ -1459,37 +1498,23 @@ class _GateConv(Function):
         C4 = wp.shape[0]
         dh = dw = dsp = dwc = None
         if ctx.has_h:
-            _, Hm, Wm, Cc = h.shape
+            g = ConvGeom.of((B,) + h.shape[1:], C4, 3, 3, pad=1)
             dys = None
             if ctx.needs_input_grad[0]:
                 dh = torch.empty_like(h)
-                if _b3_pays(B * Hm * Wm, Cc, 9 * C4, C4):
-                    dys = split_op(dhg)
-                    _igemm_b3(dys, _weight_operand(wp, dys, None, transposed=True), None, dh, N_img=B, Hi=Hm, Wi=Wm, Kc=C4, ldx=C4, Ho=Hm, Wo=Wm,
-                              Nout=Cc, ldc=Cc, ldw=9 * C4, KH=3, KW=3, pad=1, mode=1)
-                else:
-                    _igemm(dhg, wp, None, dh, N_img=B, Hi=Hm, Wi=Wm, Kc=C4, ldx=C4, Ho=Hm, Wo=Wm, Nout=Cc, ldc=Cc, ldw=Cc,
-                           KH=3, KW=3, pad=1, mode=1)
+                dys = _conv_dgrad(g, dhg, wp, dh)
             if ctx.needs_input_grad[1]:
                 dwp = torch.empty_like(wp)
-                if _w3_pays(B * Hm * Wm, C4, 9 * Cc, Cc):
-                    wsch = _wgrad_scheme(Cc, C4)
-                    _wgrad_b3(split_op(h, wsch), dys if dys is not None and dys.scheme == wsch else split_op(dhg, wsch), dwp, N_img=B, Hi=Hm, Wi=Wm, Ci=Cc, Ho=Hm,
-                              Wo=Wm, Co=C4, ldo=9 * Cc, KH=3, KW=3, pad=1)
-                else:
-                    _wgrad(h, dhg, dwp, N_img=B, Hi=Hm, Wi=Wm, Ci=Cc, ldx=Cc, Ho=Hm, Wo=Wm, Co=C4, ldy=C4, ldo=9 * Cc,
-                           KH=3, KW=3, pad=1)
+                _conv_wgrad(g, h, dhg, dwp, dys=dys)
                 dw = dwp.permute(0, 3, 1, 2)
         elif ctx.needs_input_grad[1]:
             dw = torch.zeros_like(wp).permute(0, 3, 1, 2)
         if ctx.needs_input_grad[2]:
             dsp = torch.empty_like(spcol)
-            _igemm(dhg, wc, None, dsp, N_img=P, Hi=1, Wi=1, Kc=N3, ldx=C4, Ho=1, Wo=1, Nout=KP, ldc=KP, ldw=KP, mode=1,
-                   nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP)
+            _igemm(_gemm_desc(P, KP, N3, ldx=C4, ldw=KP, ldc=KP, mode=1, nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP), dhg, wc, None, dsp)
         if ctx.needs_input_grad[3]:
             dwc = torch.empty_like(wc)
-            _wgrad(spcol, dhg, dwc, N_img=P, Hi=1, Wi=1, Ci=KP, ldx=KP, Ho=1, Wo=1, Co=N3, ldy=C4, ldo=KP, nbatch=B,
-                   sX=P * KP, sY=P * C4, sO=N3 * KP)
+            _wgrad(_gemm_wgrad_desc(P, N3, KP, ldx=KP, ldy=C4, ldo=KP, nbatch=B, sX=P * KP, sY=P * C4, sO=N3 * KP), spcol, dhg, dwc)
         return dh, dw, dsp, dwc, None
 
 
@@ -1677,15 +1702,14 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
             FUSION_COUNTS["rank1_dsp_split"] += 1
             xs = dpre._sp_cache["f16x2"]
             ws = _split_wcT(wc)             # [B][KP][3C]: K contiguous, one scale per row
-            d = ConvDesc(P, 1, 1, N3, C4, 1, 1, KP, KP, 1, 1, 1, 0, 1, 0, N3, 1.0, 0, 0, B, P * C4, KP * N3, P * KP, 0, None)
+            d = _gemm_desc(P, KP, N3, ldx=C4, ldw=N3, ldc=KP, nbatch=B, sX=P * C4, sW=KP * N3, sC=P * KP)
             d.w_scale_rows = 1
             if rc is not None:          # one item per sample: items without loss gradient at this step are zero tiles
                 d.row_last, d.row_step = rc.last.data_ptr(), int(step)
             check(hip.lib().sp_conv_igemm_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(ws.buf), ptr(ws.scale), None, ptr(dsp),
                                                 hip.stream()), "sp_conv_igemm_f16x2 (batched)")
         else:
-            _igemm(dpre, wc, None, dsp, N_img=P, Hi=1, Wi=1, Kc=N3, ldx=C4, Ho=1, Wo=1, Nout=KP, ldc=KP, ldw=KP, mode=1,
-                   nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP)
+            _igemm(_gemm_desc(P, KP, N3, ldx=C4, ldw=KP, ldc=KP, mode=1, nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP), dpre, wc, None, dsp)
     if need_dwc:
         dwc = torch.empty_like(wc)
         if emit and RANK1_DWC_SPLIT and rank1_split_ok:
@@ -1695,7 +1719,8 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
             FUSION_COUNTS["rank1_dwc_split"] += 1
             ys = dpre._sp_cache["f16x2"]
             xs = split_op(torch.nn.functional.pad(spcol, (0, 32 - KP)), "f16x2")
-            d = hip.WgradDesc(1, P // 64, 64, 32, 32, P // 64, 64, N3, C4, 1, 1, 1, 0, 1, KP, 0, 1.0, B, P * 32, P * C4, N3 * KP)
+            d = WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=N3, ldy=C4, KH=1, KW=1, stride=1, pad=0, dil=1,
+                          ldo=KP, alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * C4, strideO=N3 * KP)
             if rc is not None:
                 d.row_last, d.row_step = rc.last.data_ptr(), int(step)
             check(L.sp_conv_wgrad_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(ys.buf), ptr(ys.scale), ptr(dwc), None, hip.stream()),
@@ -1704,8 +1729,7 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
             ws = hip.workspace(L.sp_rank1_dwc_workspace(B, P, N3, KP), dpre.device, slot=0)
             check(L.sp_rank1_dwc(ptr(dpre), ptr(spcol), B, P, C4, N3, KP, ptr(ws), ptr(dwc), hip.stream()), "sp_rank1_dwc")
         else:
-            _wgrad(spcol, dpre, dwc, N_img=P, Hi=1, Wi=1, Ci=KP, ldx=KP, Ho=1, Wo=1, Co=N3, ldy=C4, ldo=KP, nbatch=B,
-                   sX=P * KP, sY=P * C4, sO=N3 * KP)
+            _wgrad(_gemm_wgrad_desc(P, N3, KP, ldx=KP, ldy=C4, ldo=KP, nbatch=B, sX=P * KP, sY=P * C4, sO=N3 * KP), spcol, dpre, dwc)
     return dpre, dcp, dsp, dwc
 
 
@@ -1720,11 +1744,10 @@ def gateconv_lstm_fusable(h, w_h, spcol) -> bool:
     C % 32 == 0 channels, P % 256 == 0 pixels per sample (a 256-pixel tile inside one sample), KP <= 32"""
     if not (FUSE_GATE_LSTM and USE_BF16X3 and not THROUGHPUT_MODE and h is not None):
         return False
-    N, H, W_, Ci = h.shape
     B, P, KP = spcol.shape
-    Co, _, KH, KW = w_h.shape
-    return (_scheme_for(Ci) == "f16x2" and Ci % 32 == 0 and Co == 4 * Ci and (KH, KW) == (3, 3) and P == H * W_
-            and P % 256 == 0 and KP <= 32 and _b3_pays(N * P, Co, 9 * Ci, Ci, a_elems=h.numel(), free_a=True))
+    g = _geom_of_logical(h.shape, w_h, pad=1)
+    return (_scheme_for(g.Ci) == "f16x2" and g.Ci % 32 == 0 and g.Co == 4 * g.Ci and (g.KH, g.KW) == (3, 3) and P == g.H * g.W
+            and P % 256 == 0 and KP <= 32 and g.fwd_split(free_a=True, a_elems=h.numel()))
 
 
 class _GateConvLstm(Function):
@@ -1736,11 +1759,11 @@ class _GateConvLstm(Function):
         ctx.step = step
         h_prev, xg, c_prev = h_prev.contiguous(), xg.contiguous(), c_prev.contiguous()
         spcol, wc = spcol.contiguous(), wc.contiguous()
-        N, H, W_, Ci = h_prev.shape
         B, P, KP = spcol.shape
         wp = _phys(w_h.detach())
-        Co, KH, KW, _ = wp.shape
-        assert xg.numel() == B * P * Co and wc.shape == (B, 3 * Ci, KP) and N == B, (xg.shape, spcol.shape, wc.shape)
+        g = ConvGeom.of(h_prev.shape, *wp.shape[:3], pad=1)
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        assert xg.numel() == B * P * g.Co and wc.shape == (B, 3 * g.Ci, KP) and g.N == B, (xg.shape, spcol.shape, wc.shape)
         xs = split_op(h_prev)
         wsplit = _weight_operand(wp, xs, wcache)
         if xs.kind != "scalar":
@@ -1749,12 +1772,11 @@ class _GateConvLstm(Function):
         c = torch.empty_like(c_prev)
         h = torch.empty_like(c_prev) if hslot is None else hslot[0].hbuf(hslot[1], c_prev)          # (DrtBatch, t): see _LstmCellRank1
         hint = _amax_hint(xg.device)
-        d = ConvDesc(N, H, W_, Ci, Ci, H, W_, Co, Co, KH, KW, 1, 1, 1, 0, KH * KW * Ci, 1.0, 0, 0, 1, 0, 0, 0, 0, None)
-        d.w_scale_rows = int(wsplit.kind == "rows")
+        d = g.fwd_desc(w_scale_rows=int(wsplit.kind == "rows"))
         cbounds = _cell_bounds(c_prev, c)
         # |h| = |o * c| <= |c| <= t + 1: with that bound the epilogue writes h's split operand itself (no max|h| pass, no split pass)
         hplanes = torch.empty(2 * h.numel() + 32, dtype=torch.float16, device=h.device) \
-            if (LSTM_H_PLANES and hint is not None and cbounds[0] is not None and Ci % 16 == 0) else None
+            if (LSTM_H_PLANES and hint is not None and cbounds[0] is not None and g.Ci % 16 == 0) else None
 
         def launch():
             check(hip.lib().sp_gateconv_lstm_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(wsplit.buf), ptr(wsplit.scale),
@@ -1763,7 +1785,7 @@ class _GateConvLstm(Function):
                                                    ptr(hint) if hplanes is not None else None,
                                                    float(cbounds[0]) if hplanes is not None else 0.0, hip.stream()),
                   "sp_gateconv_lstm_f16x2")
-        _timed(lambda: (("h2_fwd", N * P, Co, KH * KW * Ci, f"{KH}x{KW}", 1), 2.0 * N * P * Co * KH * KW * Ci), launch)
+        _timed(lambda: (("h2_fwd", g.M, g.Co, g.K, f"{g.KH}x{g.KW}", 1), 2.0 * g.M * g.Co * g.K), launch)
         FUSION_COUNTS["gateconv_lstm"] += 1
         FUSION_COUNTS["gateconv_lstm_hplanes"] += int(hplanes is not None)
         if hint is not None:
@@ -1772,18 +1794,17 @@ class _GateConvLstm(Function):
         ctx.set_materialize_grads(False)
         ctx.cbounds = cbounds
         defer = wcache.get("defer") if isinstance(wcache, dict) else None
-        ctx.defer_final = defer.claim() if (defer is not None and ctx.needs_input_grad[1]) else False
-        keep = ctx.needs_input_grad[1] and _w3_pays(N * P, Co, KH * KW * Ci, Ci, free_splits=True) \
-            and xs.scheme == _wgrad_scheme(Ci, Co)
+        ctx.defer_final = defer.claim() if (defer is not None and need_dw) else False
+        keep = need_dw and g.wgrad_split(free_splits=True) == xs.scheme
         ctx.xs_scheme = (xs.scheme, xs.kind) if keep else None
-        ctx.wcache = wcache
+        ctx.geom, ctx.wcache = g, wcache
         # the gate gradient dpre of this step has three consumers: xg's fan-in, the h-gate conv's data and weight gradient.  When all
         # of them read its split form, its fp32 form is never written (_lstm_rank1_backward skip_fp32)
         ctx.fan = getattr(xg, "_sp_fan", None)
         ctx.h_events = getattr(h_prev, "_sp_fan_ev", None)      # (events dict of h_prev's fan-out, this consumer's index) or None
-        ctx.skip_ok = (ctx.fan is not None and _scheme_for(Co) == "f16x2"
-                       and (not ctx.needs_input_grad[0] or _b3_pays(N * P, Ci, KH * KW * Co, Co, a_elems=xg.numel(), free_a=True))
-                       and (not ctx.needs_input_grad[1] or (keep and _wgrad_scheme(Ci, Co) == "f16x2")))
+        ctx.skip_ok = (ctx.fan is not None and _scheme_for(g.Co) == "f16x2"
+                       and (not need_dx or g.dgrad_split(free_a=True, a_elems=xg.numel()))
+                       and (not need_dw or (keep and g.wgrad_scheme == "f16x2")))
         ctx.save_for_backward(gates, c_prev, c, spcol, wc, h_prev, wp, xs.buf if keep else None, xs.scale if keep else None)
         return h, c
 
@@ -1813,7 +1834,7 @@ class _GateConvLstm(Function):
             cached_before = set(ctx.wcache) if isinstance(ctx.wcache, dict) else set()
             with torch.cuda.stream(side):
                 side.wait_event(ready)
-                dhp, _ = _conv_backward(h_prev, wp, dpre, xs, 1, 1, 1, ctx.wcache, True, False, step=ctx.step)
+                dhp, _ = _conv_backward(ctx.geom, h_prev, wp, dpre, xs, ctx.wcache, True, False, step=ctx.step)
                 done = torch.cuda.Event()
                 done.record(side)
             dhp.record_stream(main)                      # allocated under the side stream, read (and freed) on the current one
@@ -1838,9 +1859,9 @@ class _GateConvLstm(Function):
             FUSION_COUNTS["async_dgrad"] += 1
             dw = None
             if ctx.needs_input_grad[1]:
-                _, dw = _conv_backward(h_prev, wp, dpre, xs, 1, 1, 1, ctx.wcache, False, True, defer_final=ctx.defer_final, step=ctx.step)
+                _, dw = _conv_backward(ctx.geom, h_prev, wp, dpre, xs, ctx.wcache, False, True, defer_final=ctx.defer_final, step=ctx.step)
             return dhp, dw, dpre, dcp, dsp, dwc, None, None, None
-        dhp, dw = _conv_backward(h_prev, wp, dpre, xs, 1, 1, 1, ctx.wcache, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+        dhp, dw = _conv_backward(ctx.geom, h_prev, wp, dpre, xs, ctx.wcache, ctx.needs_input_grad[0], ctx.needs_input_grad[1],
                                  defer_final=ctx.defer_final, step=ctx.step)
         return dhp, dw, dpre, dcp, dsp, dwc, None, None, None
 

@@ -355,7 +355,8 @@ def test_split_counts_of_the_weight_gradient_kernels_follow_the_round_quantisati
     L = hip.lib()
 
     def desc(M_img, Ho, Wo, Ci, Co, k):
-        return hip.WgradDesc(M_img, Ho, Wo, Ci, Ci, Ho, Wo, Co, Co, k, k, 1, k // 2, 1, k * k * Ci, 0, 1.0, 1, 0, 0, 0)
+        return hip.WgradDesc(N_img=M_img, Hi=Ho, Wi=Wo, Ci=Ci, ldx=Ci, Ho=Ho, Wo=Wo, Co=Co, ldy=Co, KH=k, KW=k, stride=1, pad=k // 2, dil=1,
+                             ldo=k * k * Ci, beta=0, alpha=1.0, nbatch=1)
 
     def splits(fn, d, *a):
         Co, ldo = d.Co, d.ldo
@@ -379,6 +380,50 @@ def test_split_counts_of_the_weight_gradient_kernels_follow_the_round_quantisati
     # fp32 wgrad_kernel: two workgroups per CU
     fp = L.sp_conv_wgrad_workspace
     assert splits(fp, desc(32, 80, 128, 64, 64, 1)) == 512         # one tile: 512 workgroups (was 128)
+
+
+def test_conv_geometry_fills_the_descriptors_of_its_three_gemms():
+    """Host logic, no GPU: functional.ConvGeom is the one place that fills sp_conv_desc / sp_wgrad_desc for a conv's forward, data-gradient
+    and weight-gradient GEMM.  Every field is pinned against the values the call sites passed by hand before it existed, written out
+    as literals: the data gradient swaps input and output extents and channel counts (mode 1), its weight leading dimension is Ci on the
+    fp32 kernel (the physical weight as it is) but KH * KW * Co on the split kernels (the transposed operand of split_op_wT)."""
+    from scanpaths_amd import functional as F
+
+    def fields(d):
+        return {name: getattr(d, name) for name, _ in d._fields_}
+
+    def conv(**kw):          # a ConvDesc's fields: what every launch leaves at zero, then the given ones
+        return dict(dict(alpha=1.0, beta=0, relu=0, nbatch=1, strideX=0, strideW=0, strideC=0, ksplit=0, workspace=None, w_scale_rows=0,
+                         row_last=None, row_step=0), **kw)
+
+    def wgrad(**kw):
+        return dict(dict(beta=0, alpha=1.0, nbatch=1, strideX=0, strideY=0, strideO=0, x_scale_vec=0, y_scale_vec=0, row_last=None,
+                         row_step=0), **kw)
+
+    # 3 x 3, stride 2, dilation 2, pad 2 on [2, 17, 23, 32] -> [2, 9, 12, 48]
+    g = F.ConvGeom.of((2, 17, 23, 32), 48, 3, 3, stride=2, pad=2, dil=2)
+    assert (g.Ho, g.Wo, g.M, g.K) == (9, 12, 216, 288)
+    assert fields(g.fwd_desc()) == conv(N_img=2, Hi=17, Wi=23, Kc=32, ldx=32, Ho=9, Wo=12, Nout=48, ldc=48, KH=3, KW=3, stride=2, pad=2,
+                                        dil=2, mode=0, ldw=288)
+    assert fields(g.fwd_desc(relu=1)) == conv(N_img=2, Hi=17, Wi=23, Kc=32, ldx=32, Ho=9, Wo=12, Nout=48, ldc=48, KH=3, KW=3, stride=2,
+                                              pad=2, dil=2, mode=0, ldw=288, relu=1)
+    assert fields(g.dgrad_desc(False)) == conv(N_img=2, Hi=9, Wi=12, Kc=48, ldx=48, Ho=17, Wo=23, Nout=32, ldc=32, KH=3, KW=3, stride=2,
+                                               pad=2, dil=2, mode=1, ldw=32)
+    assert fields(g.dgrad_desc(True, beta=1)) == conv(N_img=2, Hi=9, Wi=12, Kc=48, ldx=48, Ho=17, Wo=23, Nout=32, ldc=32, KH=3, KW=3,
+                                                      stride=2, pad=2, dil=2, mode=1, ldw=432, beta=1)
+    assert fields(g.wgrad_desc()) == wgrad(N_img=2, Hi=17, Wi=23, Ci=32, ldx=32, Ho=9, Wo=12, Co=48, ldy=48, KH=3, KW=3, stride=2, pad=2,
+                                           dil=2, ldo=288)
+    # 1 x 1 on [4, 10, 16, 64] -> [4, 10, 16, 256]
+    g = F.ConvGeom.of((4, 10, 16, 64), 256, 1, 1)
+    assert (g.Ho, g.Wo, g.M, g.K) == (10, 16, 640, 64)
+    assert fields(g.fwd_desc()) == conv(N_img=4, Hi=10, Wi=16, Kc=64, ldx=64, Ho=10, Wo=16, Nout=256, ldc=256, KH=1, KW=1, stride=1, pad=0,
+                                        dil=1, mode=0, ldw=64)
+    assert fields(g.dgrad_desc(False)) == conv(N_img=4, Hi=10, Wi=16, Kc=256, ldx=256, Ho=10, Wo=16, Nout=64, ldc=64, KH=1, KW=1, stride=1,
+                                               pad=0, dil=1, mode=1, ldw=64)
+    assert fields(g.dgrad_desc(True)) == conv(N_img=4, Hi=10, Wi=16, Kc=256, ldx=256, Ho=10, Wo=16, Nout=64, ldc=64, KH=1, KW=1, stride=1,
+                                              pad=0, dil=1, mode=1, ldw=256)
+    assert fields(g.wgrad_desc(beta=1)) == wgrad(N_img=4, Hi=10, Wi=16, Ci=64, ldx=64, Ho=10, Wo=16, Co=256, ldy=256, KH=1, KW=1, stride=1,
+                                                 pad=0, dil=1, ldo=64, beta=1)
 
 
 def test_post_accumulate_hook_fires_for_an_undefined_gradient():

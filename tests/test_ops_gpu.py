@@ -646,12 +646,10 @@ def test_row_sparse_data_gradient_in_live_first_tile_order_equals_the_dense_laun
     dy = _rand(nimg, H, W, Co, seed=7).to(dev) * live              # dead samples: exactly zero rows (what the recurrence produces)
     x = torch.zeros(nimg, H, W, Ci, device=dev)
     outs = []
+    geom = F.ConvGeom.of(x.shape, Co, 3, 3, stride=1, pad=1, dil=1)
     for rows in (None, (F.RowsCtx(lastd), step)):
-        dys = F.split_op(dy, channel=True)
-        wT = F._weight_operand(wp, dys, {}, transposed=True)
         dx = torch.full_like(x, float("nan"))
-        F._igemm_b3(dys, wT, None, dx, N_img=nimg, Hi=H, Wi=W, Kc=Co, ldx=Co, Ho=H, Wo=W, Nout=Ci, ldc=Ci, ldw=9 * Co, KH=3, KW=3,
-                    stride=1, pad=1, dil=1, mode=1, beta=0, rows=rows)
+        assert F._conv_dgrad(geom, dy, wp, dx, wcache={}, channel=True, rows=rows) is not None      # ran on the split kernel
         outs.append(dx)
     torch.cuda.synchronize()
     assert torch.isfinite(outs[1]).all()
@@ -890,7 +888,8 @@ def test_batched_pointwise_gemm_with_per_item_weights_on_wider_rows():
     w = (torch.randn(B, N, Kc, generator=g) * 0.1).to(dev)
     xs, ws = F.split_op(x, "f16x2"), F.split_op(w, "f16x2")
     out = torch.full((B, P, N), float("nan"), device=dev)
-    d = hip.ConvDesc(P, 1, 1, Kc, ldx, 1, 1, N, N, 1, 1, 1, 0, 1, 0, Kc, 1.0, 0, 0, B, P * ldx, N * Kc, P * N, 0, None)
+    d = hip.ConvDesc(N_img=P, Hi=1, Wi=1, Kc=Kc, ldx=ldx, Ho=1, Wo=1, Nout=N, ldc=N, KH=1, KW=1, stride=1, pad=0, dil=1, mode=0, ldw=Kc, alpha=1.0,
+                     nbatch=B, strideX=P * ldx, strideW=N * Kc, strideC=P * N)
     L = hip.lib()
     args = (hip.ptr(xs.buf), hip.ptr(xs.scale), hip.ptr(ws.buf), hip.ptr(ws.scale), None, hip.ptr(out), hip.stream())
     assert L.sp_conv_igemm_f16x2(C.byref(d), *args) == 0
@@ -899,7 +898,8 @@ def test_batched_pointwise_gemm_with_per_item_weights_on_wider_rows():
     assert err < 1e-6, err
     for bad in (dict(P=500), dict(sW=N * Kc + 16), dict(ldx=Kc - 16)):      # partial tiles per item / padded weight sets / ldx < Kc
         Pb, sW, lx = bad.get("P", P), bad.get("sW", N * Kc), bad.get("ldx", ldx)
-        db = hip.ConvDesc(Pb, 1, 1, Kc, lx, 1, 1, N, N, 1, 1, 1, 0, 1, 0, Kc, 1.0, 0, 0, B, Pb * lx, sW, Pb * N, 0, None)
+        db = hip.ConvDesc(N_img=Pb, Hi=1, Wi=1, Kc=Kc, ldx=lx, Ho=1, Wo=1, Nout=N, ldc=N, KH=1, KW=1, stride=1, pad=0, dil=1, mode=0, ldw=Kc,
+                          alpha=1.0, nbatch=B, strideX=Pb * lx, strideW=sW, strideC=Pb * N)
         assert L.sp_conv_igemm_f16x2(C.byref(db), *args) == -1, bad
 
 
@@ -916,7 +916,8 @@ def test_batched_weight_gradient_with_padded_taps_on_wider_rows():
     x = torch.randn(B, P, KP, generator=g).to(dev)
     ys, xs = F.split_op(dy, "f16x2"), F.split_op(torch.nn.functional.pad(x, (0, 32 - KP)), "f16x2")
     out = torch.full((B * Co * KP + 64,), 7.0, device=dev)
-    d = hip.WgradDesc(1, P // 64, 64, 32, 32, P // 64, 64, Co, ldy, 1, 1, 1, 0, 1, KP, 0, 1.0, B, P * 32, P * ldy, Co * KP)
+    d = hip.WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=Co, ldy=ldy, KH=1, KW=1, stride=1, pad=0, dil=1, ldo=KP,
+                      alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * ldy, strideO=Co * KP)
     L = hip.lib()
     assert L.sp_conv_wgrad_f16x2_workspace(C.byref(d)) == 0
     assert L.sp_conv_wgrad_f16x2(C.byref(d), hip.ptr(xs.buf), hip.ptr(xs.scale), hip.ptr(ys.buf), hip.ptr(ys.scale), hip.ptr(out), None,
@@ -1056,7 +1057,8 @@ def test_c_abi_error_codes():
     st = hip.stream()
     assert L.sp_split2_f16(None, 64, hip.ptr(x), hip.ptr(x), 0, st) == -2
     assert L.sp_split2_f16(hip.ptr(x), 60, hip.ptr(x), hip.ptr(x), 0, st) == -1          # row length not a multiple of 16
-    d = hip.ConvDesc(1, 4, 4, 48, 48, 4, 4, 64, 64, 1, 1, 1, 0, 1, 0, 48, 1.0, 0, 0, 1, 0, 0, 0, 0, None)
+    d = hip.ConvDesc(N_img=1, Hi=4, Wi=4, Kc=48, ldx=48, Ho=4, Wo=4, Nout=64, ldc=64, KH=1, KW=1, stride=1, pad=0, dil=1, mode=0, ldw=48, alpha=1.0,
+                     nbatch=1)
     assert L.sp_conv_igemm_f16x2(C.byref(d), hip.ptr(x), hip.ptr(x), hip.ptr(x), hip.ptr(x), None, hip.ptr(x), st) == -1   # Kc % 32
     assert L.sp_conv_igemm_f16x2(C.byref(d), None, hip.ptr(x), hip.ptr(x), hip.ptr(x), None, hip.ptr(x), st) == -2
     assert L.sp_lstm_rank1_fwd(hip.ptr(x), None, None, hip.ptr(x), hip.ptr(x), 1, 4, 48, 12, hip.ptr(x), hip.ptr(x), hip.ptr(x), None,

@@ -11,9 +11,10 @@ dev = torch.device("cuda:0")
 x = torch.randn(M, K, device=dev)
 w = torch.randn(N, K, device=dev)
 y = torch.empty(M, N, device=dev)
-xs, ws = F.split3(x), F.split3(w)
+xs, ws = F.split_op(x, "bf16x3"), F.split_op(w, "bf16x3")
+desc = F.ConvGeom.of((1, 1, M, K), N, 1, 1).fwd_desc()
 def run():
-    F._igemm_b3(xs, ws, None, y, N_img=1, Hi=1, Wi=M, Kc=K, ldx=K, Ho=1, Wo=M, Nout=N, ldc=N, ldw=K)
+    F._igemm_b3(desc, xs, ws, None, y)
 run(); torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()

@@ -14,7 +14,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     from scanpaths_amd import functional as F, hip
-    from scanpaths_amd.hip import ConvDesc
     dev, L = torch.device("cuda", 0), hip.lib()
     B, P, Cc, KP = 32, 2560, 512, 20
     C4, N3 = 4 * Cc, 3 * Cc
@@ -40,11 +39,12 @@ def main():
 
     def pair():
         ws = F.split_w(wc.transpose(1, 2).contiguous().view(B * KP, N3), "f16x2")
-        d = ConvDesc(P, 1, 1, N3, C4, 1, 1, KP, KP, 1, 1, 1, 0, 1, 0, N3, 1.0, 0, 0, B, P * C4, KP * N3, P * KP, 0, None)
+        d = F._gemm_desc(P, KP, N3, ldx=C4, ldw=N3, ldc=KP, nbatch=B, sX=P * C4, sW=KP * N3, sC=P * KP)
         d.w_scale_rows = 1
         F.check(L.sp_conv_igemm_f16x2(C.byref(d), ptr(ys.buf), ptr(ys.scale), ptr(ws.buf), ptr(ws.scale), None, ptr(dsp), st), "igemm")
         xs = F.split_op(torch.nn.functional.pad(spcol, (0, 32 - KP)), "f16x2")
-        d2 = hip.WgradDesc(1, P // 64, 64, 32, 32, P // 64, 64, N3, C4, 1, 1, 1, 0, 1, KP, 0, 1.0, B, P * 32, P * C4, N3 * KP)
+        d2 = hip.WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=N3, ldy=C4, KH=1, KW=1, stride=1, pad=0, dil=1, ldo=KP,
+                           alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * C4, strideO=N3 * KP)
         F.check(L.sp_conv_wgrad_f16x2(C.byref(d2), ptr(xs.buf), ptr(xs.scale), ptr(ys.buf), ptr(ys.scale), ptr(dwc), None, st), "wgrad")
 
     def timeit(f, n=30):
@@ -66,11 +66,12 @@ def main():
             F.check(L.sp_rank1_grads_f16x2(ptr(ys.buf), ptr(ys.scale), C4, ptr(ws0.buf), ptr(ws0.scale), ptr(spcol), B, P, N3, KP, ptr(dsp), ptr(dwc),
                                            ptr(wsp), ptr(last), 5, st), "fused")
         def pr():
-            d = ConvDesc(P, 1, 1, N3, C4, 1, 1, KP, KP, 1, 1, 1, 0, 1, 0, N3, 1.0, 0, 0, B, P * C4, KP * N3, P * KP, 0, None)
+            d = F._gemm_desc(P, KP, N3, ldx=C4, ldw=N3, ldc=KP, nbatch=B, sX=P * C4, sW=KP * N3, sC=P * KP)
             d.w_scale_rows = 1
             d.row_last, d.row_step = last.data_ptr(), 5
             F.check(L.sp_conv_igemm_f16x2(C.byref(d), ptr(ys.buf), ptr(ys.scale), ptr(ws0.buf), ptr(ws0.scale), None, ptr(dsp), st), "igemm")
-            d2 = hip.WgradDesc(1, P // 64, 64, 32, 32, P // 64, 64, N3, C4, 1, 1, 1, 0, 1, KP, 0, 1.0, B, P * 32, P * C4, N3 * KP)
+            d2 = hip.WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=N3, ldy=C4, KH=1, KW=1, stride=1, pad=0, dil=1, ldo=KP,
+                               alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * C4, strideO=N3 * KP)
             d2.row_last, d2.row_step = last.data_ptr(), 5
             F.check(L.sp_conv_wgrad_f16x2(C.byref(d2), ptr(xs0.buf), ptr(xs0.scale), ptr(ys.buf), ptr(ys.scale), ptr(dwc), None, st), "wgrad")
         out["live%d_fused_kernel_us" % live] = timeit(fk)

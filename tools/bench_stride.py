@@ -16,9 +16,10 @@ for Ci, Co in ((512, 2048), (512, 2112), (544, 2048), (544, 2112), (512, 1984), 
     hs, ws, wT, gys = F.split_op(h, "f16x2"), F.split_op(wp, "f16x2"), F.split_op_wT(wp, "f16x2"), F.split_op(gy, "f16x2")
     y = torch.empty(B, Hm, Wm, Co, device=dev); dx = torch.empty(B, Hm, Wm, Ci, device=dev); dw = torch.empty_like(wp)
     FL = 2.0 * B * Hm * Wm * Co * 9 * Ci
-    fns = {"fwd": lambda: F._igemm_b3(hs, ws, None, y, N_img=B, Hi=Hm, Wi=Wm, Kc=Ci, ldx=Ci, Ho=Hm, Wo=Wm, Nout=Co, ldc=Co, ldw=9 * Ci, KH=3, KW=3, pad=1, mode=0),
-           "dgrad": lambda: F._igemm_b3(gys, wT, None, dx, N_img=B, Hi=Hm, Wi=Wm, Kc=Co, ldx=Co, Ho=Hm, Wo=Wm, Nout=Ci, ldc=Ci, ldw=9 * Co, KH=3, KW=3, pad=1, mode=1),
-           "wgrad": lambda: F._wgrad_b3(hs, gys, dw, N_img=B, Hi=Hm, Wi=Wm, Ci=Ci, Ho=Hm, Wo=Wm, Co=Co, ldo=9 * Ci, KH=3, KW=3, pad=1)}
+    geom = F.ConvGeom.of(h.shape, Co, 3, 3, pad=1)      # the kernels themselves, operands pre-split: the launchers below the cost models
+    fns = {"fwd": lambda: F._igemm_b3(geom.fwd_desc(), hs, ws, None, y),
+           "dgrad": lambda: F._igemm_b3(geom.dgrad_desc(True), gys, wT, None, dx),
+           "wgrad": lambda: F._wgrad_b3(geom.wgrad_desc(), hs, gys, dw)}
     res = {}
     for name, fn in fns.items():
         fn(); torch.cuda.synchronize()
