@@ -603,6 +603,30 @@ int sp_saliency_metrics(const double* sal, const double* fix, const double* jitt
                         void* scratch, double* auc, double* nss, double* kld, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Fixation and density maps from scanpaths (csrc/fixmaps.hip): the producers of sp_saliency_metrics' inputs.  float64 throughout.
+ * ---------------------------------------------------------------------------------------------- */
+/* Rasterise K scanpaths into G maps [G][H][W].  fix [total][ncol >= 2] rows (x, y[, duration]); scanpath k is the count[k] rows from
+ * row start[k] on (any length) and lands in map group[k] (a group outside [0, G) is ignored).  Pixel rule, in float64:
+ * col = floor((x * W) / frame_w), row = floor((y * H) / frame_h); a fixation with non-finite x or y, x < 0, x >= frame_w, y < 0 or
+ * y >= frame_h is dropped and counted in dropped[G]; col == W / row == H from rounding is clamped to the last pixel.  weight 0: 1 at
+ * every hit pixel, 1: hit count, 2: sum of column 2 (ncol >= 3).  Every map is written (zeros without a fixation); sums add in
+ * input order, scanpath by scanpath and fixation by fixation (np.add.at): bit-identical between calls, no float atomics. */
+int sp_fixation_maps(const double* fix, int ncol, const int64_t* start, const int* count, const int* group, int K, int G, int H, int W,
+                     double frame_w, double frame_h, int weight, double* maps, int* dropped, void* stream);
+/* scipy.ndimage.gaussian_filter of G maps [G][H][W] in three launches: axis 0, then axis 1, then the optional normalisation.
+ * wy [ry + 1], wx [rx + 1]: the half kernels w[j], j = 0..r, of scipy's normalised weights (r = 0, w = {1}: that axis is unfiltered).
+ * mode 0: constant (cval 0), 1: reflect, 2: nearest; norm 0: none, 1: each map / its sum, 2: / its max (a zero sum or max leaves the
+ * map as it is).  max(H, W) <= sp_gaussian_blur_maps_max_axis() (one strip of 32 lines of the filtered axis lives in LDS); workspace
+ * >= sp_gaussian_blur_maps_workspace(G, H, W) bytes; in may equal out.  Taps are summed from -r to +r per pixel: results do not
+ * depend on the batch a map is part of. */
+int sp_gaussian_blur_maps_max_axis(void);
+int64_t sp_gaussian_blur_maps_workspace(int G, int H, int W);
+int sp_gaussian_blur_maps(const double* in, int G, int H, int W, const double* wy, int ry, const double* wx, int rx, int mode, int norm,
+                          void* workspace, double* out, void* stream);
+/* out[n] = the number of x[n][0..P-1] > 0: the fixated-pixel counts that size sp_saliency_metrics' scratch slices */
+int sp_count_positive(const double* x, int N, int P, int* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Dataset transforms of one batch (csrc/transforms.hip): what every task's Dataset.__getitem__ does per sample before collate_func.
  * ---------------------------------------------------------------------------------------------- */
 /* transforms.Resize((H, W)) (Pillow 8-bit BILINEAR) -> ToTensor() -> Normalize(mean, std) of a ragged batch of RGB uint8 HWC images

@@ -1,0 +1,199 @@
+"""Fixation and density maps from scanpaths, on the device (csrc/fixmaps.hip): the producers of the inputs of saliency_metrics_pairs.
+
+    maps, dropped = fixation_maps(scanpaths, groups, frame_size, output_shape=None, weight="binary")   # [G,H,W] float64, [G] int32
+    dens = density_maps(maps, sigma, truncate=4.0, mode="constant", normalise=None)                    # scipy gaussian_filter per map
+    scores = scanpath_saliency(gt_scanpaths, gt_groups, pred_scanpaths, pred_groups, frame_size, sigma)
+    # {"AUC_Judd", "NSS", "KLdiv": float64 [G], "gt_dropped", "pred_dropped": int32 [G]}, all on the device
+
+The reference has no such code (its callers rasterise with numpy and blur with scipy on the host); the pixel rule is the one of
+include/scanpaths_amd.h sp_fixation_maps, the filter is scipy.ndimage.gaussian_filter.  sigma has no default: the library does not
+pick a visual angle.  No interpolating resize of mismatched maps, no CPU path."""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ... import hip
+from ...hip import check, ptr
+
+WEIGHTS = {"binary": 0, "count": 1, "duration": 2}
+MODES = {"constant": 0, "reflect": 1, "nearest": 2}
+NORMALISE = {None: 0, "sum": 1, "max": 2}
+_FIELDS = ("start_x", "start_y", "duration")
+
+
+def _device() -> torch.device:
+    if not torch.cuda.is_available():
+        raise hip.HipError("scanpaths_amd fixation / density maps run on a HIP device only (no CPU path)")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _rows(sp) -> np.ndarray:
+    """one scanpath -> float64 [n, ncol]: a structured fixation vector (start_x, start_y, duration) or an [n, >= 2] array"""
+    a = np.asarray(sp)
+    if a.dtype.names is not None:
+        if any(f not in a.dtype.names for f in _FIELDS[:2]):
+            raise ValueError(f"structured scanpath without start_x / start_y fields: {a.dtype.names}")
+        cols = [f for f in _FIELDS if f in a.dtype.names]
+        return np.stack([np.asarray(a[f], dtype=np.float64).reshape(-1) for f in cols], 1)
+    a = a.astype(np.float64)
+    if a.size == 0:
+        return np.zeros((0, a.shape[-1] if a.ndim == 2 and a.shape[-1] >= 2 else 0))
+    if a.ndim != 2 or a.shape[1] < 2:
+        raise ValueError(f"a scanpath is an [n, >= 2] array of (x, y[, duration]) rows, got shape {a.shape}")
+    return a
+
+
+class _Upload:
+    """the concatenated fixations of a list of scanpaths on the device (ONE copy of the fixations) with their start / count / group"""
+
+    def __init__(self, scanpaths: Sequence, groups, num_groups: Optional[int], dev):
+        arrs = [_rows(s) for s in scanpaths]
+        grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
+        if len(arrs) != grp.shape[0]:
+            raise ValueError(f"{len(arrs)} scanpaths but {grp.shape[0]} groups")
+        if grp.size and grp.min() < 0:
+            raise ValueError("negative group index")
+        self.G = int(num_groups) if num_groups is not None else (int(grp.max()) + 1 if grp.size else 0)
+        if grp.size and grp.max() >= self.G:
+            raise ValueError(f"group index {int(grp.max())} with num_groups = {self.G}")
+        widths = {a.shape[1] for a in arrs if a.shape[0]}
+        if len(widths) > 1:
+            raise ValueError(f"scanpaths need the same number (>= 2) of columns, got {sorted(widths)}")
+        self.ncol = widths.pop() if widths else 2
+        self.K = len(arrs)
+        counts = np.array([a.shape[0] for a in arrs], dtype=np.int64)
+        cat = np.concatenate([a for a in arrs if a.shape[0]], 0) if counts.sum() else np.zeros((1, self.ncol))
+        self.fix = torch.from_numpy(np.ascontiguousarray(cat)).to(dev)
+        self.start = torch.from_numpy(np.cumsum(counts) - counts).to(dev)
+        self.count = torch.from_numpy(counts.astype(np.int32)).to(dev)
+        self.group = torch.from_numpy(grp.astype(np.int32)).to(dev)
+
+    def rasterise(self, frame_size, output_shape, weight: str, K: Optional[int] = None, G: Optional[int] = None):
+        """maps [G,H,W], dropped [G] of the first K scanpaths (all by default)"""
+        if weight not in WEIGHTS:
+            raise ValueError(f"weight {weight!r}: one of {sorted(WEIGHTS)}")
+        if weight == "duration" and self.ncol < 3:
+            raise ValueError("weight='duration' needs a third (duration) column")
+        fh, fw = (float(v) for v in frame_size)
+        H, W = (int(v) for v in (output_shape if output_shape is not None else frame_size))
+        if not (fh > 0 and fw > 0 and np.isfinite(fh) and np.isfinite(fw)) or H < 1 or W < 1:
+            raise ValueError(f"frame_size {tuple(frame_size)} / output_shape {(H, W)}: positive sizes are required")
+        K = self.K if K is None else K
+        G = self.G if G is None else G
+        dev = self.fix.device
+        maps = torch.empty((G, H, W), dtype=torch.float64, device=dev)
+        dropped = torch.empty(G, dtype=torch.int32, device=dev)
+        if G:
+            check(hip.lib().sp_fixation_maps(ptr(self.fix), self.ncol, ptr(self.start), ptr(self.count), ptr(self.group), K, G, H, W, fw,
+                                             fh, WEIGHTS[weight], ptr(maps), ptr(dropped), hip.stream()), "sp_fixation_maps")
+        return maps, dropped
+
+
+def fixation_maps(scanpaths: Sequence, groups, frame_size, output_shape=None, weight: str = "binary", num_groups: Optional[int] = None
+                  ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scanpaths: list of [n, >= 2] arrays (x, y[, duration]) or structured fixation vectors (start_x, start_y, duration), of any
+    length; groups[k]: the map of scanpath k; frame_size = (height, width) of the coordinate frame; output_shape (H, W) defaults to
+    the frame; weight "binary" / "count" / "duration"; num_groups: the number of maps (default max(groups) + 1; a group without a
+    scanpath gives a zero map).  Returns (maps [G,H,W] float64, dropped [G] int32: fixations outside the frame or non-finite), on the
+    device.  Pixel: col = floor(x * W / frame_w), row = floor(y * H / frame_h); duration sums add in input order (np.add.at)."""
+    return _Upload(scanpaths, groups, num_groups, _device()).rasterise(frame_size, output_shape, weight)
+
+
+def gaussian_weights(sigma: float, truncate: float = 4.0) -> np.ndarray:
+    """scipy.ndimage's 1-D Gaussian kernel (_gaussian_kernel1d, order 0), [2 r + 1] with r = int(truncate * sigma + 0.5), bit for bit"""
+    sd = float(sigma)
+    radius = int(float(truncate) * sd + 0.5)
+    if radius < 0:
+        raise ValueError("negative radius")
+    sigma2 = sd * sd
+    x = np.arange(-radius, radius + 1)
+    phi_x = np.exp(-0.5 / sigma2 * x ** 2)
+    return phi_x / phi_x.sum()
+
+
+def _half_kernel(sigma: float, truncate: float) -> np.ndarray:
+    if sigma <= 1e-15:                    # scipy leaves such an axis unfiltered
+        return np.ones(1)
+    w = gaussian_weights(sigma, truncate)
+    return np.ascontiguousarray(w[len(w) // 2:])
+
+
+def density_maps(maps, sigma, truncate: float = 4.0, mode: str = "constant", normalise: Optional[str] = None) -> torch.Tensor:
+    """scipy.ndimage.gaussian_filter(map, sigma, mode=mode, cval=0, truncate=truncate) of every map of [G,H,W] (device or host; computed
+    in float64), axis 0 first; sigma: a number or (sigma_y, sigma_x), 0 leaves that axis unfiltered; mode "constant", "reflect" or
+    "nearest"; normalise None, "sum" or "max" divides each map by its sum / max (a zero map stays zero).  Returns a device tensor."""
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: one of {sorted(MODES)}")
+    if normalise not in NORMALISE:
+        raise ValueError(f"normalise {normalise!r}: None, 'sum' or 'max'")
+    sg = np.asarray(sigma, dtype=np.float64).reshape(-1)
+    if sg.size == 1:
+        sg = np.repeat(sg, 2)
+    if sg.size != 2 or not np.isfinite(sg).all() or (sg < 0).any():
+        raise ValueError(f"sigma {sigma!r}: a non-negative number or (sigma_y, sigma_x)")
+    if not (np.isfinite(truncate) and truncate >= 0):
+        raise ValueError(f"truncate {truncate!r}")
+    m = maps if isinstance(maps, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(maps, dtype=np.float64)))
+    if m.ndim != 3:
+        raise ValueError(f"maps {tuple(m.shape)}: [G,H,W] is required")
+    dev = _device()
+    L = hip.lib()
+    m = m.to(device=dev, dtype=torch.float64).contiguous()
+    G, H, W = m.shape
+    if max(H, W) > L.sp_gaussian_blur_maps_max_axis():
+        raise ValueError(f"maps of {H}x{W}: the filter holds at most {L.sp_gaussian_blur_maps_max_axis()} pixels per axis")
+    out = torch.empty_like(m)
+    if G == 0:
+        return out
+    hy, hx = _half_kernel(sg[0], truncate), _half_kernel(sg[1], truncate)
+    wts = torch.from_numpy(np.concatenate([hy, hx])).to(dev)
+    ws = torch.empty(int(L.sp_gaussian_blur_maps_workspace(G, H, W)), dtype=torch.uint8, device=dev)      # the axis-0 result
+    check(L.sp_gaussian_blur_maps(ptr(m), G, H, W, ptr(wts), len(hy) - 1, wts.data_ptr() + 8 * len(hy), len(hx) - 1, MODES[mode],
+                                  NORMALISE[normalise], ptr(ws), ptr(out), hip.stream()), "sp_gaussian_blur_maps")
+    return out
+
+
+def scanpath_saliency(gt_scanpaths: Sequence, gt_groups, pred_scanpaths: Sequence, pred_groups, frame_size, sigma, output_shape=None,
+                      mode: str = "constant", pred_weight: str = "count", truncate: float = 4.0, num_groups: Optional[int] = None
+                      ) -> Dict[str, torch.Tensor]:
+    """How well the predicted scanpaths of each group predict where people looked.  Per group g (num_groups maps, default
+    max(gt_groups) + 1): predicted density = the blur of the pred_weight map of all predicted scanpaths of g; then
+      AUC_Judd = AUC_Judd(predicted density, binary human fixation map, jitter=False)   (Gaussian maps must not be jittered)
+      NSS      = NSS(predicted density, binary human fixation map)
+      KLdiv    = KLdiv(saliencyMap=predicted density, fixationMap=the same blur of the human count map)
+    as float64 device tensors [G], with gt_dropped / pred_dropped int32 [G].  A group without human fixations or without
+    predictions scores as the metric functions do on its empty map (NaN for AUC_Judd and NSS): nothing is left out.
+    One upload of all fixations, 2 + 2 + 1 + 2 launches and one [G] copy of fixated-pixel counts, whatever G."""
+    from . import visual_attention_metrics as M
+    dev = _device()
+    gt_groups = np.asarray(list(gt_groups), dtype=np.int64).reshape(-1)
+    pred_groups = np.asarray(list(pred_groups), dtype=np.int64).reshape(-1)
+    G = int(num_groups) if num_groups is not None else (int(gt_groups.max()) + 1 if gt_groups.size else 0)
+    for name, grp in (("gt_groups", gt_groups), ("pred_groups", pred_groups)):
+        if grp.size and (grp.min() < 0 or grp.max() >= G):
+            raise ValueError(f"{name}: group index outside [0, {G})")
+    if G == 0:
+        z = torch.empty(0, dtype=torch.float64, device=dev)
+        zi = torch.empty(0, dtype=torch.int32, device=dev)
+        return {"AUC_Judd": z, "NSS": z.clone(), "KLdiv": z.clone(), "gt_dropped": zi, "pred_dropped": zi.clone()}
+    if pred_weight not in ("count", "duration", "binary"):
+        raise ValueError(f"pred_weight {pred_weight!r}")
+    # human scanpaths first, predicted ones shifted by G: one upload, maps [0, G) human and [G, 2G) predicted
+    up = _Upload(list(gt_scanpaths) + list(pred_scanpaths), np.concatenate([gt_groups, pred_groups + G]), 2 * G, dev)
+    if pred_weight == "count":
+        counts, dropped = up.rasterise(frame_size, output_shape, "count")
+    else:
+        # the human density is always the blur of the COUNT map: rasterise the two halves with their own weights
+        counts, dropped = up.rasterise(frame_size, output_shape, pred_weight)
+        gt_counts, _ = up.rasterise(frame_size, output_shape, "count", K=len(gt_groups), G=G)
+        counts[:G] = gt_counts
+    binary, _ = up.rasterise(frame_size, output_shape, "binary", K=len(gt_groups), G=G)
+    dens = density_maps(counts, sigma, truncate=truncate, mode=mode)
+    P = dens.shape[1] * dens.shape[2]
+    pred, human = dens[G:].reshape(G, P), dens[:G].reshape(G, P)
+    auc, nss, _ = M._saliency_metrics_device(pred, binary.reshape(G, P))
+    _, _, kld = M._saliency_metrics_device(pred, human, want_auc=False)
+    return {"AUC_Judd": auc, "NSS": nss, "KLdiv": kld, "gt_dropped": dropped[:G], "pred_dropped": dropped[G:]}

@@ -6,6 +6,9 @@ csrc/scanmetrics.hip, plus the batched form the validation loops need:
     sed, stde = sed_stde_pairs(scanpaths, pairs, stimulus.shape)                                  # device tensors [npairs]
 
     auc, nss, kld = saliency_metrics_pairs(saliency_maps, fixation_maps)                        # device tensors [N]
+    maps, dropped = fixation_maps(scanpaths, groups, frame_size)                                 # saliency_maps.py, re-exported here
+    dens = density_maps(maps, sigma=10)
+    scores = scanpath_saliency(gt_scanpaths, gt_groups, pred_scanpaths, pred_groups, frame_size, sigma=10)
 
 SED is bit-exact; STDE follows numpy's float64 evaluation order (differences only in the last bit of exp()).  No CPU path."""
 from __future__ import annotations
@@ -76,36 +79,60 @@ def saliency_metrics_pairs(saliency_maps, fixation_maps, jitter=None) -> Tuple[t
     reference's AUC_Judd(s, f, jitter=False) / NSS(s, f) / KLdiv(s, f) per map, or AUC_Judd's jittered score when that map's jitter
     is given.  NaN where the reference returns NaN (no fixation; a constant map under AUC-Judd)."""
     dev = _device()
-    L = hip.lib()
-    S = np.asarray(saliency_maps.cpu() if isinstance(saliency_maps, torch.Tensor) else saliency_maps, dtype=np.float64)
-    F = np.asarray(fixation_maps.cpu() if isinstance(fixation_maps, torch.Tensor) else fixation_maps, dtype=np.float64)
+    on_device = all(isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float64 for m in (saliency_maps, fixation_maps))
+    if on_device:                                                  # the maps stay where they are (saliency_maps.py produces them there)
+        S, F = saliency_maps, fixation_maps
+    else:
+        S = np.asarray(saliency_maps.cpu() if isinstance(saliency_maps, torch.Tensor) else saliency_maps, dtype=np.float64)
+        F = np.asarray(fixation_maps.cpu() if isinstance(fixation_maps, torch.Tensor) else fixation_maps, dtype=np.float64)
     if S.ndim != 3 or S.shape != F.shape:
-        raise ValueError(f"saliency maps {S.shape} and fixation maps {F.shape}: the same [N,H,W] shape is required (no resizing)")
+        raise ValueError(f"saliency maps {tuple(S.shape)} and fixation maps {tuple(F.shape)}: the same [N,H,W] shape is required (no "
+                         "resizing)")
     N, P = S.shape[0], S.shape[1] * S.shape[2]
-    out = tuple(torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
     if N == 0:
-        return out
+        return tuple(torch.empty(0, dtype=torch.float64, device=dev) for _ in range(3))
+    if on_device:
+        s_d, f_d = S.contiguous().reshape(N, P), F.contiguous().reshape(N, P)
+    else:
+        s_d = torch.from_numpy(np.ascontiguousarray(S.reshape(N, P))).to(dev)
+        f_d = torch.from_numpy(np.ascontiguousarray(F.reshape(N, P))).to(dev)
+    j_d = None
+    if jitter is not None:
+        J = jitter if isinstance(jitter, torch.Tensor) else np.asarray(jitter, dtype=np.float64)
+        if tuple(J.shape) != tuple(S.shape):
+            raise ValueError(f"jitter {tuple(J.shape)} must have the saliency maps' shape {tuple(S.shape)}")
+        if isinstance(J, torch.Tensor):
+            j_d = J.to(device=dev, dtype=torch.float64).contiguous().reshape(N, P)
+        else:
+            j_d = torch.from_numpy(np.ascontiguousarray(J.reshape(N, P))).to(dev)
+    return _saliency_metrics_device(s_d, f_d, j_d, None if on_device else (F.reshape(N, -1) > 0).sum(1))
+
+
+def _saliency_metrics_device(s_d, f_d, j_d=None, nfix=None, want_auc=True):
+    """sp_saliency_metrics on contiguous float64 device rows [N,P].  nfix: the fixated-pixel counts when the host has them, else they
+    come from one device reduction and one [N] copy.  want_auc False gives no map a scratch slice: a map with more fixated pixels than
+    the LDS holds then reports NaN for AUC-Judd without sorting them (NSS and KLdiv are unaffected)."""
+    L = hip.lib()
+    dev = s_d.device
+    N, P = s_d.shape
+    out = tuple(torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
     # AUC-Judd keeps the sorted fixated values in LDS up to sp_saliency_metrics_lds_fixations(); a map with more gets a slice of a
     # global scratch buffer: 8 * next_pow2(Nfix) + 4 * Nfix bytes (rounded up to 8)
-    nfix = (F.reshape(N, -1) > 0).sum(1)
-    lds = L.sp_saliency_metrics_lds_fixations()
     need = np.zeros(N, dtype=np.int64)
-    big = nfix > lds
-    if big.any():
-        n2 = 2 ** np.ceil(np.log2(np.maximum(nfix[big], 1))).astype(np.int64)
-        need[big] = 8 * n2 + (4 * nfix[big] + 7) // 8 * 8
+    if want_auc:
+        if nfix is None:
+            cnt = torch.empty(N, dtype=torch.int32, device=dev)
+            check(L.sp_count_positive(ptr(f_d), N, P, ptr(cnt), hip.stream()), "sp_count_positive")
+            nfix = cnt.cpu().numpy().astype(np.int64)
+        lds = L.sp_saliency_metrics_lds_fixations()
+        big = nfix > lds
+        if big.any():
+            n2 = 2 ** np.ceil(np.log2(np.maximum(nfix[big], 1))).astype(np.int64)
+            need[big] = 8 * n2 + (4 * nfix[big] + 7) // 8 * 8
     off = np.zeros(N + 1, dtype=np.int64)
     off[1:] = np.cumsum(need)
     off_d = torch.from_numpy(off).to(dev)
     scratch = torch.empty(int(off[-1]), dtype=torch.uint8, device=dev) if off[-1] else None
-    s_d = torch.from_numpy(np.ascontiguousarray(S.reshape(N, P))).to(dev)
-    f_d = torch.from_numpy(np.ascontiguousarray(F.reshape(N, P))).to(dev)
-    j_d = None
-    if jitter is not None:
-        J = np.asarray(jitter, dtype=np.float64)
-        if J.shape != S.shape:
-            raise ValueError(f"jitter {J.shape} must have the saliency maps' shape {S.shape}")
-        j_d = torch.from_numpy(np.ascontiguousarray(J.reshape(N, P))).to(dev)
     check(L.sp_saliency_metrics(ptr(s_d), ptr(f_d), ptr(j_d), N, P, ptr(off_d), ptr(scratch), ptr(out[0]), ptr(out[1]), ptr(out[2]),
                                 hip.stream()), "sp_saliency_metrics")
     return out
@@ -229,3 +256,6 @@ def scaled_time_delay_embedding_distance(human_scanpath, simulated_scanpath, ima
         return None
     tde, _ = tde_pairs([human_scanpath, simulated_scanpath], [(0, 1)], k=0, max_dim=float(max(np.shape(image))))
     return float(tde.item())
+
+
+from .saliency_maps import density_maps, fixation_maps, gaussian_weights, scanpath_saliency  # noqa: E402,F401  (producers of the maps above)

@@ -452,3 +452,47 @@ def pairs_eval_scanmatch(gt_fix_vectors, predict_fix_vectors, ScanMatchwithDurat
             coll = coll[np.isnan(coll.sum(axis=1)) == False]   # noqa: E712
         out.append(np.sum(coll, axis=0) / len(gt_fix_vectors[index]) if coll.shape[0] != 0 else np.array([np.nan] * 2))
     return np.array(out)
+
+
+# ---- saliency scoring of sampled scanpaths (evaltools/saliency_maps.py, csrc/fixmaps.hip) ------------------------------------------------
+def predict_results_fix_vectors(predict_results):
+    """the ``predict_results`` records of inference.run_test_loop (qid, X, Y in the 320x240 sampling frame, T in ms) ->
+    (fixation vectors [n, 3] with the duration in seconds, keys = the records' qid): the arguments saliency_evaluation takes"""
+    fvs, keys = [], []
+    for r in predict_results:
+        x, y, t = (np.asarray(r[k], dtype=np.float64).reshape(-1) for k in ("X", "Y", "T"))
+        if not (len(x) == len(y) == len(t)):
+            raise ValueError(f"record of qid {r['qid']!r}: X, Y and T differ in length")
+        fvs.append(np.stack([x, y, t / 1000.0], 1))
+        keys.append(r["qid"])
+    return fvs, keys
+
+
+def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, frame_size=(240, 320), *, sigma, **kw):
+    """Saliency metrics of predicted scanpaths against human ones, one map set per distinct key (a question id, an image name: any
+    hashable), in first-appearance order of gt_keys.  gt_fix_vectors[i] belongs to gt_keys[i], predict_fix_vectors[j] to
+    predict_keys[j]; a predicted key that gt_keys does not hold raises ValueError.  sigma (pixels of the output map) is required;
+    **kw goes to evaltools.saliency_maps.scanpath_saliency (output_shape, mode, pred_weight, truncate).
+    Returns (means, per_key): means[metric] = nanmean over the keys and means[metric + "_nan"] = how many keys scored NaN, for
+    AUC_Judd, NSS and KLdiv; per_key = {"keys": [...], metric: float64 [G] numpy arrays, "gt_dropped" / "pred_dropped": int [G]}."""
+    from .evaltools.saliency_maps import scanpath_saliency
+    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
+    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index = {}
+    for k in gt_keys:
+        index.setdefault(k, len(index))
+    unknown = [k for k in predict_keys if k not in index]
+    if unknown:
+        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    res = scanpath_saliency(gt_fix_vectors, [index[k] for k in gt_keys], predict_fix_vectors, [index[k] for k in predict_keys],
+                            frame_size, sigma, num_groups=len(index), **kw)
+    per_key = {"keys": list(index)}
+    per_key.update({k: v.cpu().numpy() for k, v in res.items()})
+    means = {}
+    for m in ("AUC_Judd", "NSS", "KLdiv"):
+        v = per_key[m]
+        nan = np.isnan(v)
+        means[m] = float(v[~nan].mean()) if (~nan).any() else float("nan")
+        means[m + "_nan"] = int(nan.sum())
+    return means, per_key
