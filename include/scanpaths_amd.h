@@ -601,6 +601,27 @@ int sp_rowscale_idx(const float* coef, const float* g, const int* idx, int R, in
 int sp_saliency_metrics_lds_fixations(void);
 int sp_saliency_metrics(const double* sal, const double* fix, const double* jitter, int N, int P, const int64_t* scratch_off,
                         void* scratch, double* auc, double* nss, double* kld, void* stream);
+/* The pool of shuffled-AUC negatives.  fix [G][P] float64 fixation maps, cls [G]: the image each map was recorded on, a HOST array
+ * (read and checked before anything is launched: a value outside [0, E) is SP_EINVAL); cls_dev [G]: device words the call fills with
+ * cls for sp_saliency_scores.  cnt [E][P] = the number of maps g with cls[g] = e and fix[g][p] > 0, tot [P] = the sum of cnt over e;
+ * both int32, every entry written.  One thread owns a pixel: no atomics. */
+int sp_fixation_pool_counts(const double* fix, const int* cls, int G, int P, int E, int* cls_dev, int* cnt, int* tot, void* stream);
+/* Shuffled AUC, CC, SIM and information gain of N maps of P pixels, float64, one launch (Bylinskii et al. 2019, on sum-normalised
+ * maps, no min-max step).  sal: predicted density S; fix: fixation map F (fixated where > 0); dens: human density D; base: baseline Bm.
+ *   sAUC: exact weighted Mann-Whitney AUC of S at the n fixated pixels against the pool weights w[p] (integers, w <= 0: not in the
+ *     pool): sum over fixated i of (2 sum_p w[p] [S[p] < S[i]] + sum_p w[p] [S[p] == S[i]]), in int64, / (2 n W), W = sum w.
+ *     w of map m = pool[m * pool_stride + p] - (cnt ? cnt[cls[m]][p] : 0): pool = tot, pool_stride = 0 with sp_fixation_pool_counts'
+ *     cnt / cls_dev (E images), or pool = one weight map per map (pool_stride = P) with cnt = cls = NULL.
+ *     NaN if n = 0, W = 0, S holds a NaN or cls[m] is outside [0, E).  Scratch as for sp_saliency_metrics: a map with more than
+ *     sp_saliency_metrics_lds_fixations() fixated pixels sorts them in scratch + scratch_off[m], >= 8 * next_pow2(n) bytes, else NaN.
+ *   CC = Pearson correlation of S and D (NaN if a centred sum of squares is 0 or not finite); SIM = sum min(S / sum S, D / sum D)
+ *   (NaN if a sum is <= 0 or not finite); IG = mean over fixated i of log2(eps + p[i]) - log2(eps + q[i]), p = (1 - uniform_mix) S /
+ *   sum S + uniform_mix / P, q the same of Bm, eps = 2^-52 (NaN if n = 0 or a sum is <= 0 or not finite); 0 <= uniform_mix <= 1.
+ * A metric whose output or one of whose inputs is NULL is skipped (sAUC: fix, pool; CC, SIM: dens; IG: fix, base); SP_ENULL if that
+ * skips all four, if sal is NULL, or if exactly one of cnt / cls is given. */
+int sp_saliency_scores(const double* sal, const double* fix, const double* dens, const double* base, const int* pool, int64_t pool_stride,
+                       const int* cnt, const int* cls, int E, int N, int P, double uniform_mix, const int64_t* scratch_off, void* scratch,
+                       double* sauc, double* cc, double* sim, double* ig, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Fixation and density maps from scanpaths (csrc/fixmaps.hip): the producers of sp_saliency_metrics' inputs.  float64 throughout.

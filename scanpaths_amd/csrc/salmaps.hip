@@ -12,7 +12,8 @@
 //     argmin stay in the workgroup, so the gradient goes to the chosen step in the same launch); 3 + (objects) passes per step map,
 //     4 more per chosen step.
 //   * DurationSmoothL1Loss / MLPRayleighDistribution / CC_MatchLoss: one workgroup over all elements (mask sum, then value+gradient).
-// Metrics (fp64, one workgroup per map, one launch for a batch): see saliency_metrics_kernel.
+// Metrics (fp64, one workgroup per map, one launch for a batch): see saliency_metrics_kernel; shuffled AUC, CC, SIM and information
+// gain (Bylinskii et al. 2019; no counterpart in the reference): pool_counts_kernel and saliency_scores_kernel.
 #include "common.h"
 
 namespace {
@@ -678,6 +679,165 @@ __global__ __launch_bounds__(NT) void saliency_metrics_kernel(const double* __re
     if (threadIdx.x == 0) auc[n] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The pool of shuffled-AUC negatives: cnt[e][p] = #(maps g of image e with F_g[p] > 0), tot[p] = sum_e cnt[e][p].  One thread owns
+// pixel p for every map and image (its loads are coalesced across the wave), so the counts need neither atomics nor a zeroed buffer.
+// Maps are read eight at a time so that the loads are in flight together and not behind the count updates.
+__global__ __launch_bounds__(NT) void pool_counts_kernel(const double* __restrict__ fix, const int* __restrict__ cls, int G, int P, int E,
+                                                         int* __restrict__ cnt, int* __restrict__ tot) {
+    const int p = blockIdx.x * NT + threadIdx.x;
+    if (p >= P) return;
+    for (int e = 0; e < E; ++e) cnt[(int64_t)e * P + p] = 0;
+    int t = 0;
+    for (int g0 = 0; g0 < G; g0 += 8) {
+        double f[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) f[k] = g0 + k < G ? fix[(int64_t)(g0 + k) * P + p] : 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (f[k] > 0.0) {
+                const int c = cls[g0 + k];
+                if (c >= 0 && c < E) {            // the host checked; a stray value must not write outside cnt
+                    cnt[(int64_t)c * P + p] += 1;
+                    ++t;
+                }
+            }
+    }
+    tot[p] = t;
+}
+
+// Shuffled AUC, CC, SIM and information gain, float64, one 256-thread workgroup per map (include/scanpaths_amd.h sp_saliency_scores).
+//   pass 1: the sums of S, D, Bm, the fixated-pixel count n, the pool weight W (int64) and the NaN count of S;
+//   pass 2: the centred products of CC, the min terms of SIM and, at fixated pixels, the log2 terms of IG;
+//   sAUC:   the fixated values sorted in descending order (bitonic, in LDS up to SM_LDS_FIX, else in the map's scratch slice).  A pool
+//     pixel of value v and weight w then finds by two binary searches how many fixated values lie above v (a) and at or above v (b)
+//     and adds w * (a + b) to its thread's int64: summed over the pool this is sum_i (2 below_i + equal_i) -- the histogram and prefix
+//     sum of AUC-Judd collapse, since sum_i prefix[i] = sum_k hist[k] (n - k).  Integer sums: the result does not depend on order.
+// Double sums: per-thread strided, then the fixed block tree (as above).
+constexpr double IG_EPS = 2.220446049250313e-16;
+__global__ __launch_bounds__(NT) void saliency_scores_kernel(const double* __restrict__ sal, const double* __restrict__ fix,
+                                                             const double* __restrict__ dens, const double* __restrict__ base,
+                                                             const int* __restrict__ pool, int64_t pool_stride,
+                                                             const int* __restrict__ cnt, const int* __restrict__ cls, int E, int P,
+                                                             double alpha, const int64_t* __restrict__ scratch_off, char* scratch,
+                                                             double* __restrict__ sauc, double* __restrict__ cc,
+                                                             double* __restrict__ sim, double* __restrict__ ig) {
+    __shared__ double sh[4];
+    __shared__ long long shl[4];
+    __shared__ double thr_lds[SM_LDS_FIX];
+    __shared__ int fill;
+    const int n = blockIdx.x;
+    const double* S = sal + (int64_t)n * P;
+    const double* F = fix ? fix + (int64_t)n * P : nullptr;
+    const double* D = dens ? dens + (int64_t)n * P : nullptr;
+    const double* B = base ? base + (int64_t)n * P : nullptr;
+    const bool do_auc = sauc && F && pool, do_cc = cc && D, do_sim = sim && D, do_ig = ig && F && B;
+    const int* T = pool ? pool + (int64_t)n * pool_stride : nullptr;
+    const int* C = nullptr;
+    bool cls_ok = true;
+    if (cnt) {
+        const int c = cls[n];
+        cls_ok = c >= 0 && c < E;
+        if (cls_ok) C = cnt + (int64_t)c * P;
+    }
+    auto wt = [&](int i) { return C ? T[i] - C[i] : T[i]; };
+    // pass 1
+    double sS = 0.0, sD = 0.0, sB = 0.0;
+    long long nfix = 0, W = 0, nanS = 0;
+    for (int i = threadIdx.x; i < P; i += NT) {
+        const double s = S[i];
+        sS += s;
+        nanS += isnan(s);
+        if (D) sD += D[i];
+        if (B) sB += B[i];
+        if (F) nfix += F[i] > 0.0;
+        if (do_auc && cls_ok) {
+            const int w = wt(i);
+            W += w > 0 ? w : 0;
+        }
+    }
+    sS = block_sum_d(sS, sh);
+    sD = block_sum_d(sD, sh);
+    sB = block_sum_d(sB, sh);
+    nfix = block_sum_ll(nfix, shl);
+    W = block_sum_ll(W, shl);
+    nanS = block_sum_ll(nanS, shl);
+    // pass 2: CC, SIM, IG
+    if (do_cc || do_sim || do_ig) {
+        const double mS = sS / P, mD = sD / P, ka = 1.0 - alpha, ua = alpha / P;
+        double cxy = 0.0, cxx = 0.0, cyy = 0.0, smin = 0.0, gain = 0.0;
+        for (int i = threadIdx.x; i < P; i += NT) {
+            const double s = S[i];
+            if (D) {
+                const double d = D[i], a = s - mS, b = d - mD;
+                cxy += a * b;
+                cxx += a * a;
+                cyy += b * b;
+                smin += fmin(s / sS, d / sD);
+            }
+            if (do_ig && F[i] > 0.0) gain += log2(IG_EPS + (ka * s / sS + ua)) - log2(IG_EPS + (ka * B[i] / sB + ua));
+        }
+        cxy = block_sum_d(cxy, sh);
+        cxx = block_sum_d(cxx, sh);
+        cyy = block_sum_d(cyy, sh);
+        smin = block_sum_d(smin, sh);
+        gain = block_sum_d(gain, sh);
+        if (threadIdx.x == 0) {
+            const bool okS = sS > 0.0 && isfinite(sS), okD = sD > 0.0 && isfinite(sD), okB = sB > 0.0 && isfinite(sB);
+            if (do_cc) cc[n] = (cxx > 0.0 && cyy > 0.0 && isfinite(cxx) && isfinite(cyy)) ? cxy / sqrt(cxx * cyy) : NAN;
+            if (do_sim) sim[n] = (okS && okD) ? smin : NAN;
+            if (do_ig) ig[n] = (nfix > 0 && okS && okB) ? gain / (double)nfix : NAN;
+        }
+    }
+    if (!do_auc) return;
+    // ---- sAUC ----
+    const int nf = (int)nfix;
+    int n2 = 1;
+    while (n2 < nf) n2 <<= 1;
+    double* thr = thr_lds;
+    bool ok = cls_ok && nf > 0 && W > 0 && nanS == 0;
+    if (ok && nf > SM_LDS_FIX) {
+        if (!scratch || scratch_off[n] < 0 || scratch_off[n + 1] - scratch_off[n] < (int64_t)n2 * 8) ok = false;      // host sized it otherwise
+        else thr = (double*)(scratch + scratch_off[n]);
+    }
+    if (!ok) {                                   // uniform over the workgroup: every term comes from a block sum
+        if (threadIdx.x == 0) sauc[n] = NAN;
+        return;
+    }
+    if (threadIdx.x == 0) fill = 0;
+    for (int i = threadIdx.x; i < n2; i += NT) thr[i] = -INFINITY;
+    __syncthreads();
+    for (int i = threadIdx.x; i < P; i += NT)
+        if (F[i] > 0.0) {
+            const int k = atomicAdd(&fill, 1);
+            if (k < nf) thr[k] = S[i];
+        }
+    __syncthreads();
+    if (nf > 1) bitonic_desc(thr, n2);
+    long long num = 0;
+    for (int i = threadIdx.x; i < P; i += NT) {
+        const int w = wt(i);
+        if (w <= 0) continue;
+        const double v = S[i];
+        int lo = 0, hi = nf;                     // a = #(thr > v) = the first k with thr[k] <= v
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (thr[mid] <= v) hi = mid;
+            else lo = mid + 1;
+        }
+        const int a = lo;
+        hi = nf;                                 // b = #(thr >= v) = the first k >= a with thr[k] < v
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (thr[mid] < v) hi = mid;
+            else lo = mid + 1;
+        }
+        num += (long long)w * (a + lo);
+    }
+    num = block_sum_ll(num, shl);
+    if (threadIdx.x == 0) sauc[n] = (double)num / (double)(2LL * nf * W);
+}
+
 }  // namespace
 
 extern "C" int sp_smooth_l1_loss(const float* x, const float* gt, const float* mask, int64_t n, float* out, float* coef, void* stream) {
@@ -782,6 +942,35 @@ extern "C" int sp_saliency_metrics(const double* sal, const double* fix, const d
     if (N < 1 || P < 1) return SP_EINVAL;
     hipLaunchKernelGGL(saliency_metrics_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, sal, fix, jitter, P, scratch_off,
                        (char*)scratch, auc, nss, kld);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_fixation_pool_counts(const double* fix, const int* cls, int G, int P, int E, int* cls_dev, int* cnt, int* tot,
+                                       void* stream) {
+    if (!fix || !cls || !cls_dev || !cnt || !tot) return SP_ENULL;
+    if (G < 1 || P < 1 || E < 1) return SP_EINVAL;
+    for (int g = 0; g < G; ++g)
+        if (cls[g] < 0 || cls[g] >= E) return SP_EINVAL;
+    const hipError_t e = hipMemcpyAsync(cls_dev, cls, (size_t)G * sizeof(int), hipMemcpyHostToDevice, (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(pool_counts_kernel, dim3((unsigned)sp_cdiv(P, NT)), dim3(NT), 0, (hipStream_t)stream, fix, cls_dev, G, P, E, cnt,
+                       tot);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+extern "C" int sp_saliency_scores(const double* sal, const double* fix, const double* dens, const double* base, const int* pool,
+                                  int64_t pool_stride, const int* cnt, const int* cls, int E, int N, int P, double uniform_mix,
+                                  const int64_t* scratch_off, void* scratch, double* sauc, double* cc, double* sim, double* ig,
+                                  void* stream) {
+    const bool do_auc = sauc && fix && pool, do_ig = ig && fix && base;
+    if (!sal || (!cnt != !cls) || !(do_auc || do_ig || (dens && (cc || sim))) || (do_auc && !scratch_off)) return SP_ENULL;
+    if (N < 1 || P < 1) return SP_EINVAL;
+    if (do_auc && ((pool_stride != 0 && pool_stride != P) || (cnt && E < 1))) return SP_EINVAL;
+    if (do_ig && !(uniform_mix >= 0.0 && uniform_mix <= 1.0)) return SP_EINVAL;
+    hipLaunchKernelGGL(saliency_scores_kernel, dim3(N), dim3(NT), 0, (hipStream_t)stream, sal, fix, dens, base, pool, pool_stride, cnt,
+                       cls, E, P, uniform_mix, scratch_off, (char*)scratch, sauc, cc, sim, ig);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

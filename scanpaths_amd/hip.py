@@ -175,6 +175,8 @@ SIGNATURES = {
     "sp_rowscale_idx": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "sp_saliency_metrics_lds_fixations": (_I, []),
     "sp_saliency_metrics": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "sp_fixation_pool_counts": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "sp_saliency_scores": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
     "sp_fixation_maps": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _P]),
     "sp_gaussian_blur_maps_max_axis": (_I, []),
     "sp_gaussian_blur_maps_workspace": (_L, [_I, _I, _I]),

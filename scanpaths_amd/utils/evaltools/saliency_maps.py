@@ -4,6 +4,7 @@
     dens = density_maps(maps, sigma, truncate=4.0, mode="constant", normalise=None)                    # scipy gaussian_filter per map
     scores = scanpath_saliency(gt_scanpaths, gt_groups, pred_scanpaths, pred_groups, frame_size, sigma)
     # {"AUC_Judd", "NSS", "KLdiv": float64 [G], "gt_dropped", "pred_dropped": int32 [G]}, all on the device
+    scores = scanpath_saliency(..., extra_metrics=("sAUC", "CC", "SIM", "IG"), image_groups=img, uniform_mix=0.01)   # + those keys
 
 The reference has no such code (its callers rasterise with numpy and blur with scipy on the host); the pixel rule is the one of
 include/scanpaths_amd.h sp_fixation_maps, the filter is scipy.ndimage.gaussian_filter.  sigma has no default: the library does not
@@ -157,8 +158,9 @@ def density_maps(maps, sigma, truncate: float = 4.0, mode: str = "constant", nor
 
 
 def scanpath_saliency(gt_scanpaths: Sequence, gt_groups, pred_scanpaths: Sequence, pred_groups, frame_size, sigma, output_shape=None,
-                      mode: str = "constant", pred_weight: str = "count", truncate: float = 4.0, num_groups: Optional[int] = None
-                      ) -> Dict[str, torch.Tensor]:
+                      mode: str = "constant", pred_weight: str = "count", truncate: float = 4.0, num_groups: Optional[int] = None, *,
+                      extra_metrics: Sequence[str] = (), image_groups=None, uniform_mix=None, baseline_sigma=None,
+                      prediction: str = "scanpaths") -> Dict[str, torch.Tensor]:
     """How well the predicted scanpaths of each group predict where people looked.  Per group g (num_groups maps, default
     max(gt_groups) + 1): predicted density = the blur of the pred_weight map of all predicted scanpaths of g; then
       AUC_Judd = AUC_Judd(predicted density, binary human fixation map, jitter=False)   (Gaussian maps must not be jittered)
@@ -166,19 +168,48 @@ def scanpath_saliency(gt_scanpaths: Sequence, gt_groups, pred_scanpaths: Sequenc
       KLdiv    = KLdiv(saliencyMap=predicted density, fixationMap=the same blur of the human count map)
     as float64 device tensors [G], with gt_dropped / pred_dropped int32 [G].  A group without human fixations or without
     predictions scores as the metric functions do on its empty map (NaN for AUC_Judd and NSS): nothing is left out.
-    One upload of all fixations, 2 + 2 + 1 + 2 launches and one [G] copy of fixated-pixel counts, whatever G."""
+    One upload of all fixations, 2 + 2 + 1 + 2 launches and one [G] copy of fixated-pixel counts, whatever G.
+
+    extra_metrics: any of "sAUC", "CC", "SIM", "IG" (visual_attention_metrics.saliency_scores_pairs; the paper's formulae on
+    sum-normalised maps, without the MATLAB benchmark code's min-max step) adds those keys and leaves the other ones bit for bit:
+      image_groups [G]: the image group g was recorded on (default: every group is its own image);
+      sAUC = the binary human map of g against the pool of pixels fixated in groups of OTHER images;
+      CC, SIM = the predicted density against the human density KLdiv uses;
+      IG = over the baseline Bm of g: the blur (baseline_sigma, default sigma) of the summed human count maps of all groups on other
+           images, one blur per image; uniform_mix is then required (no default).
+    prediction="centre_prior": the predicted density of g IS its Bm (pred_scanpaths must be empty): the floor a model has to beat.
+    Extras cost one more upload of the human fixations and 2 + 2 + 1 + 1 launches, whatever G."""
     from . import visual_attention_metrics as M
-    dev = _device()
     gt_groups = np.asarray(list(gt_groups), dtype=np.int64).reshape(-1)
     pred_groups = np.asarray(list(pred_groups), dtype=np.int64).reshape(-1)
     G = int(num_groups) if num_groups is not None else (int(gt_groups.max()) + 1 if gt_groups.size else 0)
     for name, grp in (("gt_groups", gt_groups), ("pred_groups", pred_groups)):
         if grp.size and (grp.min() < 0 or grp.max() >= G):
             raise ValueError(f"{name}: group index outside [0, {G})")
+    extra = tuple(extra_metrics)
+    unknown = [m for m in extra if m not in M.EXTRA_METRICS]
+    if unknown or len(set(extra)) != len(extra):
+        raise ValueError(f"extra_metrics {extra!r}: distinct names out of {M.EXTRA_METRICS}")
+    if prediction not in ("scanpaths", "centre_prior"):
+        raise ValueError(f"prediction {prediction!r}: 'scanpaths' or 'centre_prior'")
+    centre = prediction == "centre_prior"
+    if centre and len(pred_scanpaths):
+        raise ValueError("prediction='centre_prior' takes no predicted scanpaths")
+    alpha = M._check_mix(uniform_mix) if "IG" in extra else 0.0
+    if image_groups is None:
+        cls = np.arange(G, dtype=np.int64)
+    else:
+        cls = np.asarray(list(image_groups), dtype=np.int64).reshape(-1)
+        if cls.shape[0] != G or (G and cls.min() < 0):
+            raise ValueError(f"image_groups: one non-negative image index per group ({G}) is required, got {cls.shape[0]}")
+    E = int(cls.max()) + 1 if G else 0
+    dev = _device()
     if G == 0:
         z = torch.empty(0, dtype=torch.float64, device=dev)
         zi = torch.empty(0, dtype=torch.int32, device=dev)
-        return {"AUC_Judd": z, "NSS": z.clone(), "KLdiv": z.clone(), "gt_dropped": zi, "pred_dropped": zi.clone()}
+        out = {"AUC_Judd": z, "NSS": z.clone(), "KLdiv": z.clone(), "gt_dropped": zi, "pred_dropped": zi.clone()}
+        out.update({m: z.clone() for m in M.EXTRA_METRICS if m in extra})
+        return out
     if pred_weight not in ("count", "duration", "binary"):
         raise ValueError(f"pred_weight {pred_weight!r}")
     # human scanpaths first, predicted ones shifted by G: one upload, maps [0, G) human and [G, 2G) predicted
@@ -194,6 +225,28 @@ def scanpath_saliency(gt_scanpaths: Sequence, gt_groups, pred_scanpaths: Sequenc
     dens = density_maps(counts, sigma, truncate=truncate, mode=mode)
     P = dens.shape[1] * dens.shape[2]
     pred, human = dens[G:].reshape(G, P), dens[:G].reshape(G, P)
-    auc, nss, _ = M._saliency_metrics_device(pred, binary.reshape(G, P))
+    base = None
+    if centre or "IG" in extra:
+        # per-image human count maps [0, E) and their total [E] from one more rasterisation; the counts are integers, so the
+        # complement total - image is exact whatever the order.  One blur per image, then each group takes its image's map.
+        ub = _Upload(list(gt_scanpaths) * 2, np.concatenate([cls[gt_groups], np.full(len(gt_groups), E, dtype=np.int64)]), E + 1, dev)
+        per_image, _ = ub.rasterise(frame_size, output_shape, "count")
+        others = per_image[E:] - per_image[:E]
+        base = density_maps(others, sigma if baseline_sigma is None else baseline_sigma, truncate=truncate, mode=mode).reshape(E, P)
+        if not np.array_equal(cls, np.arange(G)):
+            base = base.index_select(0, torch.from_numpy(cls).to(dev))
+    if centre:
+        pred = base
+    fixed = binary.reshape(G, P)
+    nfix = M._count_positive(fixed)
+    auc, nss, _ = M._saliency_metrics_device(pred, fixed, nfix=nfix)
     _, _, kld = M._saliency_metrics_device(pred, human, want_auc=False)
-    return {"AUC_Judd": auc, "NSS": nss, "KLdiv": kld, "gt_dropped": dropped[:G], "pred_dropped": dropped[G:]}
+    out = {"AUC_Judd": auc, "NSS": nss, "KLdiv": kld, "gt_dropped": dropped[:G], "pred_dropped": dropped[G:]}
+    if extra:
+        cls_d = cnt = tot = None
+        if "sAUC" in extra:
+            cls_d, cnt, tot = M._pool_counts_device(fixed, cls, E)
+        need_d = "CC" in extra or "SIM" in extra
+        out.update(M._saliency_scores_device(pred, fixed if ("sAUC" in extra or "IG" in extra) else None, human if need_d else None,
+                                             base if "IG" in extra else None, tot, 0, cnt, cls_d, E, alpha, nfix, want=extra))
+    return out

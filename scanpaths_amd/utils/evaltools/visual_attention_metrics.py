@@ -9,11 +9,13 @@ csrc/scanmetrics.hip, plus the batched form the validation loops need:
     maps, dropped = fixation_maps(scanpaths, groups, frame_size)                                 # saliency_maps.py, re-exported here
     dens = density_maps(maps, sigma=10)
     scores = scanpath_saliency(gt_scanpaths, gt_groups, pred_scanpaths, pred_groups, frame_size, sigma=10)
+    extra = saliency_scores_pairs(saliency_maps, fixation_maps, density_maps, baseline_maps, image_groups=img, uniform_mix=0.01)
+    # {"sAUC", "CC", "SIM", "IG": device tensors [N]}; per map: AUC_shuffled, CC, SIM, InfoGain
 
 SED is bit-exact; STDE follows numpy's float64 evaluation order (differences only in the last bit of exp()).  No CPU path."""
 from __future__ import annotations
 
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -108,6 +110,13 @@ def saliency_metrics_pairs(saliency_maps, fixation_maps, jitter=None) -> Tuple[t
     return _saliency_metrics_device(s_d, f_d, j_d, None if on_device else (F.reshape(N, -1) > 0).sum(1))
 
 
+def _count_positive(f_d) -> np.ndarray:
+    """the fixated-pixel counts (F > 0) of device rows [N,P]: one device reduction and one [N] copy"""
+    cnt = torch.empty(f_d.shape[0], dtype=torch.int32, device=f_d.device)
+    check(hip.lib().sp_count_positive(ptr(f_d), f_d.shape[0], f_d.shape[1], ptr(cnt), hip.stream()), "sp_count_positive")
+    return cnt.cpu().numpy().astype(np.int64)
+
+
 def _saliency_metrics_device(s_d, f_d, j_d=None, nfix=None, want_auc=True):
     """sp_saliency_metrics on contiguous float64 device rows [N,P].  nfix: the fixated-pixel counts when the host has them, else they
     come from one device reduction and one [N] copy.  want_auc False gives no map a scratch slice: a map with more fixated pixels than
@@ -121,9 +130,7 @@ def _saliency_metrics_device(s_d, f_d, j_d=None, nfix=None, want_auc=True):
     need = np.zeros(N, dtype=np.int64)
     if want_auc:
         if nfix is None:
-            cnt = torch.empty(N, dtype=torch.int32, device=dev)
-            check(L.sp_count_positive(ptr(f_d), N, P, ptr(cnt), hip.stream()), "sp_count_positive")
-            nfix = cnt.cpu().numpy().astype(np.int64)
+            nfix = _count_positive(f_d)
         lds = L.sp_saliency_metrics_lds_fixations()
         big = nfix > lds
         if big.any():
@@ -187,6 +194,188 @@ def KLdiv(saliencyMap, fixationMap):
     s, f = _pair(saliencyMap, fixationMap)
     _, _, kld = saliency_metrics_pairs(s[None], f[None])
     return float(kld.item())
+
+
+# ---- shuffled AUC, CC, SIM, information gain (Bylinskii et al., TPAMI 2019; no counterpart in the reference), csrc/salmaps.hip --------
+# The paper's formulae on SUM-normalised maps.  The MATLAB benchmark code additionally min-max normalises a map before SIM and IG;
+# that is not done here, because it changes a density's likelihood.
+EXTRA_METRICS = ("sAUC", "CC", "SIM", "IG")
+
+
+def _is_device_f64(m) -> bool:
+    return isinstance(m, torch.Tensor) and m.is_cuda and m.dtype == torch.float64
+
+
+def _host_or_device(m):
+    """a float64 device tensor as it is, anything else as a float64 numpy array"""
+    if m is None or _is_device_f64(m):
+        return m
+    return np.asarray(m.cpu() if isinstance(m, torch.Tensor) else m, dtype=np.float64)
+
+
+def _rows_on_device(m, N, P, dev):
+    if m is None:
+        return None
+    if isinstance(m, torch.Tensor):
+        return m.contiguous().reshape(N, P)
+    return torch.from_numpy(np.ascontiguousarray(m.reshape(N, P))).to(dev)
+
+
+def _check_mix(uniform_mix) -> float:
+    if uniform_mix is None:
+        raise TypeError("information gain needs the keyword uniform_mix (the weight of the uniform density mixed into both maps; it has "
+                        "no default: 0 is allowed, and then every fixation on an exact zero of a density costs 52 bits)")
+    a = float(uniform_mix)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"uniform_mix {uniform_mix!r}: a weight in [0, 1]")
+    return a
+
+
+def _scratch_offsets(nfix: np.ndarray, lds: int, dev):
+    """sp_saliency_scores' scratch slices: 8 * next_pow2(Nfix) bytes for a map with more fixated pixels than the LDS holds"""
+    need = np.zeros(len(nfix), dtype=np.int64)
+    big = nfix > lds
+    if big.any():
+        need[big] = 8 * 2 ** np.ceil(np.log2(nfix[big])).astype(np.int64)
+    off = np.zeros(len(nfix) + 1, dtype=np.int64)
+    off[1:] = np.cumsum(need)
+    return torch.from_numpy(off).to(dev), (torch.empty(int(off[-1]), dtype=torch.uint8, device=dev) if off[-1] else None)
+
+
+def _pool_counts_device(f_d, cls: np.ndarray, E: int):
+    """sp_fixation_pool_counts of device rows [G,P]: (cls on the device [G], cnt [E,P], tot [P]) int32"""
+    G, P = f_d.shape
+    dev = f_d.device
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    cls_d = torch.empty(G, dtype=torch.int32, device=dev)
+    cnt = torch.empty((E, P), dtype=torch.int32, device=dev)
+    tot = torch.empty(P, dtype=torch.int32, device=dev)
+    check(hip.lib().sp_fixation_pool_counts(ptr(f_d), cls.ctypes.data, G, P, E, ptr(cls_d), ptr(cnt), ptr(tot), hip.stream()),
+          "sp_fixation_pool_counts")
+    return cls_d, cnt, tot
+
+
+def _saliency_scores_device(s_d, f_d=None, d_d=None, b_d=None, pool=None, pool_stride=0, cnt=None, cls_d=None, E=0, uniform_mix=0.0,
+                            nfix=None, want=EXTRA_METRICS) -> Dict[str, torch.Tensor]:
+    """sp_saliency_scores on contiguous float64 device rows [N,P]: ONE launch for the metrics of `want` whose inputs are given"""
+    L = hip.lib()
+    dev = s_d.device
+    N, P = s_d.shape
+    have = {"sAUC": f_d is not None and pool is not None, "CC": d_d is not None, "SIM": d_d is not None,
+            "IG": f_d is not None and b_d is not None}
+    out = {m: torch.empty(N, dtype=torch.float64, device=dev) for m in EXTRA_METRICS if m in want and have[m]}
+    if not out:
+        return out
+    off_d = scratch = None
+    if "sAUC" in out:
+        off_d, scratch = _scratch_offsets(_count_positive(f_d) if nfix is None else nfix, L.sp_saliency_metrics_lds_fixations(), dev)
+    check(L.sp_saliency_scores(ptr(s_d), ptr(f_d), ptr(d_d), ptr(b_d), ptr(pool) if "sAUC" in out else None, pool_stride, ptr(cnt),
+                               ptr(cls_d), E, N, P, float(uniform_mix), ptr(off_d), ptr(scratch), ptr(out.get("sAUC")),
+                               ptr(out.get("CC")), ptr(out.get("SIM")), ptr(out.get("IG")), hip.stream()), "sp_saliency_scores")
+    return out
+
+
+def saliency_scores_pairs(saliency_maps, fixation_maps=None, density_maps=None, baseline_maps=None, other_maps=None, image_groups=None,
+                          *, uniform_mix=None) -> Dict[str, torch.Tensor]:
+    """Shuffled AUC, CC, SIM and information gain of N maps, [N,H,W] each (numpy or torch; float64 device tensors are used in place,
+    anything else is computed in float64), from one launch per entry point whatever N.  Returns a dict of float64 device tensors [N]
+    with the metrics the inputs allow:
+      "sAUC": fixation_maps (fixated where > 0) and the negatives' pool, given either as other_maps [N,H,W] (non-negative integer
+              weights per pixel) or as image_groups [N] (the image each map was recorded on: the pool of map g is then every pixel
+              fixated in a map of ANOTHER image, weighted by the number of such maps).  The exact weighted Mann-Whitney AUC of the
+              unnormalised saliency values: ties count half, no random splits, no threshold step.
+      "CC", "SIM": density_maps.  Pearson correlation; sum of min(S / sum S, D / sum D).
+      "IG": fixation_maps and baseline_maps, and the keyword uniform_mix (required then, no default; 0 is allowed): the mean over the
+              fixated pixels of log2(eps + p) - log2(eps + q), p = (1 - uniform_mix) S / sum S + uniform_mix / (H W), q the same of the
+              baseline, eps = 2^-52.
+    These are the paper's formulae (Bylinskii et al. 2019) on sum-normalised maps; the MATLAB benchmark code's additional min-max
+    normalisation before SIM and IG is not applied, because it changes a density's likelihood.  NaN: sAUC without a fixation, with
+    an empty pool or a NaN pixel; CC of a constant map; SIM / IG with a sum <= 0 or not finite; IG without a fixation.  No resizing:
+    mismatched shapes raise."""
+    maps = {"saliency": _host_or_device(saliency_maps), "fixation": _host_or_device(fixation_maps),
+            "density": _host_or_device(density_maps), "baseline": _host_or_device(baseline_maps)}
+    S = maps["saliency"]
+    if S.ndim != 3:
+        raise ValueError(f"saliency maps {tuple(S.shape)}: [N,H,W] is required")
+    for name, m in maps.items():
+        if m is not None and tuple(m.shape) != tuple(S.shape):
+            raise ValueError(f"{name} maps {tuple(m.shape)} and saliency maps {tuple(S.shape)}: the same [N,H,W] shape is required (no "
+                             "resizing)")
+    N, P = S.shape[0], S.shape[1] * S.shape[2]
+    if other_maps is not None and image_groups is not None:
+        raise ValueError("the pool of negatives comes from other_maps or from image_groups, not both")
+    if (other_maps is not None or image_groups is not None) and maps["fixation"] is None:
+        raise ValueError("the shuffled AUC needs fixation_maps")
+    if maps["baseline"] is not None and maps["fixation"] is None:
+        raise ValueError("information gain needs fixation_maps")
+    alpha = _check_mix(uniform_mix) if maps["baseline"] is not None else 0.0
+    cls = E = other = None
+    if image_groups is not None:
+        cls = np.asarray(image_groups.cpu() if isinstance(image_groups, torch.Tensor) else list(image_groups), dtype=np.int64).reshape(-1)
+        if cls.shape[0] != N or (N and cls.min() < 0):
+            raise ValueError(f"image_groups: {N} non-negative image indices are required, got {cls.shape[0]}")
+        E = int(cls.max()) + 1 if N else 0
+    if other_maps is not None:
+        other = other_maps if isinstance(other_maps, torch.Tensor) else np.asarray(other_maps)
+        if tuple(other.shape) != tuple(S.shape):
+            raise ValueError(f"other maps {tuple(other.shape)} and saliency maps {tuple(S.shape)}: the same [N,H,W] shape is required")
+        if isinstance(other, torch.Tensor):
+            o = other.to(torch.float64)
+            bad = (~torch.isfinite(o) | (o != o.round()) | (o < 0) | (o > 2 ** 31 - 1)).any()
+        else:
+            o = other.astype(np.float64)
+            bad = not np.isfinite(o).all() or (o != np.round(o)).any() or (o < 0).any() or (o > 2 ** 31 - 1).any()
+        if bool(bad):
+            raise ValueError("other maps hold counts: non-negative integers are required")
+    if not any(m is not None for m in (other, cls, maps["density"], maps["baseline"])):
+        raise ValueError("nothing to score: give a pool (other_maps or image_groups), density_maps or baseline_maps")
+    dev = _device()
+    if N == 0:
+        empty = {"sAUC": maps["fixation"] is not None and (other is not None or cls is not None), "CC": maps["density"] is not None,
+                 "SIM": maps["density"] is not None, "IG": maps["baseline"] is not None}
+        return {m: torch.empty(0, dtype=torch.float64, device=dev) for m in EXTRA_METRICS if empty[m]}
+    s_d, f_d, d_d, b_d = (_rows_on_device(maps[k], N, P, dev) for k in ("saliency", "fixation", "density", "baseline"))
+    F = maps["fixation"]
+    nfix = None if F is None or isinstance(F, torch.Tensor) else (F.reshape(N, -1) > 0).sum(1).astype(np.int64)
+    if other is not None:
+        pool = (other if isinstance(other, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(other))).to(device=dev, dtype=torch.int32)
+        return _saliency_scores_device(s_d, f_d, d_d, b_d, pool.contiguous().reshape(N, P), P, uniform_mix=alpha, nfix=nfix)
+    if cls is not None:
+        cls_d, cnt, tot = _pool_counts_device(f_d, cls, E)
+        return _saliency_scores_device(s_d, f_d, d_d, b_d, tot, 0, cnt, cls_d, E, alpha, nfix)
+    return _saliency_scores_device(s_d, f_d, d_d, b_d, uniform_mix=alpha, nfix=nfix)
+
+
+def AUC_shuffled(saliencyMap, fixationMap, otherMap):
+    """Shuffled AUC (Zhang et al. 2008; Bylinskii et al. 2019) in its exact form: the weighted Mann-Whitney AUC of the saliency values
+    at the fixated pixels (fixationMap > 0) against the pixels of otherMap, which holds non-negative integer counts (how often a pixel
+    was fixated on OTHER images); ties count half, the map is compared unnormalised.  NaN without a fixation, with an empty otherMap
+    or a NaN pixel; a non-integral or negative otherMap raises ValueError."""
+    s, f = _pair(saliencyMap, fixationMap)
+    _pair(saliencyMap, otherMap)
+    return float(saliency_scores_pairs(s[None], f[None], other_maps=np.asarray(otherMap)[None])["sAUC"].item())
+
+
+def CC(saliencyMap, densityMap):
+    """Pearson's correlation coefficient of the two maps (NaN if one of them is constant)"""
+    s, d = _pair(saliencyMap, densityMap)
+    return float(saliency_scores_pairs(s[None], density_maps=d[None])["CC"].item())
+
+
+def SIM(saliencyMap, densityMap):
+    """histogram intersection of the two sum-normalised maps (no min-max step; NaN if a map's sum is <= 0 or not finite)"""
+    s, d = _pair(saliencyMap, densityMap)
+    return float(saliency_scores_pairs(s[None], density_maps=d[None])["SIM"].item())
+
+
+def InfoGain(saliencyMap, fixationMap, baselineMap, *, uniform_mix):
+    """information gain over the baseline in bits per fixation: mean over the fixated pixels of log2(eps + p) - log2(eps + q) with
+    p = (1 - uniform_mix) S / sum S + uniform_mix / P, q the same of the baseline, eps = 2^-52 (sum-normalised maps, no min-max
+    step).  uniform_mix is required: with 0 a fixation on an exact zero of a density costs 52 bits."""
+    _check_mix(uniform_mix)
+    s, f = _pair(saliencyMap, fixationMap)
+    _, b = _pair(saliencyMap, baselineMap)
+    return float(saliency_scores_pairs(s[None], f[None], baseline_maps=b[None], uniform_mix=uniform_mix)["IG"].item())
 
 
 # ---- scanpath distances (visual_attention_metrics.py:205-218, :332-388, :444-476) ----------------------------------------------------

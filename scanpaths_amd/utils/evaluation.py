@@ -468,31 +468,110 @@ def predict_results_fix_vectors(predict_results):
     return fvs, keys
 
 
-def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, frame_size=(240, 320), *, sigma, **kw):
-    """Saliency metrics of predicted scanpaths against human ones, one map set per distinct key (a question id, an image name: any
-    hashable), in first-appearance order of gt_keys.  gt_fix_vectors[i] belongs to gt_keys[i], predict_fix_vectors[j] to
-    predict_keys[j]; a predicted key that gt_keys does not hold raises ValueError.  sigma (pixels of the output map) is required;
-    **kw goes to evaltools.saliency_maps.scanpath_saliency (output_shape, mode, pred_weight, truncate).
-    Returns (means, per_key): means[metric] = nanmean over the keys and means[metric + "_nan"] = how many keys scored NaN, for
-    AUC_Judd, NSS and KLdiv; per_key = {"keys": [...], metric: float64 [G] numpy arrays, "gt_dropped" / "pred_dropped": int [G]}."""
-    from .evaltools.saliency_maps import scanpath_saliency
-    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
-    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
+def _key_index(gt_keys, image_keys):
+    """keys in first-appearance order -> (index of every key, image index per key or None): one image per key, or ValueError"""
     index = {}
     for k in gt_keys:
         index.setdefault(k, len(index))
-    unknown = [k for k in predict_keys if k not in index]
-    if unknown:
-        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
-    res = scanpath_saliency(gt_fix_vectors, [index[k] for k in gt_keys], predict_fix_vectors, [index[k] for k in predict_keys],
-                            frame_size, sigma, num_groups=len(index), **kw)
-    per_key = {"keys": list(index)}
-    per_key.update({k: v.cpu().numpy() for k, v in res.items()})
+    if image_keys is None:
+        return index, None
+    image_keys = list(image_keys)
+    if len(image_keys) != len(gt_keys):
+        raise ValueError("one image key per ground-truth fixation vector is required")
+    images, of_key = {}, {}
+    for k, im in zip(gt_keys, image_keys):
+        if of_key.setdefault(k, im) != im:
+            raise ValueError(f"key {k!r} is given on two images: {of_key[k]!r} and {im!r}")
+        images.setdefault(im, len(images))
+    return index, [images[of_key[k]] for k in index]
+
+
+def _saliency_means(per_key, metrics):
     means = {}
-    for m in ("AUC_Judd", "NSS", "KLdiv"):
+    for m in metrics:
         v = per_key[m]
         nan = np.isnan(v)
         means[m] = float(v[~nan].mean()) if (~nan).any() else float("nan")
         means[m + "_nan"] = int(nan.sum())
-    return means, per_key
+    return means
+
+
+def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, frame_size=(240, 320), *, sigma, extra_metrics=(),
+                        image_keys=None, **kw):
+    """Saliency metrics of predicted scanpaths against human ones, one map set per distinct key (a question id, an image name: any
+    hashable), in first-appearance order of gt_keys.  gt_fix_vectors[i] belongs to gt_keys[i], predict_fix_vectors[j] to
+    predict_keys[j]; a predicted key that gt_keys does not hold raises ValueError.  sigma (pixels of the output map) is required;
+    **kw goes to evaltools.saliency_maps.scanpath_saliency (output_shape, mode, pred_weight, truncate, uniform_mix, baseline_sigma).
+    extra_metrics: any of "sAUC", "CC", "SIM", "IG" (Bylinskii et al. 2019 on sum-normalised maps, no min-max step; "IG" needs the
+    keyword uniform_mix); image_keys[i]: the image gt_fix_vectors[i] was recorded on (default: every key is its own image; one key on
+    two images raises ValueError) -- the shuffled AUC's negatives and the baseline of the information gain come from the OTHER images.
+    Returns (means, per_key): means[metric] = nanmean over the keys and means[metric + "_nan"] = how many keys scored NaN, for
+    AUC_Judd, NSS, KLdiv and every extra; per_key = {"keys": [...], metric: float64 [G] numpy arrays, "gt_dropped" / "pred_dropped":
+    int [G]}.  The same call on the human side alone: saliency_human_evaluation (ceiling), saliency_centre_prior_evaluation (floor)."""
+    from .evaltools.saliency_maps import scanpath_saliency
+    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
+    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, images = _key_index(gt_keys, image_keys)
+    unknown = [k for k in predict_keys if k not in index]
+    if unknown:
+        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    if extra_metrics or images is not None:
+        kw = dict(kw, extra_metrics=extra_metrics, image_groups=images)
+    res = scanpath_saliency(gt_fix_vectors, [index[k] for k in gt_keys], predict_fix_vectors, [index[k] for k in predict_keys],
+                            frame_size, sigma, num_groups=len(index), **kw)
+    per_key = {"keys": list(index)}
+    per_key.update({k: v.cpu().numpy() for k, v in res.items()})
+    return _saliency_means(per_key, ("AUC_Judd", "NSS", "KLdiv") + tuple(extra_metrics)), per_key
+
+
+def saliency_centre_prior_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *, sigma, extra_metrics=(), image_keys=None, **kw):
+    """The centre-prior floor of saliency_evaluation: the prediction of a key is its baseline, the blur of every human fixation
+    recorded on the OTHER images -- what can be said about where people look without seeing the image.  Same arguments (without
+    predictions), same (means, per_key) result; the information gain over the baseline is exactly 0 for every key that has one, and a
+    key without another image scores NaN."""
+    return saliency_evaluation(gt_fix_vectors, [], gt_keys, [], frame_size, sigma=sigma, extra_metrics=extra_metrics,
+                               image_keys=image_keys, prediction="centre_prior", **kw)
+
+
+def saliency_human_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *, sigma, extra_metrics=(), image_keys=None, **kw):
+    """The human ceiling of saliency_evaluation: for every key with at least two human scanpaths each scanpath in turn is held out as
+    the human side and the other scanpaths of the key are the prediction; the key's score is the nanmean over its held-out scanpaths.
+    A key with one scanpath scores NaN and is counted in means[metric + "_nan"] (its fixations still belong to the other keys' pools
+    and baselines).  All held-out folds of the call are scored together by the launches of one saliency_evaluation call; the pool of
+    a fold counts the held-out maps of the other images.  Same (means, per_key) result; gt_dropped / pred_dropped are sums over the
+    folds."""
+    from .evaltools.saliency_maps import scanpath_saliency
+    gt_keys = list(gt_keys)
+    if len(gt_keys) != len(gt_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, images = _key_index(gt_keys, image_keys)
+    members = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        members[index[k]].append(i)
+    fold_key = np.array([index[k] for k in gt_keys], dtype=np.int64)           # fold i holds out scanpath i
+    pred, pred_fold = [], []
+    for i, k in enumerate(gt_keys):
+        for j in members[index[k]]:
+            if j != i:
+                pred.append(gt_fix_vectors[j])
+                pred_fold.append(i)
+    if extra_metrics or images is not None:
+        kw = dict(kw, extra_metrics=extra_metrics, image_groups=fold_key if images is None else np.asarray(images)[fold_key])
+    res = scanpath_saliency(gt_fix_vectors, np.arange(len(gt_keys)), pred, pred_fold, frame_size, sigma, num_groups=len(gt_keys), **kw)
+    metrics = ("AUC_Judd", "NSS", "KLdiv") + tuple(extra_metrics)
+    folds = {k: v.cpu().numpy() for k, v in res.items()}
+    per_key = {"keys": list(index)}
+    for m in metrics:
+        per_key[m] = np.full(len(index), np.nan)
+    for m in ("gt_dropped", "pred_dropped"):
+        per_key[m] = np.zeros(len(index), dtype=np.int64)
+        np.add.at(per_key[m], fold_key, folds[m])
+    for q, mem in enumerate(members):
+        if len(mem) < 2:
+            continue
+        for m in metrics:
+            v = folds[m][mem]
+            if not np.isnan(v).all():
+                per_key[m][q] = np.nanmean(v)
+    return _saliency_means(per_key, metrics), per_key
