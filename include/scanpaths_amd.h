@@ -534,6 +534,22 @@ int sp_scan_tde(const double* fix, int ncol, const int64_t* start, const int* co
  * = (vector, direction, length, position, duration), five NaNs for a pair with a scanpath of fewer than 3 fixations. */
 int sp_scan_multimatch(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs,
                        double screen_w, double screen_h, double* out, void* stream);
+/* Scanpath distances beyond the reference's toolbox (csrc/scandist.hip, one wavefront per pair), same fixation
+ * layout as sp_scan_sed_stde; P = the first scanpath of a pair (n fixations), Q = the second (m); coordinates / max_dim;
+ * d(i,j) = sqrt(dx*dx + dy*dy), every operation rounded on its own.  dtw: D[n-1][m-1] of D[i][j] = min(D[i-1][j-1], D[i-1][j],
+ * D[i][j-1]) + d(i,j); frechet: the same recursion with max in place of +; hausdorff: max(max_i min_j d, max_j min_i d);
+ * eyenalysis: (sum_i min_j d + sum_j min_i d) / max(n, m), position only, sums left to right.  Each output [npairs] may be NULL (not
+ * all four) and only the ones given are computed.  NaN for a pair with an empty scanpath.  The kernels guard themselves: a pair with a
+ * scanpath of more than sp_scan_max_fixations() fixations gets NaN in every output and none of its fixations is read. */
+int sp_scan_distances(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, double max_dim,
+                      double* dtw, double* frechet, double* hausdorff, double* eyenalysis, void* stream);
+/* Cross-recurrence (Anderson et al. 2015) of the first N = min(n, m) fixations of each scanpath: c[i][j] = d(i,j) <= radius over the
+ * full N x N matrix, R = sum c.  out [npairs][4] = REC = 100 R / N^2, DET = 100 D_L / R (points on diagonal runs of length >= min_line,
+ * all 2N - 1 diagonals), LAM = 100 (H_L + V_L) / (2 R) (points on row / column runs), CORM = 100 sum (j - i) c[i][j] / ((N - 1) R);
+ * integer counts, one multiplication and one division in double each.  NaN: all four for N = 0 or a scanpath beyond the limit; DET,
+ * LAM, CORM for R = 0; CORM for N = 1.  radius > 0 in the units left after the division by max_dim; min_line >= 2. */
+int sp_scan_recurrence(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, double max_dim,
+                       double radius, int min_line, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

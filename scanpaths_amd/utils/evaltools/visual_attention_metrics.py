@@ -12,6 +12,9 @@ csrc/scanmetrics.hip, plus the batched form the validation loops need:
     extra = saliency_scores_pairs(saliency_maps, fixation_maps, density_maps, baseline_maps, image_groups=img, uniform_mix=0.01)
     # {"sAUC", "CC", "SIM", "IG": device tensors [N]}; per map: AUC_shuffled, CC, SIM, InfoGain
 
+    d = scanpath_distances_pairs(scanpaths, pairs, metrics=("DTW", "REC", "DET"), radius=30.0)   # {metric: float64 numpy [npairs]}
+    DTW(h, s), frechet_distance(h, s), hausdorff_distance(h, s), eyenalysis_distance(h, s), cross_recurrence(h, s, radius=30.0)
+
 SED is bit-exact; STDE follows numpy's float64 evaluation order (differences only in the last bit of exp()).  No CPU path."""
 from __future__ import annotations
 
@@ -445,6 +448,129 @@ def scaled_time_delay_embedding_distance(human_scanpath, simulated_scanpath, ima
         return None
     tde, _ = tde_pairs([human_scanpath, simulated_scanpath], [(0, 1)], k=0, max_dim=float(max(np.shape(image))))
     return float(tde.item())
+
+
+# ---- DTW, Frechet, Hausdorff, Eyenalysis, cross-recurrence (no counterpart in the reference), csrc/scandist.hip ------------
+SCANPATH_DISTANCES = ("DTW", "Frechet", "Hausdorff", "Eyenalysis", "REC", "DET", "LAM", "CORM")
+_RECURRENCE = SCANPATH_DISTANCES[4:]
+MAX_FIXATIONS = 64          # = sp_scan_max_fixations(), known here so that a refusal needs no library (held equal by the tests)
+
+
+def _check_distance_args(metrics, max_dim, radius, min_line):
+    """(metrics as a tuple, max_dim, radius or None, min_line), or the refusal -- before any device or library call"""
+    metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+    unknown = [m for m in metrics if m not in SCANPATH_DISTANCES]
+    if unknown:
+        raise ValueError(f"unknown scanpath distance {unknown[0]!r}: one of {SCANPATH_DISTANCES}")
+    if len(set(metrics)) != len(metrics):
+        raise ValueError(f"repeated scanpath distance in {metrics}")
+    if not metrics:
+        raise ValueError("no scanpath distance asked for")
+    md = float(max_dim)
+    if not (np.isfinite(md) and md > 0):
+        raise ValueError(f"max_dim {max_dim!r}: a positive finite number")
+    if isinstance(min_line, bool) or int(min_line) != min_line or int(min_line) < 2:
+        raise ValueError(f"min_line {min_line!r}: an integer >= 2")
+    rad = None
+    if any(m in _RECURRENCE for m in metrics):
+        if radius is None:
+            raise TypeError("the cross-recurrence measures need the keyword radius (in the units left after the division by max_dim; it "
+                            "has no default)")
+        rad = float(radius)
+        if not (np.isfinite(rad) and rad > 0):
+            raise ValueError(f"radius {radius!r}: a positive finite number")
+    return metrics, md, rad, int(min_line)
+
+
+def scanpath_distances_pairs(scanpaths: Sequence[np.ndarray], pairs, metrics=SCANPATH_DISTANCES[:4], max_dim: float = 1.0, radius=None,
+                             min_line: int = 2) -> Dict[str, np.ndarray]:
+    """scanpaths / pairs as for sed_stde_pairs: pairs[p] = (human index P, simulated index Q); only x and y are read, divided by max_dim
+    first.  metrics: any of SCANPATH_DISTANCES (default: the four distances) --
+      "DTW": dynamic time warping, D[i][j] = min(D[i-1][j-1], D[i-1][j], D[i][j-1]) + d(i,j); "Frechet": the discrete Frechet distance,
+      the same recursion with max in place of +; "Hausdorff": max(max_i min_j d, max_j min_i d); "Eyenalysis" (position only):
+      (sum_i min_j d + sum_j min_i d) / max(n, m);
+      "REC", "DET", "LAM", "CORM": the cross-recurrence measures of Anderson et al. (2015) in per cent, over the first N = min(n, m)
+      fixations of each scanpath, two fixations recurrent when d <= radius (keyword radius, required then, in the units left after the
+      division by max_dim) and lines counted from min_line points.
+    Returns {metric: float64 numpy [npairs]}: NaN for a pair with an empty scanpath; DET / LAM / CORM NaN without a recurrent point,
+    CORM NaN for N = 1.  One upload, one launch per entry point (sp_scan_distances, sp_scan_recurrence) and one copy back whatever the
+    number of pairs; an empty pair list touches no device."""
+    metrics, md, rad, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
+    arrs = [np.asarray(a, dtype=np.float64) for a in scanpaths]
+    arrs = [a.reshape(len(a), -1) if len(a) else np.zeros((0, a.shape[-1] if a.ndim == 2 else 2)) for a in arrs]
+    ncol = max([a.shape[1] for a in arrs if a.shape[0]], default=2)
+    if any(a.shape[1] != ncol and a.shape[0] > 0 for a in arrs) or ncol < 2:
+        raise ValueError("scanpaths need the same number (>= 2) of columns")
+    counts = np.array([a.shape[0] for a in arrs], dtype=np.int32)
+    if len(counts) and counts.max() > MAX_FIXATIONS:
+        raise ValueError(f"scanpath of {counts.max()} fixations exceeds the kernel limit {MAX_FIXATIONS}")
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if pr.size and (pr.min() < 0 or pr.max() >= len(arrs)):
+        raise ValueError(f"pair index out of range: {len(arrs)} scanpaths, indices {pr.min()} .. {pr.max()}")
+    npairs = pr.shape[0]
+    if npairs == 0:
+        return {m: np.zeros(0, dtype=np.float64) for m in metrics}
+    dev = _device()
+    L = hip.lib()
+    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
+        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
+    # one host buffer, one upload: fixations | starts (int64) | pairs (int32) | counts (int32)
+    cat = np.concatenate([a for a in arrs if a.shape[0]] or [np.zeros((1, ncol))], 0)
+    start = np.cumsum(counts, dtype=np.int64) - counts
+    parts = [np.ascontiguousarray(cat).view(np.uint8).reshape(-1), start.view(np.uint8), pr.astype(np.int32).reshape(-1).view(np.uint8),
+             counts.view(np.uint8)]
+    off = np.cumsum([0] + [len(b) for b in parts])
+    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
+    fix_p, start_p, pairs_p, count_p = (buf.data_ptr() + int(o) for o in off[:4])
+    dist = [m for m in SCANPATH_DISTANCES[:4] if m in metrics]
+    out = torch.empty((len(dist) + (4 if rad is not None else 0)) * npairs, dtype=torch.float64, device=dev)
+    if dist:
+        slot = {m: out.data_ptr() + 8 * npairs * k for k, m in enumerate(dist)}
+        check(L.sp_scan_distances(fix_p, ncol, start_p, count_p, pairs_p, npairs, md, slot.get("DTW"), slot.get("Frechet"),
+                                  slot.get("Hausdorff"), slot.get("Eyenalysis"), hip.stream()), "sp_scan_distances")
+    if rad is not None:
+        check(L.sp_scan_recurrence(fix_p, ncol, start_p, count_p, pairs_p, npairs, md, rad, min_line,
+                                   out.data_ptr() + 8 * npairs * len(dist), hip.stream()), "sp_scan_recurrence")
+    host = out.cpu().numpy()               # the one copy back (synchronises: buf and out outlive the launches)
+    rec = host[len(dist) * npairs:].reshape(npairs, 4) if rad is not None else None
+    res = {}
+    for m in metrics:
+        res[m] = (np.ascontiguousarray(rec[:, _RECURRENCE.index(m)]) if m in _RECURRENCE
+                  else host[dist.index(m) * npairs:(dist.index(m) + 1) * npairs].copy())
+    return res
+
+
+def _one_distance(metric, human_scanpath, simulated_scanpath):
+    return float(scanpath_distances_pairs([human_scanpath, simulated_scanpath], [(0, 1)], metrics=(metric,))[metric][0])
+
+
+def DTW(human_scanpath, simulated_scanpath):
+    """dynamic time warping distance of the two scanpaths' positions (sum of d along the cheapest monotone alignment); NaN if one is empty"""
+    return _one_distance("DTW", human_scanpath, simulated_scanpath)
+
+
+def frechet_distance(human_scanpath, simulated_scanpath):
+    """discrete Frechet distance (Eiter & Mannila 1994): the largest d along the monotone alignment that keeps it smallest"""
+    return _one_distance("Frechet", human_scanpath, simulated_scanpath)
+
+
+def hausdorff_distance(human_scanpath, simulated_scanpath):
+    """Hausdorff distance of the two sets of fixation positions"""
+    return _one_distance("Hausdorff", human_scanpath, simulated_scanpath)
+
+
+def eyenalysis_distance(human_scanpath, simulated_scanpath):
+    """Eyenalysis (Mathot et al. 2012) on positions only: every fixation's distance to the nearest fixation of the other scanpath,
+    summed over both scanpaths and divided by the longer one's length"""
+    return _one_distance("Eyenalysis", human_scanpath, simulated_scanpath)
+
+
+def cross_recurrence(human_scanpath, simulated_scanpath, *, radius, min_line=2):
+    """{"REC", "DET", "LAM", "CORM"} of Anderson et al. (2015), in per cent: recurrence, determinism (diagonal lines), laminarity (row
+    and column lines) and centre of recurrence mass of the cross-recurrence matrix of the first min(n, m) fixations.  radius (pixels;
+    required, no default): two fixations are recurrent when d <= radius."""
+    res = scanpath_distances_pairs([human_scanpath, simulated_scanpath], [(0, 1)], metrics=_RECURRENCE, radius=radius, min_line=min_line)
+    return {m: float(res[m][0]) for m in _RECURRENCE}
 
 
 from .saliency_maps import density_maps, fixation_maps, gaussian_weights, scanpath_saliency  # noqa: E402,F401  (producers of the maps above)

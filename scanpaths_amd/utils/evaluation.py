@@ -575,3 +575,103 @@ def saliency_human_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *,
             if not np.isnan(v).all():
                 per_key[m][q] = np.nanmean(v)
     return _saliency_means(per_key, metrics), per_key
+
+
+# ---- DTW, Frechet, Hausdorff, Eyenalysis and cross-recurrence of sampled scanpaths (evaltools/visual_attention_metrics.py, -------------
+# ---- csrc/scandist.hip): measures the reference's tables do not hold, so they get a keyed call of their own ----------------------------
+_LOWER_IS_BETTER = ("DTW", "Frechet", "Hausdorff", "Eyenalysis")
+_HIGHER_IS_BETTER = ("REC", "DET", "LAM")            # CORM is signed: it has no best
+
+
+def _xy(fv) -> np.ndarray:
+    if isinstance(fv, np.ndarray) and fv.dtype.names is None and fv.ndim == 2:
+        return np.asarray(fv[:, :2], dtype=np.float64)
+    a = np.array([list(_) for _ in list(fv)], dtype=np.float64)
+    return a.reshape(len(a), -1)[:, :2] if len(a) else np.zeros((0, 2))
+
+
+def _nanmean(v) -> float:
+    v = v[~np.isnan(v)]
+    return float(v.mean()) if v.size else float("nan")
+
+
+def _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_line):
+    """pairs[p] = (human path, predicted path), owner[p] = (key index, prediction id), the pairs of one prediction next to each other
+    -> (means, per_key) of the keyed calls below"""
+    from .evaltools.visual_attention_metrics import scanpath_distances_pairs
+    scores = scanpath_distances_pairs(paths, pairs, metrics=metrics, max_dim=max_dim, radius=radius, min_line=min_line)
+    G = len(index)
+    own = np.asarray(owner, dtype=np.int64).reshape(-1, 2)
+    key_of_pair, pred_of_pair = own[:, 0], own[:, 1]
+
+    def by_key(key_of):                                  # per key: the positions that belong to it, in their order
+        order = np.argsort(key_of, kind="stable")
+        return np.split(order, np.cumsum(np.bincount(key_of, minlength=G))[:-1])
+
+    seg = np.flatnonzero(np.r_[True, pred_of_pair[1:] != pred_of_pair[:-1]]) if len(own) else np.zeros(0, dtype=np.int64)
+    pairs_of_key, preds_of_key = by_key(key_of_pair), by_key(key_of_pair[seg])
+    per_key = {"keys": list(index)}
+    names = []
+    for m in metrics:
+        v = scores[m]
+        per_key[m] = np.array([_nanmean(v[ps]) for ps in pairs_of_key], dtype=np.float64)
+        names.append(m)
+        if m in _LOWER_IS_BETTER or m in _HIGHER_IS_BETTER:
+            # the best over each prediction's human scanpaths (fmin / fmax skip NaN; all NaN stays NaN), then the mean over the key's predictions
+            best = (np.fmin if m in _LOWER_IS_BETTER else np.fmax).reduceat(v, seg) if len(seg) else np.zeros(0)
+            per_key[m + "_best"] = np.array([_nanmean(best[ps]) for ps in preds_of_key], dtype=np.float64)
+            names.append(m + "_best")
+    return _saliency_means(per_key, names), per_key
+
+
+def scanpath_distance_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, metrics, max_dim=1.0, radius=None,
+                                 min_line=2):
+    """DTW / Frechet / Hausdorff / Eyenalysis / REC / DET / LAM / CORM (metrics: any of visual_attention_metrics.SCANPATH_DISTANCES;
+    the recurrence measures need radius) of predicted scanpaths against human ones, grouped by key as saliency_evaluation groups them:
+    gt_fix_vectors[i] belongs to gt_keys[i], predict_fix_vectors[j] to predict_keys[j], a predicted key that gt_keys does not hold
+    raises ValueError.  Every (human scanpath of the key, prediction of the key) pair of the whole call is scored in one batch on the
+    device.  Returns (means, per_key): per_key[metric] = nanmean over the key's pairs, per_key[metric + "_best"] = mean over the key's
+    predictions of the best value over the key's human scanpaths (the smallest distance, the largest REC / DET / LAM; CORM has none),
+    float64 [G] in first-appearance order of gt_keys (per_key["keys"]); a key without predictions scores NaN.  means[name] = nanmean
+    over the keys, means[name + "_nan"] = how many keys scored NaN.  The ceiling: scanpath_distance_human_evaluation."""
+    from .evaltools.visual_attention_metrics import _check_distance_args
+    metrics, max_dim, radius, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
+    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
+    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, _ = _key_index(gt_keys, None)
+    unknown = [k for k in predict_keys if k not in index]
+    if unknown:
+        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in predict_fix_vectors]
+    humans = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        humans[index[k]].append(i)
+    pairs, owner = [], []
+    for j, k in enumerate(predict_keys):
+        for i in humans[index[k]]:
+            pairs.append((i, len(gt_keys) + j))
+            owner.append((index[k], j))
+    return _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_line)
+
+
+def scanpath_distance_human_evaluation(gt_fix_vectors, gt_keys, *, metrics, max_dim=1.0, radius=None, min_line=2):
+    """The human ceiling of scanpath_distance_evaluation: every ordered pair of distinct human scanpaths of a key, the first as the
+    human side and the second as the "prediction"; a key with one scanpath scores NaN.  Same (means, per_key) result."""
+    from .evaltools.visual_attention_metrics import _check_distance_args
+    metrics, max_dim, radius, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
+    gt_keys = list(gt_keys)
+    if len(gt_keys) != len(gt_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, _ = _key_index(gt_keys, None)
+    members = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        members[index[k]].append(i)
+    pairs, owner = [], []
+    for q, mem in enumerate(members):
+        for j in mem:
+            for i in mem:
+                if i != j:
+                    pairs.append((i, j))
+                    owner.append((q, j))
+    return _distance_tables(index, [_xy(fv) for fv in gt_fix_vectors], pairs, owner, metrics, max_dim, radius, min_line)
