@@ -550,6 +550,30 @@ int sp_scan_distances(const double* fix, int ncol, const int64_t* start, const i
  * LAM, CORM for R = 0; CORM for N = 1.  radius > 0 in the units left after the division by max_dim; min_line >= 2. */
 int sp_scan_recurrence(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, double max_dim,
                        double radius, int min_line, double* out, void* stream);
+/* Sequence score and fixation edit distance on mean-shift clusters (csrc/seqscore.hip), float64, every operation
+ * rounded on its own, sums left to right in index order.
+ * Mean shift with the flat kernel, one block per group: group g = rows gstart[g] .. +gcount[g] of pts [rows][ncol >= 2] (x, y, ...),
+ * at most the max_points() value below of them.  Every point is a seed: c = the point; repeat { S = points with dx*dx + dy*dy <= h*h
+ * around c, k = |S|, new = (sum_S x / k, sum_S y / k), step = sqrt(dx*dx + dy*dy) of new - c, c = new } until step <= 1e-3 h or
+ * max_iter iterations have followed the first; the seed's entry is (k, c).  Entries ordered by k, then x, then y descending, then seed
+ * ascending; an entry that no kept entry before it has within h*h is kept and is the next cluster.  The K centres of group g go to rows
+ * gstart[g] .. of centres [rows][2], K to ncentres[g], the centres' k to weight [rows] (may be NULL), the cluster of every point of the
+ * group (smallest dx*dx + dy*dy, the lowest cluster on ties) to labels [rows] (may be NULL).  A group with a count outside
+ * [0, max_points()] gets ncentres -1 and labels -1 and none of its points is read.  bandwidth h > 0 and finite, max_iter >= 1. */
+int sp_meanshift_max_points(void);
+int sp_meanshift(const double* pts, int ncol, const int64_t* gstart, const int* gcount, int ngroups, double bandwidth, int max_iter,
+                 double* centres, int* ncentres, int* weight, int* labels, void* stream);
+/* The cluster of every fixation of nscan scanpaths (fixation layout of sp_scan_sed_stde) under the centres of group[s], as sp_meanshift
+ * wrote them: labels_out [rows], -1 where the group has ncentres <= 0.  A scanpath beyond sp_scan_max_fixations() is left alone. */
+int sp_scan_cluster_strings(const double* fix, int ncol, const int64_t* start, const int* count, const int* group, int nscan,
+                            const double* centres, const int64_t* gstart, const int* ncentres, int* labels_out, void* stream);
+/* Strings a = labels[start[i] .. +count[i]] (n) and b likewise (m) of pairs[p] = (i, j).  ss[p] = F[n][m] / max(n, m) with F[i][0] =
+ * gap * i, F[0][j] = gap * j, F[i][j] = max(F[i-1][j-1] + (a[i-1] == b[j-1] ? 1 : 0), F[i-1][j] + gap, F[i][j-1] + gap) (Needleman-Wunsch;
+ * gap <= 0 and finite; gap 0: LCS / max(n, m)); fed[p] = the unit-cost Levenshtein distance, as a double.  Each output [npairs] may be
+ * NULL (not both).  NaN in both for a pair with a negative label or a count outside [0, sp_scan_max_fixations()] (nothing of it is
+ * read); ss NaN for n = m = 0. */
+int sp_scan_sequence(const int* labels, const int64_t* start, const int* count, const int* pairs, int npairs, double gap, double* ss,
+                     double* fed, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -147,6 +147,10 @@ SIGNATURES = {
     "sp_scan_multimatch": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _P, _P]),
     "sp_scan_distances": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, _P, _P, _P, _P, _P]),
     "sp_scan_recurrence": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, _P, _P]),
+    "sp_meanshift_max_points": (_I, []),
+    "sp_meanshift": (_I, [_P, _I, _P, _P, _I, C.c_double, _I, _P, _P, _P, _P, _P]),
+    "sp_scan_cluster_strings": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
+    "sp_scan_sequence": (_I, [_P, _P, _P, _P, _I, C.c_double, _P, _P, _P]),
     "sp_sample_actions": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, _P, _P]),
     "sp_generate_scanpath": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sp_beam_search": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -596,10 +596,14 @@ def _nanmean(v) -> float:
 
 
 def _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_line):
-    """pairs[p] = (human path, predicted path), owner[p] = (key index, prediction id), the pairs of one prediction next to each other
-    -> (means, per_key) of the keyed calls below"""
+    """pairs[p] = (human path, predicted path) -> (means, per_key) of the keyed calls below"""
     from .evaltools.visual_attention_metrics import scanpath_distances_pairs
     scores = scanpath_distances_pairs(paths, pairs, metrics=metrics, max_dim=max_dim, radius=radius, min_line=min_line)
+    return _pair_tables(index, scores, owner, metrics, _LOWER_IS_BETTER, _HIGHER_IS_BETTER)
+
+
+def _pair_tables(index, scores, owner, metrics, lower_is_better, higher_is_better):
+    """scores[metric] [npairs], owner[p] = (key index, prediction id), the pairs of one prediction next to each other -> (means, per_key)"""
     G = len(index)
     own = np.asarray(owner, dtype=np.int64).reshape(-1, 2)
     key_of_pair, pred_of_pair = own[:, 0], own[:, 1]
@@ -616,9 +620,9 @@ def _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_l
         v = scores[m]
         per_key[m] = np.array([_nanmean(v[ps]) for ps in pairs_of_key], dtype=np.float64)
         names.append(m)
-        if m in _LOWER_IS_BETTER or m in _HIGHER_IS_BETTER:
+        if m in lower_is_better or m in higher_is_better:
             # the best over each prediction's human scanpaths (fmin / fmax skip NaN; all NaN stays NaN), then the mean over the key's predictions
-            best = (np.fmin if m in _LOWER_IS_BETTER else np.fmax).reduceat(v, seg) if len(seg) else np.zeros(0)
+            best = (np.fmin if m in lower_is_better else np.fmax).reduceat(v, seg) if len(seg) else np.zeros(0)
             per_key[m + "_best"] = np.array([_nanmean(best[ps]) for ps in preds_of_key], dtype=np.float64)
             names.append(m + "_best")
     return _saliency_means(per_key, names), per_key
@@ -675,3 +679,78 @@ def scanpath_distance_human_evaluation(gt_fix_vectors, gt_keys, *, metrics, max_
                     pairs.append((i, j))
                     owner.append((q, j))
     return _distance_tables(index, [_xy(fv) for fv in gt_fix_vectors], pairs, owner, metrics, max_dim, radius, min_line)
+
+
+# ---- sequence score and fixation edit distance on mean-shift clusters (evaltools/sequence_score.py, csrc/seqscore.hip) -----------------
+def _cluster_groups(index, gt_keys, cluster_keys):
+    """cluster group of every key: its own, or the one of its cluster key (several keys on one image share the image's clusters)"""
+    _, images = _key_index(gt_keys, cluster_keys)
+    return np.arange(len(index), dtype=np.int64) if images is None else np.asarray(images, dtype=np.int64)
+
+
+def sequence_score_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, bandwidth, metrics=("SS", "FED"), gap=0.0,
+                              max_iter=300, cluster_keys=None):
+    """Sequence score (Yang et al. 2020) and fixation edit distance (Mondal et al. 2023) of predicted scanpaths against human ones,
+    grouped by key as scanpath_distance_evaluation groups them.  All human fixations of a key are clustered by mean shift with the
+    flat kernel of radius bandwidth (required; pixels of the fixations' frame), every scanpath of the key becomes the string of its
+    fixations' clusters, SS = Needleman-Wunsch score (0/1 similarity, gap <= 0) / the longer length, FED = Levenshtein distance.
+    cluster_keys[i] (optional): the image gt_fix_vectors[i] was recorded on -- keys that share one are clustered together (one key on
+    two images raises ValueError).  Clustering, strings and every (human, prediction) pair of the whole call run as one batch on the
+    device.  Returns (means, per_key) as scanpath_distance_evaluation: per_key["SS"] / ["FED"] = nanmean over the key's pairs,
+    ["SS_best"] = mean over the key's predictions of the largest SS over the key's human scanpaths, ["FED_best"] of the smallest FED;
+    a key without predictions scores NaN; means[name + "_nan"] counts the NaN keys.  The ceiling: sequence_score_human_evaluation."""
+    from .evaltools.sequence_score import _check_cluster_args, _check_sequence_args, keyed_sequence_scores
+    _check_cluster_args(bandwidth, max_iter)
+    metrics, gap = _check_sequence_args(metrics, gap)
+    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
+    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, _ = _key_index(gt_keys, None)
+    unknown = [k for k in predict_keys if k not in index]
+    if unknown:
+        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    group_of_key = _cluster_groups(index, gt_keys, cluster_keys)
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in predict_fix_vectors]
+    path_group = np.array([group_of_key[index[k]] for k in gt_keys + predict_keys], dtype=np.int64)
+    human_group = np.r_[path_group[:len(gt_keys)], np.full(len(predict_keys), -1, dtype=np.int64)]
+    humans = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        humans[index[k]].append(i)
+    pairs, owner = [], []
+    for j, k in enumerate(predict_keys):
+        for i in humans[index[k]]:
+            pairs.append((i, len(gt_keys) + j))
+            owner.append((index[k], j))
+    scores = keyed_sequence_scores(paths, path_group, human_group, pairs, int(group_of_key.max()) + 1 if len(index) else 0,
+                                   bandwidth=bandwidth, metrics=metrics, gap=gap, max_iter=max_iter)
+    return _pair_tables(index, scores, owner, metrics, ("FED",), ("SS",))
+
+
+def sequence_score_human_evaluation(gt_fix_vectors, gt_keys, *, bandwidth, metrics=("SS", "FED"), gap=0.0, max_iter=300,
+                                    cluster_keys=None):
+    """The human ceiling of sequence_score_evaluation: every ordered pair of distinct human scanpaths of a key, the first as the human
+    side and the second as the "prediction", under the clusters of all human fixations of the key (the "prediction" included, as the
+    published evaluation does); a key with one scanpath scores NaN.  Same (means, per_key) result."""
+    from .evaltools.sequence_score import _check_cluster_args, _check_sequence_args, keyed_sequence_scores
+    _check_cluster_args(bandwidth, max_iter)
+    metrics, gap = _check_sequence_args(metrics, gap)
+    gt_keys = list(gt_keys)
+    if len(gt_keys) != len(gt_fix_vectors):
+        raise ValueError("one key per fixation vector is required")
+    index, _ = _key_index(gt_keys, None)
+    group_of_key = _cluster_groups(index, gt_keys, cluster_keys)
+    path_group = np.array([group_of_key[index[k]] for k in gt_keys], dtype=np.int64)
+    members = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        members[index[k]].append(i)
+    pairs, owner = [], []
+    for q, mem in enumerate(members):
+        for j in mem:
+            for i in mem:
+                if i != j:
+                    pairs.append((i, j))
+                    owner.append((q, j))
+    scores = keyed_sequence_scores([_xy(fv) for fv in gt_fix_vectors], path_group, path_group, pairs,
+                                   int(group_of_key.max()) + 1 if len(index) else 0, bandwidth=bandwidth, metrics=metrics, gap=gap,
+                                   max_iter=max_iter)
+    return _pair_tables(index, scores, owner, metrics, ("FED",), ("SS",))
