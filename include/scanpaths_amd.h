@@ -534,6 +534,22 @@ int sp_scan_tde(const double* fix, int ncol, const int64_t* start, const int* co
  * = (vector, direction, length, position, duration), five NaNs for a pair with a scanpath of fewer than 3 fixations. */
 int sp_scan_multimatch(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs,
                        double screen_w, double screen_h, double* out, void* stream);
+/* MultiMatch scanpath simplification (Jarodzka et al. 2010, Dewhurst et al. 2012; csrc/scansimplify.hip, one
+ * wavefront per scanpath), fixation layout of sp_scan_multimatch, float64, every operation rounded on its own.  With n saccades,
+ * l_i = fixation i+1 - fixation i, rho_i = sqrt(lx_i*lx_i + ly_i*ly_i), for 0 <= i <= n-2: direction candidate (lx_i*lx_{i+1} +
+ * ly_i*ly_{i+1}) > cos_tdir * (rho_i * rho_{i+1}) and duration_{i+1} < tdur; amplitude candidate rho_i < tamp and duration_{i+1} < tdur.
+ * A pass goes left to right over the candidates as they are at its start: a candidate i deletes fixation i+1 and the pass goes on at
+ * i+2, else at i+1.  A round = a direction pass (none when cos_tdir >= 1), then an amplitude pass on its result; rounds repeat until
+ * one deletes nothing.  The first and the last fixation stay.  The kept rows (x, y, duration) of scanpath k go to rows start[k] ..
+ * +count_out[k] of fix_out [total][3].  A count outside [0, sp_scan_max_fixations()] gives count_out 0 and none of its fixations is
+ * read.  cos_tdir in [-1, 1] (the cosine of the direction threshold, computed once by the caller), tdur and tamp finite and >= 0. */
+int sp_scan_simplify(const double* fix, int ncol, const int64_t* start, const int* count, int nscan, double cos_tdir, double tdur,
+                     double tamp, double* fix_out, int* count_out, void* stream);
+/* sp_scan_multimatch of simplified scanpaths: gate_count = the counts before simplification.  Five NaNs where gate_count < 3 for
+ * either scanpath of a pair, or count < 2 or count > sp_scan_max_fixations(); else the alignment and medians of sp_scan_multimatch
+ * (a scanpath of 2 fixations = 1 saccade is scored). */
+int sp_scan_multimatch_gated(const double* fix, int ncol, const int64_t* start, const int* count, const int* gate_count,
+                             const int* pairs, int npairs, double screen_w, double screen_h, double* out, void* stream);
 /* Scanpath distances beyond the reference's toolbox (csrc/scandist.hip, one wavefront per pair), same fixation
  * layout as sp_scan_sed_stde; P = the first scanpath of a pair (n fixations), Q = the second (m); coordinates / max_dim;
  * d(i,j) = sqrt(dx*dx + dy*dy), every operation rounded on its own.  dtw: D[n-1][m-1] of D[i][j] = min(D[i-1][j-1], D[i-1][j],

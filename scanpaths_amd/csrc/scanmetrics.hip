@@ -110,6 +110,8 @@ __global__ __launch_bounds__(64) void sed_stde_kernel(const double* __restrict__
 // (the rule by which the reference drops a pair).  float64 in numpy's evaluation order (no FMA contraction), so the alignment path
 // and four of the five values are bit-identical with the host restatement utils/evaltools/multimatch.py (its checker); the direction
 // value depends on atan2's last bit.  The DP keeps one row of costs and 2 bits of back-pointer per cell in per-thread scratch.
+// gate (may be NULL; sp_scan_multimatch_gated): the scanpaths' fixation counts BEFORE simplification.  With it the
+// "fewer than 3" rule looks at gate, and a simplified scanpath of 2 fixations = 1 saccade is scored (count < 2 or > MAXFIX: NaNs).
 constexpr int MMSAC = MAXFIX - 1;                 // saccades per scanpath
 __device__ __forceinline__ double mm_hyp(double a, double b) { return __dsqrt_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b))); }
 __device__ double mm_median(double* v, int n) {   // numpy.median: sort, mean of the two middle values for an even count
@@ -127,13 +129,14 @@ __device__ double mm_median(double* v, int n) {   // numpy.median: sort, mean of
 
 __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
                                                         const int* __restrict__ count, const int* __restrict__ pairs, int npairs,
-                                                        double screen_w, double screen_h, double* __restrict__ out) {
+                                                        double screen_w, double screen_h, double* __restrict__ out,
+                                                        const int* __restrict__ gate) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= npairs) return;
     const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
     const int n1 = count[i1], n2 = count[i2];
     double* o = out + 5 * (int64_t)p;
-    if (n1 < 3 || n2 < 3) {
+    if (gate ? (gate[i1] < 3 || gate[i2] < 3 || n1 < 2 || n2 < 2 || n1 > MAXFIX || n2 > MAXFIX) : (n1 < 3 || n2 < 3)) {
         for (int k = 0; k < 5; ++k) o[k] = NAN;
         return;
     }
@@ -282,7 +285,19 @@ extern "C" int sp_scan_multimatch(const double* fix, int ncol, const int64_t* st
     if (!fix || !start || !count || !pairs || !out) return SP_ENULL;
     if (npairs < 1 || ncol < 3 || !(screen_w > 0) || !(screen_h > 0)) return SP_EINVAL;
     hipLaunchKernelGGL(multimatch_kernel, dim3((npairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, fix, ncol, start, count, pairs,
-                       npairs, screen_w, screen_h, out);
+                       npairs, screen_w, screen_h, out, (const int*)nullptr);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+// sp_scan_multimatch on simplified scanpaths (sp_scan_simplify): five NaNs where gate_count (the counts before simplification) is
+// below 3 for either scanpath of a pair, or count is outside 2 .. sp_scan_max_fixations(); else the same alignment and medians
+extern "C" int sp_scan_multimatch_gated(const double* fix, int ncol, const int64_t* start, const int* count, const int* gate_count,
+                                        const int* pairs, int npairs, double screen_w, double screen_h, double* out, void* stream) {
+    if (!fix || !start || !count || !gate_count || !pairs || !out) return SP_ENULL;
+    if (npairs < 1 || ncol < 3 || !(screen_w > 0) || !(screen_h > 0)) return SP_EINVAL;
+    hipLaunchKernelGGL(multimatch_kernel, dim3((npairs + 63) / 64), dim3(64), 0, (hipStream_t)stream, fix, ncol, start, count, pairs,
+                       npairs, screen_w, screen_h, out, gate_count);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

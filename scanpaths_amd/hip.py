@@ -145,6 +145,8 @@ SIGNATURES = {
     "sp_scan_sed_stde": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, C.c_double, _P, _P, _P]),
     "sp_scan_tde": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _P, _P, _P]),
     "sp_scan_multimatch": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _P, _P]),
+    "sp_scan_simplify": (_I, [_P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _P, _P, _P]),
+    "sp_scan_multimatch_gated": (_I, [_P, _I, _P, _P, _P, _P, _I, C.c_double, C.c_double, _P, _P]),
     "sp_scan_distances": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, _P, _P, _P, _P, _P]),
     "sp_scan_recurrence": (_I, [_P, _I, _P, _P, _P, _I, C.c_double, C.c_double, _I, _P, _P]),
     "sp_meanshift_max_points": (_I, []),

@@ -11,7 +11,26 @@ PARITY: **unpinned** -- no fixture of the original package exists in the referen
 
 Two forms: ``docomparison`` (host numpy, one pair; the reference's call signature) and ``multimatch_pairs`` (round 4: ALL pairs of a
 validation call in one launch of ``sp_scan_multimatch``, one thread per pair -- the triple python loop per pair was the wall-clock of
-validation once ScanMatch / SED / STDE ran on the device).  The host form is the device kernel's checker (tests/test_scanmatch_gpu.py)."""
+validation once ScanMatch / SED / STDE ran on the device).  The host form is the device kernel's checker (tests/test_scanmatch_gpu.py).
+
+Simplification (``grouping=True``) is MultiMatch's first stage: successive saccades that point the same way (angle
+below TDir degrees) and successive short saccades (below TAmp pixels) are merged unless the fixation between them lasts TDur or
+longer, until nothing changes.  Here it DELETES fixations: merging saccades i and i + 1 removes fixation i + 1, so the result is an
+ordinary, shorter scanpath.  float64, every operation rounded on its own.  With n saccades, lx_i = x_{i+1} - x_i, ly_i likewise,
+rho_i = sqrt(lx_i*lx_i + ly_i*ly_i), for 0 <= i <= n - 2:
+  direction candidate  (lx_i*lx_{i+1} + ly_i*ly_{i+1}) > cosT * (rho_i * rho_{i+1})  and  duration_{i+1} < TDur, with cosT =
+                       cos(radians(TDir)) computed once on the host (the device gets the same double); a zero-length saccade is never
+                       one (0 > 0 is false); no direction pass at all for TDir == 0 (cosT >= 1)
+  amplitude candidate  rho_i < TAmp  and  duration_{i+1} < TDur
+One pass, either kind, is greedy and left to right on the arrays as they are at its start: a candidate i deletes fixation i + 1 and the
+pass goes on at i + 2, otherwise at i + 1 (within a run of candidates those at even offset are taken).  One round = a direction pass,
+then an amplitude pass on its result; rounds repeat until one deletes nothing.  The first and the last fixation are never deleted; a
+path of fewer than 3 fixations is returned unchanged.  Scoring with grouping: five NaNs if either ORIGINAL scanpath has fewer than 3
+fixations, otherwise the simplified paths are scored, even one of 2 fixations = 1 saccade.
+``simplify_scanpath`` is the host restatement (plain loops) and the checker of ``simplify_scanpaths`` / ``sp_scan_simplify`` (one
+wavefront per scanpath, all scanpaths of a call in one launch).  Known differences from ``multimatch_gaze`` (parity unpinned as above):
+  * the special handling of the last saccade in its amplitude pass is not restated;
+  * merged vectors are recomputed from the kept fixations rather than summed (equal up to rounding, exactly on integer grids)."""
 from __future__ import annotations
 
 import math
@@ -51,12 +70,70 @@ def _alignment(M):
     return path[::-1]
 
 
-def docomparison(fixation_vectors1, fixation_vectors2, screensize, grouping=False, TDir=0.0, TDur=0.0, TAmp=0.0):
-    if grouping:
-        raise NotImplementedError("scanpath simplification (grouping=True) is not used by the reference and not restated")
-    if not (len(fixation_vectors1) >= 3 and len(fixation_vectors2) >= 3):
-        return [np.nan] * 5
-    p1, p2 = _structure(fixation_vectors1), _structure(fixation_vectors2)
+MAX_FIXATIONS = 64      # = sp_scan_max_fixations(): one lane per fixation in sp_scan_simplify
+
+
+def _rows(data):
+    """fixation records / sequences of (x, y, duration) -> float64 [n, 3]; a plain 2-D array keeps its (>= 3) columns"""
+    if isinstance(data, np.ndarray) and data.dtype.names is None and data.ndim == 2:
+        a = np.asarray(data, dtype=np.float64)
+        if a.shape[1] < 3:
+            raise ValueError(f"a scanpath needs the columns x, y, duration: {a.shape[1]} columns")
+        return a
+    return np.array([list(_) for _ in list(data)], dtype=np.float64).reshape(-1, 3)
+
+
+def _thresholds(TDir, TDur, TAmp):
+    """(cosT, TDur, TAmp) as floats; ValueError unless all three are finite and >= 0 and TDir <= 180 degrees"""
+    try:
+        tdir, tdur, tamp = float(TDir), float(TDur), float(TAmp)
+    except (TypeError, ValueError):
+        raise ValueError(f"TDir, TDur, TAmp must be numbers: {TDir!r}, {TDur!r}, {TAmp!r}") from None
+    for name, v in (("TDir", tdir), ("TDur", tdur), ("TAmp", tamp)):
+        if not (math.isfinite(v) and v >= 0):
+            raise ValueError(f"{name} must be finite and >= 0: {v}")
+    if tdir > 180:
+        raise ValueError(f"TDir is an angle in degrees in [0, 180]: {tdir}")
+    return (1.0 if tdir == 0 else math.cos(math.radians(tdir))), tdur, tamp
+
+
+def _simplify_pass(rows, kind, cosT, tdur, tamp):
+    """one greedy left-to-right pass over the candidates of the rows as they are now -> the kept rows"""
+    n = len(rows) - 1                                              # saccades
+    lx = [rows[i + 1][0] - rows[i][0] for i in range(n)]
+    ly = [rows[i + 1][1] - rows[i][1] for i in range(n)]
+    rho = [math.sqrt(lx[i] * lx[i] + ly[i] * ly[i]) for i in range(n)]
+    drop = set()
+    i = 0
+    while i <= n - 2:
+        if kind == "direction":
+            cand = (lx[i] * lx[i + 1] + ly[i] * ly[i + 1]) > cosT * (rho[i] * rho[i + 1])
+        else:
+            cand = rho[i] < tamp
+        if cand and rows[i + 1][2] < tdur:
+            drop.add(i + 1)
+            i += 2
+        else:
+            i += 1
+    return [r for k, r in enumerate(rows) if k not in drop]
+
+
+def simplify_scanpath(fixation_vectors, TDir, TDur, TAmp):
+    """MultiMatch simplification of one scanpath on the host (the definition in the module docstring, in plain loops): float64
+    [k, 3] = the kept (x, y, duration) rows.  The checker of simplify_scanpaths."""
+    cosT, tdur, tamp = _thresholds(TDir, TDur, TAmp)
+    rows = [(float(r[0]), float(r[1]), float(r[2])) for r in _rows(fixation_vectors)]
+    while len(rows) >= 3:                                          # every round that continues deletes a fixation
+        before = len(rows)
+        if cosT < 1.0:
+            rows = _simplify_pass(rows, "direction", cosT, tdur, tamp)
+        rows = _simplify_pass(rows, "amplitude", cosT, tdur, tamp)
+        if len(rows) == before:
+            break
+    return np.array(rows, dtype=np.float64).reshape(-1, 3)
+
+
+def _similarities(p1, p2, screensize):
     M = np.sqrt((p1["lenx"][:, None] - p2["lenx"][None, :]) ** 2 + (p1["leny"][:, None] - p2["leny"][None, :]) ** 2)
     path = _alignment(M)
     vec, ang, ln, pos, dur = [], [], [], [], []
@@ -74,23 +151,113 @@ def docomparison(fixation_vectors1, fixation_vectors2, screensize, grouping=Fals
     return [1 - un[0] / (2 * diag), 1 - un[1] / math.pi, 1 - un[2] / diag, 1 - un[3] / diag, 1 - un[4]]
 
 
-def multimatch_pairs(scanpaths, pairs, screensize):
+def docomparison(fixation_vectors1, fixation_vectors2, screensize, grouping=False, TDir=0.0, TDur=0.0, TAmp=0.0):
+    if grouping:
+        _thresholds(TDir, TDur, TAmp)
+    if not (len(fixation_vectors1) >= 3 and len(fixation_vectors2) >= 3):
+        return [np.nan] * 5
+    if grouping:                        # the rule above looked at the ORIGINAL paths; a simplified one may be down to one saccade
+        fixation_vectors1 = simplify_scanpath(fixation_vectors1, TDir, TDur, TAmp)[:, :3]
+        fixation_vectors2 = simplify_scanpath(fixation_vectors2, TDir, TDur, TAmp)[:, :3]
+    return _similarities(_structure(fixation_vectors1), _structure(fixation_vectors2), screensize)
+
+
+def _upload(arrs, ncol, dev, pairs=None):
+    """ONE host buffer, one upload: fixations [total][ncol] | starts (int64) | counts (int32) | pairs (int32, optional).  Returns the
+    device buffer (keep it alive), the device addresses of its parts, and the host counts and starts."""
+    import torch
+    counts = np.array([a.shape[0] for a in arrs], dtype=np.int32)
+    start = np.cumsum(counts, dtype=np.int64) - counts
+    cat = np.concatenate([a for a in arrs if a.shape[0]] or [np.zeros((1, ncol))], 0)
+    parts = [np.ascontiguousarray(cat).view(np.uint8).reshape(-1), start.view(np.uint8), counts.view(np.uint8)]
+    if pairs is not None:
+        parts.append(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1).view(np.uint8))
+    off = np.cumsum([0] + [len(b) for b in parts])
+    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
+    return buf, [buf.data_ptr() + int(o) for o in off[:len(parts)]], counts, start
+
+
+def _checked_rows(scanpaths):
+    arrs = [_rows(a) for a in scanpaths]
+    ncol = max([a.shape[1] for a in arrs if a.shape[0]], default=3)
+    if any(a.shape[1] != ncol and a.shape[0] > 0 for a in arrs):
+        raise ValueError("scanpaths need the same number (>= 3) of columns")
+    arrs = [a if a.shape[0] else np.zeros((0, ncol)) for a in arrs]
+    longest = max([a.shape[0] for a in arrs], default=0)
+    if longest > MAX_FIXATIONS:
+        raise ValueError(f"scanpath of {longest} fixations exceeds the kernel limit {MAX_FIXATIONS}")
+    return arrs, ncol
+
+
+def simplify_scanpaths(scanpaths, *, TDir, TDur, TAmp):
+    """MultiMatch simplification of many scanpaths on the device (sp_scan_simplify, one wavefront per scanpath): one upload, one
+    launch and one copy back whatever their number.  scanpaths: list of fixation records or [n, >= 3] arrays (x, y, duration, ...;
+    further columns are not read), at most 64 fixations each.  Returns a list of float64 [k, 3] arrays, equal bit for bit to
+    simplify_scanpath of each.  Bad thresholds and too long scanpaths are refused before the device or the library is touched; an
+    empty list touches neither."""
+    cosT, tdur, tamp = _thresholds(TDir, TDur, TAmp)
+    arrs, ncol = _checked_rows(scanpaths)
+    if not arrs:
+        return []
+    import torch
+
+    from ... import hip
+    from ...hip import check
+    L = hip.lib()
+    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
+        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    buf, (fix_p, start_p, count_p), counts, start = _upload(arrs, ncol, dev)
+    total = max(int(counts.sum()), 1)
+    out = torch.empty(total * 3 + (len(arrs) + 1) // 2, dtype=torch.float64, device=dev)      # rows | new counts (int32) behind them
+    cnt_p = out.data_ptr() + 8 * total * 3
+    check(L.sp_scan_simplify(fix_p, ncol, start_p, count_p, len(arrs), cosT, tdur, tamp, out.data_ptr(), cnt_p, hip.stream()),
+          "sp_scan_simplify")
+    host = out.cpu().numpy()             # the one copy back (synchronises: buf and out outlive the launch)
+    rows = host[:total * 3].reshape(total, 3)
+    kept = host[total * 3:].view(np.int32)[:len(arrs)]
+    return [rows[s:s + k].copy() for s, k in zip(start, kept)]
+
+
+def multimatch_pairs(scanpaths, pairs, screensize, grouping=False, TDir=0.0, TDur=0.0, TAmp=0.0):
     """MultiMatch of many pairs on the device.  scanpaths: list of fixation records / arrays (x, y, duration); pairs: [npairs, 2]
     indices into scanpaths (first, second argument of docomparison); screensize [width, height].  Returns float64 [npairs, 5]
-    (numpy), five NaNs for a pair with a scanpath of fewer than 3 fixations."""
+    (numpy), five NaNs for a pair with a scanpath of fewer than 3 fixations.
+    grouping: the scanpaths are simplified on the device first (sp_scan_simplify with TDir, TDur, TAmp) and the simplified buffer is
+    scored in place by sp_scan_multimatch_gated with the original counts as the gate: no round trip through the host in between.
+    Bad thresholds, a scanpath of more than 64 fixations and a pair index out of range are refused before the device or the library
+    is touched; an empty pair list returns an empty array."""
+    if grouping:
+        cosT, tdur, tamp = _thresholds(TDir, TDur, TAmp)
+    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    arrs = [np.array([list(_) for _ in list(a)], dtype=np.float64).reshape(-1, 3) for a in scanpaths]
+    counts = [a.shape[0] for a in arrs]
+    if max(counts, default=0) > MAX_FIXATIONS:
+        raise ValueError(f"scanpath of {max(counts)} fixations exceeds the kernel limit {MAX_FIXATIONS}")
+    if pr.size and (pr.min() < 0 or pr.max() >= len(arrs)):
+        raise ValueError(f"pair index out of range: {len(arrs)} scanpaths, indices {pr.min()} .. {pr.max()}")
+    pr = pr.astype(np.int32)
+    if pr.shape[0] == 0:
+        return np.zeros((0, 5))
     import torch
 
     from ... import hip
     from ...hip import check, ptr
-    pr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-    if pr.shape[0] == 0:
-        return np.zeros((0, 5))
     L = hip.lib()
     dev = torch.device("cuda", torch.cuda.current_device())
-    arrs = [np.array([list(_) for _ in list(a)], dtype=np.float64).reshape(-1, 3) for a in scanpaths]
-    counts = [a.shape[0] for a in arrs]
-    if max(counts) > L.sp_scan_max_fixations():
-        raise ValueError(f"scanpath of {max(counts)} fixations exceeds the kernel limit {L.sp_scan_max_fixations()}")
+    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
+        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
+    if grouping:
+        buf, (fix_p, start_p, count_p, pairs_p), _, _ = _upload(arrs, 3, dev, pairs=pr)
+        total = max(sum(counts), 1)
+        work = torch.empty(total * 3 + (len(arrs) + 1) // 2 + pr.shape[0] * 5, dtype=torch.float64, device=dev)
+        out_p = work.data_ptr() + 8 * (total * 3 + (len(arrs) + 1) // 2)     # simplified rows | their counts (int32) | the scores
+        kept_p = work.data_ptr() + 8 * total * 3
+        check(L.sp_scan_simplify(fix_p, 3, start_p, count_p, len(arrs), cosT, tdur, tamp, work.data_ptr(), kept_p, hip.stream()),
+              "sp_scan_simplify")
+        check(L.sp_scan_multimatch_gated(work.data_ptr(), 3, start_p, kept_p, count_p, pairs_p, pr.shape[0], float(screensize[0]),
+                                         float(screensize[1]), out_p, hip.stream()), "sp_scan_multimatch_gated")
+        return work[total * 3 + (len(arrs) + 1) // 2:].cpu().numpy().reshape(-1, 5)      # synchronises: buf and work outlive the launches
     count = torch.tensor(counts, dtype=torch.int32)
     start = (torch.cumsum(count.to(torch.int64), 0) - count.to(torch.int64)).to(dev)
     cat = np.concatenate(arrs, 0) if sum(counts) else np.zeros((1, 3))

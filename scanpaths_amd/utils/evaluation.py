@@ -116,6 +116,9 @@ def gtpairs_eval_scanmatch_performance_related(gt_fix_vectors, ScanMatchwithDura
 # means / stds and the "best SED / STDE" columns are assembled exactly as the reference does.
 # MultiMatch: ``multimatch`` = a callable docomparison(fv1, fv2, screensize=[320, 240]) -> 5 values.  Default: the installed
 # multimatch_gaze if importable, else utils/evaltools/multimatch.py (a restatement of the published algorithm, parity unpinned).
+# ``multimatch_grouping`` (keyword only; None = the reference's call, no simplification) = (TDir degrees, TDur, TAmp pixels): MultiMatch's
+# scanpath simplification first -- the device default simplifies and scores every pair of the call on the device, a
+# callable is called with grouping=True, TDir=, TDur=, TAmp= (multimatch_gaze's own signature).
 # Quirk kept: the dict entry "w/o duration" holds column 5 = the score WITH duration and vice versa (:292-293 append the
 # with-duration score first, :323-324 label them the other way round).
 # ====================================================================================================================
@@ -129,18 +132,37 @@ def _default_multimatch():
         return None
 
 
-def _multimatch_rows(mm, candidates):
+def _grouping_kwargs(multimatch_grouping):
+    """None -> None; a (TDir, TDur, TAmp) triple -> the keyword arguments of docomparison / multimatch_pairs (checked here, before
+    any scoring)"""
+    if multimatch_grouping is None:
+        return None
+    from .evaltools.multimatch import _thresholds
+    try:
+        tdir, tdur, tamp = multimatch_grouping
+    except (TypeError, ValueError):
+        raise ValueError(f"multimatch_grouping is None or a (TDir, TDur, TAmp) triple: {multimatch_grouping!r}") from None
+    _thresholds(tdir, tdur, tamp)
+    return {"grouping": True, "TDir": float(tdir), "TDur": float(tdur), "TAmp": float(tamp)}
+
+
+def _multimatch_rows(mm, candidates, grouping=None):
     """candidates: list of (fixation vectors 1, fixation vectors 2) -> list of 5-value rows (NaNs where MultiMatch cannot score).
-    mm None: one device launch for all candidates; else the per-pair callable (the reference's loop)."""
+    mm None: one device launch for all candidates; else the per-pair callable (the reference's loop).  grouping: None or the
+    keyword arguments of _grouping_kwargs."""
     if not candidates:
         return []
     if mm is not None:
+        if grouping is not None:
+            return [list(mm(a, b, screensize=[320, 240], **grouping)) for a, b in candidates]
         return [list(mm(a, b, screensize=[320, 240])) for a, b in candidates]
     from .evaltools.multimatch import multimatch_pairs
     paths, pairs = [], []
     for a, b in candidates:
         paths.extend([a, b])
         pairs.append((len(paths) - 2, len(paths) - 1))
+    if grouping is not None:
+        return [list(r) for r in multimatch_pairs(paths, pairs, [320, 240], **grouping)]
     return [list(r) for r in multimatch_pairs(paths, pairs, [320, 240])]
 
 
@@ -188,13 +210,14 @@ def _make_scanmatch():
 
 
 def evaluation_performance_related(gt_fix_vectors, predict_fix_vectors, all_performances, all_allocated_performances,
-                                   multimatch=None):
+                                   multimatch=None, *, multimatch_grouping=None):
     """(utils/evaluation.py:188-359)  -> cur_metrics, cur_metrics_std, scores_of_each_images"""
     mm = multimatch or _default_multimatch()
+    grouping = _grouping_kwargs(multimatch_grouping)
     sm_wd, sm_wod = _make_scanmatch()
     cand = [(gt_fix_vectors[index][inner], predict_fix_vectors[index], index, inner)
             for index in range(len(gt_fix_vectors)) for inner in range(len(gt_fix_vectors[index]))]
-    mm_all = _multimatch_rows(mm, [(a, b) for a, b, _, _ in cand])
+    mm_all = _multimatch_rows(mm, [(a, b) for a, b, _, _ in cand], grouping)
     paths, pairs, mm_rows, owner = [], [], [], []
     pred_slot = {}
     for (gt, pred, index, inner_index), rlt in zip(cand, mm_all):
@@ -230,10 +253,11 @@ def evaluation_performance_related(gt_fix_vectors, predict_fix_vectors, all_perf
     return cur_metrics, cur_metrics_std, scores_of_each_images
 
 
-def human_evaluation(dataloader, multimatch=None):
+def human_evaluation(dataloader, multimatch=None, *, multimatch_grouping=None):
     """(utils/evaluation.py:11-186)  every ordered pair of distinct human scanpaths of an image; dataloader yields batches with
     "fix_vectors", "performances", "question_ids"  -> human_metrics, human_metrics_std, scores_of_each_images_dict"""
     mm = multimatch or _default_multimatch()
+    grouping = _grouping_kwargs(multimatch_grouping)
     sm_wd, sm_wod = _make_scanmatch()
     paths, images, gt_qid_name, cand = [], [], [], []
     for batch in dataloader:
@@ -248,7 +272,7 @@ def human_evaluation(dataloader, multimatch=None):
                 for index_2 in range(len(fix_vectors)):
                     if index_2 != index_1:
                         cand.append((fix_vectors[index_1], fix_vectors[index_2], base + index_1, base + index_2, (img, index_1, index_2)))
-    mm_all = _multimatch_rows(mm, [(a, b) for a, b, _, _, _ in cand])
+    mm_all = _multimatch_rows(mm, [(a, b) for a, b, _, _, _ in cand], grouping)
     pairs, mm_rows, owner = [], [], []
     for (_, _, p1, p2, own), rlt in zip(cand, mm_all):
         if np.any(np.isnan(np.asarray(rlt, dtype=np.float64))):
@@ -311,11 +335,12 @@ def _score_all(paths, pairs, mm_rows, sm_wd=None, sm_wod=None):
     return _rows_for_pairs(paths, pairs, sm_wd, sm_wod, mm_rows)
 
 
-def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, multimatch=None):
+def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, multimatch=None, *, multimatch_grouping=None):
     """(OSIE/utils/evaluation.py:151-282, COCO_Search18/utils/evaluation.py:180-311) -> cur_metrics, cur_metrics_std, scores_of_each_images.
     Every (human scanpath of the image, prediction) pair; like the reference, SED / STDE are regrouped as [-1, number of human
     scanpaths of the LAST image] for the "best" columns (equal counts per image expected)."""
     mm = multimatch or _default_multimatch()
+    grouping = _grouping_kwargs(multimatch_grouping)
     paths, pairs, cand, per_image = [], [], [], []
     for index in range(len(gt_fix_vectors)):
         pi = len(paths)
@@ -325,7 +350,7 @@ def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, mul
             paths.append(_as_ms(inner))
             pairs.append((len(paths) - 1, pi))
             cand.append((inner, predict_fix_vectors[index]))
-    mm_rows = _multimatch_rows(mm, cand)
+    mm_rows = _multimatch_rows(mm, cand, grouping)
     rows = _score_all(paths, pairs, mm_rows)
     scores_of_each_images, k = [], 0
     for n in per_image:
@@ -340,11 +365,12 @@ def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, mul
     return mean, std, scores_of_each_images
 
 
-def human_evaluation_free_viewing(dataloader, task="OSIE", multimatch=None):
+def human_evaluation_free_viewing(dataloader, task="OSIE", multimatch=None, *, multimatch_grouping=None):
     """human_evaluation of OSIE (:11-148) / COCO_Search18 (:11-178): every ordered pair of distinct human scanpaths of an image;
     batches carry "fix_vectors" and "img_names" -> human_metrics, human_metrics_std, {image name: mean score row of the image}"""
     assert task in ("OSIE", "COCO_Search18"), task
     mm = multimatch or _default_multimatch()
+    grouping = _grouping_kwargs(multimatch_grouping)
     paths, pairs, cand, names, groups = [], [], [], [], []       # groups: per image, per first scanpath: number of pairs (n - 1)
     for batch in dataloader:
         names.extend(batch["img_names"])
@@ -359,7 +385,7 @@ def human_evaluation_free_viewing(dataloader, task="OSIE", multimatch=None):
                     if i2 != i1:
                         pairs.append((base + i1, base + i2))
                         cand.append((fix_vectors[i1], fix_vectors[i2]))
-    rows = _score_all(paths, pairs, _multimatch_rows(mm, cand))
+    rows = _score_all(paths, pairs, _multimatch_rows(mm, cand, grouping))
     scores, k = [], 0
     for n in groups:
         cnt = n * (n - 1)
