@@ -37,6 +37,11 @@ import math
 
 import numpy as np
 
+from ... import hip
+from ...hip import check
+from . import _batch
+from ._batch import MAX_FIXATIONS  # noqa: F401  (re-exported; one lane per fixation in sp_scan_simplify)
+
 
 def _structure(data):
     a = np.array([list(_) for _ in list(data)], dtype=np.float64).reshape(-1, 3)
@@ -68,9 +73,6 @@ def _alignment(M):
         i, j = path[-1]
         path.append((int(prev[i, j, 0]), int(prev[i, j, 1])))
     return path[::-1]
-
-
-MAX_FIXATIONS = 64      # = sp_scan_max_fixations(): one lane per fixation in sp_scan_simplify
 
 
 def _rows(data):
@@ -162,31 +164,12 @@ def docomparison(fixation_vectors1, fixation_vectors2, screensize, grouping=Fals
     return _similarities(_structure(fixation_vectors1), _structure(fixation_vectors2), screensize)
 
 
-def _upload(arrs, ncol, dev, pairs=None):
-    """ONE host buffer, one upload: fixations [total][ncol] | starts (int64) | counts (int32) | pairs (int32, optional).  Returns the
-    device buffer (keep it alive), the device addresses of its parts, and the host counts and starts."""
-    import torch
-    counts = np.array([a.shape[0] for a in arrs], dtype=np.int32)
-    start = np.cumsum(counts, dtype=np.int64) - counts
-    cat = np.concatenate([a for a in arrs if a.shape[0]] or [np.zeros((1, ncol))], 0)
-    parts = [np.ascontiguousarray(cat).view(np.uint8).reshape(-1), start.view(np.uint8), counts.view(np.uint8)]
-    if pairs is not None:
-        parts.append(np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1).view(np.uint8))
-    off = np.cumsum([0] + [len(b) for b in parts])
-    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
-    return buf, [buf.data_ptr() + int(o) for o in off[:len(parts)]], counts, start
-
-
-def _checked_rows(scanpaths):
-    arrs = [_rows(a) for a in scanpaths]
-    ncol = max([a.shape[1] for a in arrs if a.shape[0]], default=3)
-    if any(a.shape[1] != ncol and a.shape[0] > 0 for a in arrs):
-        raise ValueError("scanpaths need the same number (>= 3) of columns")
-    arrs = [a if a.shape[0] else np.zeros((0, ncol)) for a in arrs]
-    longest = max([a.shape[0] for a in arrs], default=0)
-    if longest > MAX_FIXATIONS:
-        raise ValueError(f"scanpath of {longest} fixations exceeds the kernel limit {MAX_FIXATIONS}")
-    return arrs, ncol
+def _on_device(batch, **more):
+    """after the refusals: (device, library with its limits checked, the one upload: buffer and {name: address})"""
+    L = hip.lib()
+    _batch.check_limits(L)
+    dev = _batch.device("MultiMatch runs")
+    return (dev, L) + _batch.upload(batch.sections(**more), dev)
 
 
 def simplify_scanpaths(scanpaths, *, TDir, TDur, TAmp):
@@ -196,27 +179,17 @@ def simplify_scanpaths(scanpaths, *, TDir, TDur, TAmp):
     simplify_scanpath of each.  Bad thresholds and too long scanpaths are refused before the device or the library is touched; an
     empty list touches neither."""
     cosT, tdur, tamp = _thresholds(TDir, TDur, TAmp)
-    arrs, ncol = _checked_rows(scanpaths)
-    if not arrs:
+    b = _batch.pack([_rows(a) for a in scanpaths], min_cols=3)
+    K = len(b.counts)
+    if not K:
         return []
-    import torch
-
-    from ... import hip
-    from ...hip import check
-    L = hip.lib()
-    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
-        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    buf, (fix_p, start_p, count_p), counts, start = _upload(arrs, ncol, dev)
-    total = max(int(counts.sum()), 1)
-    out = torch.empty(total * 3 + (len(arrs) + 1) // 2, dtype=torch.float64, device=dev)      # rows | new counts (int32) behind them
-    cnt_p = out.data_ptr() + 8 * total * 3
-    check(L.sp_scan_simplify(fix_p, ncol, start_p, count_p, len(arrs), cosT, tdur, tamp, out.data_ptr(), cnt_p, hip.stream()),
-          "sp_scan_simplify")
-    host = out.cpu().numpy()             # the one copy back (synchronises: buf and out outlive the launch)
-    rows = host[:total * 3].reshape(total, 3)
-    kept = host[total * 3:].view(np.int32)[:len(arrs)]
-    return [rows[s:s + k].copy() for s, k in zip(start, kept)]
+    dev, L, buf, at = _on_device(b)
+    out = _batch.Out({"rows": (np.float64, 3 * len(b.rows)), "kept": (np.int32, K)}, dev)
+    check(L.sp_scan_simplify(at["rows"], b.ncol, at["starts"], at["counts"], K, cosT, tdur, tamp, out.ptr("rows"), out.ptr("kept"),
+                             hip.stream()), "sp_scan_simplify")
+    host = out.host()
+    rows = host["rows"].reshape(-1, 3)
+    return [rows[s:s + k].copy() for s, k in zip(b.starts, host["kept"])]
 
 
 def multimatch_pairs(scanpaths, pairs, screensize, grouping=False, TDir=0.0, TDur=0.0, TAmp=0.0):
@@ -226,45 +199,25 @@ def multimatch_pairs(scanpaths, pairs, screensize, grouping=False, TDir=0.0, TDu
     grouping: the scanpaths are simplified on the device first (sp_scan_simplify with TDir, TDur, TAmp) and the simplified buffer is
     scored in place by sp_scan_multimatch_gated with the original counts as the gate: no round trip through the host in between.
     Bad thresholds, a scanpath of more than 64 fixations and a pair index out of range are refused before the device or the library
-    is touched; an empty pair list returns an empty array."""
+    is touched; an empty pair list returns an empty array.  One upload and one copy back (the scores) either way."""
     if grouping:
         cosT, tdur, tamp = _thresholds(TDir, TDur, TAmp)
-    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    arrs = [np.array([list(_) for _ in list(a)], dtype=np.float64).reshape(-1, 3) for a in scanpaths]
-    counts = [a.shape[0] for a in arrs]
-    if max(counts, default=0) > MAX_FIXATIONS:
-        raise ValueError(f"scanpath of {max(counts)} fixations exceeds the kernel limit {MAX_FIXATIONS}")
-    if pr.size and (pr.min() < 0 or pr.max() >= len(arrs)):
-        raise ValueError(f"pair index out of range: {len(arrs)} scanpaths, indices {pr.min()} .. {pr.max()}")
-    pr = pr.astype(np.int32)
-    if pr.shape[0] == 0:
+    b = _batch.pack([np.array([list(_) for _ in list(a)], dtype=np.float64).reshape(-1, 3) for a in scanpaths], min_cols=3)
+    pr = _batch.check_pairs(pairs, len(b.counts))
+    if len(pr) == 0:
         return np.zeros((0, 5))
-    import torch
-
-    from ... import hip
-    from ...hip import check, ptr
-    L = hip.lib()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
-        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
+    dev, L, buf, at = _on_device(b, pairs=pr)
+    sections = {"scores": (np.float64, 5 * len(pr))}
+    if grouping:                                          # the simplified rows and their counts stay on the device
+        sections.update(rows=(np.float64, 3 * len(b.rows)), kept=(np.int32, len(b.counts)))
+    out = _batch.Out(sections, dev)
+    size = (float(screensize[0]), float(screensize[1]))
     if grouping:
-        buf, (fix_p, start_p, count_p, pairs_p), _, _ = _upload(arrs, 3, dev, pairs=pr)
-        total = max(sum(counts), 1)
-        work = torch.empty(total * 3 + (len(arrs) + 1) // 2 + pr.shape[0] * 5, dtype=torch.float64, device=dev)
-        out_p = work.data_ptr() + 8 * (total * 3 + (len(arrs) + 1) // 2)     # simplified rows | their counts (int32) | the scores
-        kept_p = work.data_ptr() + 8 * total * 3
-        check(L.sp_scan_simplify(fix_p, 3, start_p, count_p, len(arrs), cosT, tdur, tamp, work.data_ptr(), kept_p, hip.stream()),
-              "sp_scan_simplify")
-        check(L.sp_scan_multimatch_gated(work.data_ptr(), 3, start_p, kept_p, count_p, pairs_p, pr.shape[0], float(screensize[0]),
-                                         float(screensize[1]), out_p, hip.stream()), "sp_scan_multimatch_gated")
-        return work[total * 3 + (len(arrs) + 1) // 2:].cpu().numpy().reshape(-1, 5)      # synchronises: buf and work outlive the launches
-    count = torch.tensor(counts, dtype=torch.int32)
-    start = (torch.cumsum(count.to(torch.int64), 0) - count.to(torch.int64)).to(dev)
-    cat = np.concatenate(arrs, 0) if sum(counts) else np.zeros((1, 3))
-    fix = torch.from_numpy(np.ascontiguousarray(cat)).to(dev)
-    prd = torch.from_numpy(np.ascontiguousarray(pr)).to(dev)
-    count_d = count.to(dev)
-    out = torch.empty((pr.shape[0], 5), dtype=torch.float64, device=dev)
-    check(L.sp_scan_multimatch(ptr(fix), 3, ptr(start), ptr(count_d), ptr(prd), pr.shape[0], float(screensize[0]), float(screensize[1]),
-                               ptr(out), hip.stream()), "sp_scan_multimatch")
-    return out.cpu().numpy()
+        check(L.sp_scan_simplify(at["rows"], 3, at["starts"], at["counts"], len(b.counts), cosT, tdur, tamp, out.ptr("rows"),
+                                 out.ptr("kept"), hip.stream()), "sp_scan_simplify")
+        check(L.sp_scan_multimatch_gated(out.ptr("rows"), 3, at["starts"], out.ptr("kept"), at["counts"], at["pairs"], len(pr), *size,
+                                         out.ptr("scores"), hip.stream()), "sp_scan_multimatch_gated")
+    else:
+        check(L.sp_scan_multimatch(at["rows"], 3, at["starts"], at["counts"], at["pairs"], len(pr), *size, out.ptr("scores"),
+                                   hip.stream()), "sp_scan_multimatch")
+    return out.host("scores")["scores"].reshape(-1, 5)

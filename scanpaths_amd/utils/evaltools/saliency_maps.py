@@ -18,6 +18,7 @@ import torch
 
 from ... import hip
 from ...hip import check, ptr
+from . import _batch
 
 WEIGHTS = {"binary": 0, "count": 1, "duration": 2}
 MODES = {"constant": 0, "reflect": 1, "nearest": 2}
@@ -26,9 +27,7 @@ _FIELDS = ("start_x", "start_y", "duration")
 
 
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise hip.HipError("scanpaths_amd fixation / density maps run on a HIP device only (no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _batch.device("fixation / density maps run")
 
 
 def _rows(sp) -> np.ndarray:
@@ -48,29 +47,22 @@ def _rows(sp) -> np.ndarray:
 
 
 class _Upload:
-    """the concatenated fixations of a list of scanpaths on the device (ONE copy of the fixations) with their start / count / group"""
+    """the concatenated fixations of a list of scanpaths with their start / count / group in one buffer on the device (ONE upload):
+    fix, start, count and group are the device addresses of its sections, valid while the object lives"""
 
     def __init__(self, scanpaths: Sequence, groups, num_groups: Optional[int], dev):
-        arrs = [_rows(s) for s in scanpaths]
         grp = np.asarray(list(groups), dtype=np.int64).reshape(-1)
-        if len(arrs) != grp.shape[0]:
-            raise ValueError(f"{len(arrs)} scanpaths but {grp.shape[0]} groups")
+        if len(scanpaths) != grp.shape[0]:
+            raise ValueError(f"{len(scanpaths)} scanpaths but {grp.shape[0]} groups")
         if grp.size and grp.min() < 0:
             raise ValueError("negative group index")
         self.G = int(num_groups) if num_groups is not None else (int(grp.max()) + 1 if grp.size else 0)
         if grp.size and grp.max() >= self.G:
             raise ValueError(f"group index {int(grp.max())} with num_groups = {self.G}")
-        widths = {a.shape[1] for a in arrs if a.shape[0]}
-        if len(widths) > 1:
-            raise ValueError(f"scanpaths need the same number (>= 2) of columns, got {sorted(widths)}")
-        self.ncol = widths.pop() if widths else 2
-        self.K = len(arrs)
-        counts = np.array([a.shape[0] for a in arrs], dtype=np.int64)
-        cat = np.concatenate([a for a in arrs if a.shape[0]], 0) if counts.sum() else np.zeros((1, self.ncol))
-        self.fix = torch.from_numpy(np.ascontiguousarray(cat)).to(dev)
-        self.start = torch.from_numpy(np.cumsum(counts) - counts).to(dev)
-        self.count = torch.from_numpy(counts.astype(np.int32)).to(dev)
-        self.group = torch.from_numpy(grp.astype(np.int32)).to(dev)
+        b = _batch.pack([_rows(s) for s in scanpaths], min_cols=2, limit=None)
+        self.ncol, self.K = b.ncol, len(b.counts)
+        self._buf, at = _batch.upload(b.sections(group=grp.astype(np.int32)), dev)
+        self.fix, self.start, self.count, self.group = at["rows"], at["starts"], at["counts"], at["group"]
 
     def rasterise(self, frame_size, output_shape, weight: str, K: Optional[int] = None, G: Optional[int] = None):
         """maps [G,H,W], dropped [G] of the first K scanpaths (all by default)"""
@@ -84,12 +76,12 @@ class _Upload:
             raise ValueError(f"frame_size {tuple(frame_size)} / output_shape {(H, W)}: positive sizes are required")
         K = self.K if K is None else K
         G = self.G if G is None else G
-        dev = self.fix.device
+        dev = self._buf.device
         maps = torch.empty((G, H, W), dtype=torch.float64, device=dev)
         dropped = torch.empty(G, dtype=torch.int32, device=dev)
         if G:
-            check(hip.lib().sp_fixation_maps(ptr(self.fix), self.ncol, ptr(self.start), ptr(self.count), ptr(self.group), K, G, H, W, fw,
-                                             fh, WEIGHTS[weight], ptr(maps), ptr(dropped), hip.stream()), "sp_fixation_maps")
+            check(hip.lib().sp_fixation_maps(self.fix, self.ncol, self.start, self.count, self.group, K, G, H, W, fw, fh,
+                                             WEIGHTS[weight], ptr(maps), ptr(dropped), hip.stream()), "sp_fixation_maps")
         return maps, dropped
 
 

@@ -21,6 +21,7 @@ import torch
 
 from ... import hip
 from ...hip import check, ptr
+from . import _batch
 
 
 MAX_SYMBOLS = 1 << 18      # hard cap per sequence (3.6 h of fixation at TempBin = 50 ms): bounds the symbol / scratch buffers
@@ -44,9 +45,7 @@ class ScanMatch(object):
             if k not in ("Xres", "Yres", "Xbin", "Ybin", "Threshold", "GapValue", "TempBin", "Offset"):
                 raise ValueError('Unknown parameter: %s.' % k)
             setattr(self, k, v)
-        if not torch.cuda.is_available():
-            raise hip.HipError("scanpaths_amd ScanMatch runs on a HIP device only (no CPU path)")
-        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _batch.device("ScanMatch runs")
         self._mask_dev: Optional[torch.Tensor] = None      # custom mask (maskFromArray); None -> arithmetic grid
         self.CreateSubMatrix()
         self.GridMask()
@@ -79,8 +78,9 @@ class ScanMatch(object):
         saved = self.Offset, self.TempBin
         self.Offset, self.TempBin = (0, 0), 0.0
         try:
-            seq, _ = self._sequences_dev(pix.to(self.device), torch.arange(pix.shape[0], device=self.device),
-                                         torch.ones(pix.shape[0], dtype=torch.int32, device=self.device), ld=1)
+            pix, start = pix.to(self.device), torch.arange(pix.shape[0], device=self.device)
+            count = torch.ones(pix.shape[0], dtype=torch.int32, device=self.device)
+            seq, _ = self._sequences_dev(ptr(pix), 2, ptr(start), ptr(count), pix.shape[0], ld=1)
         finally:
             self.Offset, self.TempBin = saved
         return seq.view(self.Yres, self.Xres).cpu().numpy().astype(np.float64)
@@ -96,41 +96,31 @@ class ScanMatch(object):
         self.SubMarix = array
 
     # ---- fixations -> symbol strings ---------------------------------------------------------------------------
-    def _sequences_dev(self, fix: torch.Tensor, start: torch.Tensor, count: torch.Tensor, ld: Optional[int] = None
+    def _sequences_dev(self, fix: int, ncol: int, start: int, count: int, nsp: int, ld: Optional[int] = None
                        ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """fix (float64 [total, ncol]), start (int64 [nsp]), count (int32 [nsp]): device addresses the caller keeps alive"""
         L = hip.lib()
-        fix = fix.to(self.device, torch.float64).contiguous()
-        start = start.to(self.device, torch.int64).contiguous()
-        count = count.to(self.device, torch.int32).contiguous()
-        nsp, ncol = int(count.numel()), int(fix.shape[1])
         lens = torch.empty(nsp, dtype=torch.int32, device=self.device)
         args = (int(self.Xres), int(self.Yres), int(self.Xbin), int(self.Ybin), float(self.Offset[0]), float(self.Offset[1]),
                 float(self.TempBin), ptr(self._mask_dev))
         if ld is None:                              # sizing pass (one host sync, as the reference's python lists)
-            check(L.sp_scanmatch_sequences(ptr(fix), ncol, ptr(start), ptr(count), nsp, *args, 0, None, ptr(lens), hip.stream()),
+            check(L.sp_scanmatch_sequences(fix, ncol, start, count, nsp, *args, 0, None, ptr(lens), hip.stream()),
                   "sp_scanmatch_sequences")
             ld = max(1, int(lens.max().item()))
         if ld > MAX_SYMBOLS or ld < 0:      # longer than the LDS kernel's sp_scanmatch_max_len() is fine: match_pairs switches kernels
             raise SequenceTooLong(f"sequence of {ld} symbols exceeds the cap of {MAX_SYMBOLS}")
         seq = torch.zeros((nsp, ld), dtype=torch.int32, device=self.device)
-        check(L.sp_scanmatch_sequences(ptr(fix), ncol, ptr(start), ptr(count), nsp, *args, ld, ptr(seq), ptr(lens), hip.stream()),
+        check(L.sp_scanmatch_sequences(fix, ncol, start, count, nsp, *args, ld, ptr(seq), ptr(lens), hip.stream()),
               "sp_scanmatch_sequences")
         return seq, lens
 
     def sequences(self, scanpaths: Sequence[np.ndarray]) -> Tuple[torch.Tensor, torch.Tensor]:
         """list of [n_k, 2|3] fixation arrays -> (symbols int32 [n, ld] on the device, lengths int32 [n])"""
-        arrs = [np.asarray(a, dtype=np.float64).reshape(len(a), -1) for a in scanpaths]
-        ncol = arrs[0].shape[1] if arrs else 3
-        if any(a.shape[1] != ncol for a in arrs):
-            raise ValueError("all scanpaths need the same number of columns")
-        if self.TempBin != 0 and ncol < 3:
+        b = _batch.pack(scanpaths, min_cols=1, limit=None, allow_empty=False)
+        if self.TempBin != 0 and b.ncol < 3:
             raise IndexError("TempBin != 0 needs a duration column")          # the reference raises IndexError on d[:, 2]
-        count = torch.tensor([a.shape[0] for a in arrs], dtype=torch.int32)
-        start = torch.cumsum(count.to(torch.int64), 0) - count.to(torch.int64)
-        cat = np.concatenate(arrs, 0) if arrs else np.zeros((0, ncol))
-        if cat.shape[0] == 0:
-            cat = np.zeros((1, ncol))
-        return self._sequences_dev(torch.from_numpy(cat), start, count)
+        buf, at = _batch.upload(b.sections(), self.device)
+        return self._sequences_dev(at["rows"], b.ncol, at["starts"], at["counts"], len(b.counts))
 
     def fixationToSequence(self, data):
         data = np.asarray(data, dtype=np.float64)

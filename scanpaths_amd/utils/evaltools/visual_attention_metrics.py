@@ -25,40 +25,36 @@ import torch
 
 from ... import hip
 from ...hip import check, ptr
+from . import _batch
+from ._batch import MAX_FIXATIONS  # noqa: F401  (re-exported)
 
 
 def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise hip.HipError("scanpaths_amd scanpath metrics run on a HIP device only (no CPU path)")
-    return torch.device("cuda", torch.cuda.current_device())
+    return _batch.device("scanpath metrics run")
+
+
+def _on_device(batch, pairs):
+    """what a pairwise scorer needs once its refusals are over: (device, library with its limits checked, the one upload of the
+    scanpaths and pairs: buffer and {name: address})"""
+    dev = _device()
+    L = hip.lib()
+    _batch.check_limits(L)
+    return (dev, L) + _batch.upload(batch.sections(pairs=pairs), dev)
 
 
 def sed_stde_pairs(scanpaths: Sequence[np.ndarray], pairs, image_shape, n: int = 5, want_sed: bool = True, want_stde: bool = True
                    ) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
-    """scanpaths: list of [n_k, >=2] arrays (x, y, ...); pairs: int [npairs, 2] = (human index, simulated index);
-    image_shape: shape of the stimulus (height, width[, channels]).  Returns (sed int32 [npairs], stde float64 [npairs])."""
-    dev = _device()
-    L = hip.lib()
-    arrs = [np.asarray(a, dtype=np.float64).reshape(len(a), -1) for a in scanpaths]
-    ncol = arrs[0].shape[1]
-    if any(a.shape[1] != ncol for a in arrs) or ncol < 2:
-        raise ValueError("scanpaths need the same number (>= 2) of columns")
-    counts = [a.shape[0] for a in arrs]
-    if max(counts) > L.sp_scan_max_fixations():
-        raise ValueError(f"scanpath of {max(counts)} fixations exceeds the kernel limit {L.sp_scan_max_fixations()}")
-    count = torch.tensor(counts, dtype=torch.int32)
-    start = (torch.cumsum(count.to(torch.int64), 0) - count.to(torch.int64)).to(dev)
-    cat = np.concatenate(arrs, 0)
-    if cat.shape[0] == 0:
-        cat = np.zeros((1, ncol))
-    fix = torch.from_numpy(cat).to(dev)
-    pr = torch.as_tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev).contiguous()
-    npairs = pr.shape[0]
+    """scanpaths: list of [n_k, >=2] arrays (x, y, ...), empty ones allowed; pairs: int [npairs, 2] = (human index, simulated index);
+    image_shape: shape of the stimulus (height, width[, channels]).  Returns (sed int32 [npairs], stde float64 [npairs]); with an
+    empty scanpath SED is the other one's length and STDE is NaN."""
+    b = _batch.pack(scanpaths, min_cols=2)
+    pr = _batch.check_pairs(pairs, len(b.counts))
+    npairs = len(pr)
+    dev, L, buf, at = _on_device(b, pr)
     sed = torch.empty(npairs, dtype=torch.int32, device=dev) if want_sed else None
     stde = torch.empty(npairs, dtype=torch.float64, device=dev) if want_stde else None
-    count_d = count.to(dev)          # named: must outlive the launch
     if npairs:
-        check(L.sp_scan_sed_stde(ptr(fix), ncol, ptr(start), ptr(count_d), ptr(pr), npairs, int(image_shape[0]),
+        check(L.sp_scan_sed_stde(at["rows"], b.ncol, at["starts"], at["counts"], at["pairs"], npairs, int(image_shape[0]),
                                  int(image_shape[1]), int(n), float(max(image_shape)), ptr(sed), ptr(stde), hip.stream()),
               "sp_scan_sed_stde")
     return sed, stde
@@ -387,33 +383,17 @@ def tde_pairs(scanpaths: Sequence[np.ndarray], pairs, k: int = 0, distance_mode:
     """scanpaths / pairs as for sed_stde_pairs.  k >= 1: time_delay_embedding_distance(human / max_dim, simulated / max_dim, k,
     distance_mode); k == 0: the scaled distance over every k.  Returns (tde float64 [npairs], euclidean float64 [npairs] or None); NaN
     where the reference returns False / None."""
-    dev = _device()
-    L = hip.lib()
     if distance_mode not in ('Mean', 'Hausdorff'):
         raise ValueError(f"distance_mode {distance_mode!r}")
-    arrs = [np.asarray(a, dtype=np.float64) for a in scanpaths]
-    arrs = [a.reshape(len(a), -1) if len(a) else np.zeros((0, a.shape[-1] if a.ndim == 2 else 2)) for a in arrs]
-    ncol = max(a.shape[1] for a in arrs)
-    if any(a.shape[1] != ncol and a.shape[0] > 0 for a in arrs) or ncol < 2:
-        raise ValueError("scanpaths need the same number (>= 2) of columns")
-    arrs = [a if a.shape[0] else np.zeros((0, ncol)) for a in arrs]
-    counts = [a.shape[0] for a in arrs]
-    if max(counts) > L.sp_scan_max_fixations():
-        raise ValueError(f"scanpath of {max(counts)} fixations exceeds the kernel limit {L.sp_scan_max_fixations()}")
-    count = torch.tensor(counts, dtype=torch.int32)
-    start = (torch.cumsum(count.to(torch.int64), 0) - count.to(torch.int64)).to(dev)
-    cat = np.concatenate(arrs, 0)
-    if cat.shape[0] == 0:
-        cat = np.zeros((1, ncol))
-    fix = torch.from_numpy(cat).to(dev)
-    pr = torch.as_tensor(pairs, dtype=torch.int32).reshape(-1, 2).to(dev).contiguous()
-    npairs = pr.shape[0]
+    b = _batch.pack(scanpaths, min_cols=2)
+    pr = _batch.check_pairs(pairs, len(b.counts))
+    npairs = len(pr)
+    dev, L, buf, at = _on_device(b, pr)
     tde = torch.empty(npairs, dtype=torch.float64, device=dev)
     eucl = torch.empty(npairs, dtype=torch.float64, device=dev) if want_euclidean else None
-    count_d = count.to(dev)          # named: must outlive the launch
     if npairs:
-        check(L.sp_scan_tde(ptr(fix), ncol, ptr(start), ptr(count_d), ptr(pr), npairs, int(k), int(distance_mode == 'Hausdorff'),
-                            float(max_dim), ptr(tde), ptr(eucl), hip.stream()), "sp_scan_tde")
+        check(L.sp_scan_tde(at["rows"], b.ncol, at["starts"], at["counts"], at["pairs"], npairs, int(k),
+                            int(distance_mode == 'Hausdorff'), float(max_dim), ptr(tde), ptr(eucl), hip.stream()), "sp_scan_tde")
     return tde, eucl
 
 
@@ -453,7 +433,6 @@ def scaled_time_delay_embedding_distance(human_scanpath, simulated_scanpath, ima
 # ---- DTW, Frechet, Hausdorff, Eyenalysis, cross-recurrence (no counterpart in the reference), csrc/scandist.hip ------------
 SCANPATH_DISTANCES = ("DTW", "Frechet", "Hausdorff", "Eyenalysis", "REC", "DET", "LAM", "CORM")
 _RECURRENCE = SCANPATH_DISTANCES[4:]
-MAX_FIXATIONS = 64          # = sp_scan_max_fixations(), known here so that a refusal needs no library (held equal by the tests)
 
 
 def _check_distance_args(metrics, max_dim, radius, min_line):
@@ -496,48 +475,26 @@ def scanpath_distances_pairs(scanpaths: Sequence[np.ndarray], pairs, metrics=SCA
     CORM NaN for N = 1.  One upload, one launch per entry point (sp_scan_distances, sp_scan_recurrence) and one copy back whatever the
     number of pairs; an empty pair list touches no device."""
     metrics, md, rad, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
-    arrs = [np.asarray(a, dtype=np.float64) for a in scanpaths]
-    arrs = [a.reshape(len(a), -1) if len(a) else np.zeros((0, a.shape[-1] if a.ndim == 2 else 2)) for a in arrs]
-    ncol = max([a.shape[1] for a in arrs if a.shape[0]], default=2)
-    if any(a.shape[1] != ncol and a.shape[0] > 0 for a in arrs) or ncol < 2:
-        raise ValueError("scanpaths need the same number (>= 2) of columns")
-    counts = np.array([a.shape[0] for a in arrs], dtype=np.int32)
-    if len(counts) and counts.max() > MAX_FIXATIONS:
-        raise ValueError(f"scanpath of {counts.max()} fixations exceeds the kernel limit {MAX_FIXATIONS}")
-    pr = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
-    if pr.size and (pr.min() < 0 or pr.max() >= len(arrs)):
-        raise ValueError(f"pair index out of range: {len(arrs)} scanpaths, indices {pr.min()} .. {pr.max()}")
-    npairs = pr.shape[0]
+    b = _batch.pack(scanpaths, min_cols=2)
+    pr = _batch.check_pairs(pairs, len(b.counts))
+    npairs = len(pr)
     if npairs == 0:
         return {m: np.zeros(0, dtype=np.float64) for m in metrics}
-    dev = _device()
-    L = hip.lib()
-    if L.sp_scan_max_fixations() != MAX_FIXATIONS:
-        raise hip.HipError(f"sp_scan_max_fixations() = {L.sp_scan_max_fixations()}, this module expects {MAX_FIXATIONS}")
-    # one host buffer, one upload: fixations | starts (int64) | pairs (int32) | counts (int32)
-    cat = np.concatenate([a for a in arrs if a.shape[0]] or [np.zeros((1, ncol))], 0)
-    start = np.cumsum(counts, dtype=np.int64) - counts
-    parts = [np.ascontiguousarray(cat).view(np.uint8).reshape(-1), start.view(np.uint8), pr.astype(np.int32).reshape(-1).view(np.uint8),
-             counts.view(np.uint8)]
-    off = np.cumsum([0] + [len(b) for b in parts])
-    buf = torch.from_numpy(np.concatenate(parts)).to(dev)
-    fix_p, start_p, pairs_p, count_p = (buf.data_ptr() + int(o) for o in off[:4])
+    dev, L, buf, at = _on_device(b, pr)
     dist = [m for m in SCANPATH_DISTANCES[:4] if m in metrics]
-    out = torch.empty((len(dist) + (4 if rad is not None else 0)) * npairs, dtype=torch.float64, device=dev)
-    if dist:
-        slot = {m: out.data_ptr() + 8 * npairs * k for k, m in enumerate(dist)}
-        check(L.sp_scan_distances(fix_p, ncol, start_p, count_p, pairs_p, npairs, md, slot.get("DTW"), slot.get("Frechet"),
-                                  slot.get("Hausdorff"), slot.get("Eyenalysis"), hip.stream()), "sp_scan_distances")
+    sections = {m: (np.float64, npairs) for m in dist}
     if rad is not None:
-        check(L.sp_scan_recurrence(fix_p, ncol, start_p, count_p, pairs_p, npairs, md, rad, min_line,
-                                   out.data_ptr() + 8 * npairs * len(dist), hip.stream()), "sp_scan_recurrence")
-    host = out.cpu().numpy()               # the one copy back (synchronises: buf and out outlive the launches)
-    rec = host[len(dist) * npairs:].reshape(npairs, 4) if rad is not None else None
-    res = {}
-    for m in metrics:
-        res[m] = (np.ascontiguousarray(rec[:, _RECURRENCE.index(m)]) if m in _RECURRENCE
-                  else host[dist.index(m) * npairs:(dist.index(m) + 1) * npairs].copy())
-    return res
+        sections["recurrence"] = (np.float64, 4 * npairs)
+    out = _batch.Out(sections, dev)
+    args = (at["rows"], b.ncol, at["starts"], at["counts"], at["pairs"], npairs, md)
+    if dist:
+        check(L.sp_scan_distances(*args, out.ptr("DTW"), out.ptr("Frechet"), out.ptr("Hausdorff"), out.ptr("Eyenalysis"), hip.stream()),
+              "sp_scan_distances")
+    if rad is not None:
+        check(L.sp_scan_recurrence(*args, rad, min_line, out.ptr("recurrence"), hip.stream()), "sp_scan_recurrence")
+    host = out.host()
+    rec = host["recurrence"].reshape(npairs, 4) if rad is not None else None
+    return {m: np.ascontiguousarray(rec[:, _RECURRENCE.index(m)]) if m in _RECURRENCE else host[m] for m in metrics}
 
 
 def _one_distance(metric, human_scanpath, simulated_scanpath):

@@ -167,8 +167,11 @@ def _multimatch_rows(mm, candidates, grouping=None):
 
 
 def _rows_for_pairs(paths, pairs, sm_wd, sm_wod, mm_rows):
-    """[npairs, 9] float64: 5 MultiMatch values, ScanMatch with duration, without duration, SED, STDE for (gt, other) pairs"""
+    """[npairs, 9] float64: 5 MultiMatch values, ScanMatch with duration, without duration, SED, STDE for (gt, other) pairs;
+    sm_wd None: the pair of ScanMatch objects of _make_scanmatch"""
     from .evaltools.visual_attention_metrics import sed_stde_pairs
+    if sm_wd is None:
+        sm_wd, sm_wod = _make_scanmatch()
     if not pairs:
         return np.zeros((0, 9))
     wd = _score_pairs(sm_wd, paths, pairs)
@@ -328,13 +331,6 @@ def _flat_metrics(mm_mean, mm_std, wd, wod, sed_all, stde_all, sed_best, stde_be
     return mean, std
 
 
-def _score_all(paths, pairs, mm_rows, sm_wd=None, sm_wod=None):
-    """[npairs, 9] float64 rows (5 MultiMatch, ScanMatch with / without duration, SED, STDE) for (first, second) path-index pairs"""
-    if sm_wd is None:
-        sm_wd, sm_wod = _make_scanmatch()
-    return _rows_for_pairs(paths, pairs, sm_wd, sm_wod, mm_rows)
-
-
 def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, multimatch=None, *, multimatch_grouping=None):
     """(OSIE/utils/evaluation.py:151-282, COCO_Search18/utils/evaluation.py:180-311) -> cur_metrics, cur_metrics_std, scores_of_each_images.
     Every (human scanpath of the image, prediction) pair; like the reference, SED / STDE are regrouped as [-1, number of human
@@ -351,7 +347,7 @@ def evaluation(gt_fix_vectors, predict_fix_vectors, is_eliminating_nan=True, mul
             pairs.append((len(paths) - 1, pi))
             cand.append((inner, predict_fix_vectors[index]))
     mm_rows = _multimatch_rows(mm, cand, grouping)
-    rows = _score_all(paths, pairs, mm_rows)
+    rows = _rows_for_pairs(paths, pairs, None, None, mm_rows)
     scores_of_each_images, k = [], 0
     for n in per_image:
         scores_of_each_images.append(list(np.array([list(r) for r in rows[k:k + n]]).mean(axis=0)))
@@ -385,7 +381,7 @@ def human_evaluation_free_viewing(dataloader, task="OSIE", multimatch=None, *, m
                     if i2 != i1:
                         pairs.append((base + i1, base + i2))
                         cand.append((fix_vectors[i1], fix_vectors[i2]))
-    rows = _score_all(paths, pairs, _multimatch_rows(mm, cand, grouping))
+    rows = _rows_for_pairs(paths, pairs, None, None, _multimatch_rows(mm, cand, grouping))
     scores, k = [], 0
     for n in groups:
         cnt = n * (n - 1)
@@ -512,6 +508,51 @@ def _key_index(gt_keys, image_keys):
     return index, [images[of_key[k]] for k in index]
 
 
+def _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors=None, predict_keys=None, image_keys=None):
+    """the keys of a keyed call, checked: one per fixation vector, every predicted key among gt_keys -> (gt_keys, predict_keys as
+    lists, and the index / images of _key_index)"""
+    gt_keys, predict_keys = list(gt_keys), [] if predict_keys is None else list(predict_keys)
+    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != (0 if predict_fix_vectors is None else len(predict_fix_vectors)):
+        raise ValueError("one key per fixation vector is required")
+    index, images = _key_index(gt_keys, image_keys)
+    unknown = [k for k in predict_keys if k not in index]
+    if unknown:
+        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    return gt_keys, predict_keys, index, images
+
+
+def _members(index, gt_keys):
+    """per key: the positions of its human scanpaths, in their order"""
+    members = [[] for _ in index]
+    for i, k in enumerate(gt_keys):
+        members[index[k]].append(i)
+    return members
+
+
+def _model_pairs(index, gt_keys, predict_keys):
+    """(pairs, owner): every human scanpath i of a key against every prediction j of the key, predictions numbered behind the human
+    scanpaths; owner = (key, j), the pairs of one prediction next to each other"""
+    members = _members(index, gt_keys)
+    pairs, owner = [], []
+    for j, k in enumerate(predict_keys):
+        for i in members[index[k]]:
+            pairs.append((i, len(gt_keys) + j))
+            owner.append((index[k], j))
+    return pairs, owner
+
+
+def _ceiling_pairs(index, gt_keys):
+    """(pairs, owner): every ordered pair (i, j) of distinct human scanpaths of a key, j as the "prediction"; owner = (key, j)"""
+    pairs, owner = [], []
+    for q, mem in enumerate(_members(index, gt_keys)):
+        for j in mem:
+            for i in mem:
+                if i != j:
+                    pairs.append((i, j))
+                    owner.append((q, j))
+    return pairs, owner
+
+
 def _saliency_means(per_key, metrics):
     means = {}
     for m in metrics:
@@ -535,13 +576,7 @@ def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_ke
     AUC_Judd, NSS, KLdiv and every extra; per_key = {"keys": [...], metric: float64 [G] numpy arrays, "gt_dropped" / "pred_dropped":
     int [G]}.  The same call on the human side alone: saliency_human_evaluation (ceiling), saliency_centre_prior_evaluation (floor)."""
     from .evaltools.saliency_maps import scanpath_saliency
-    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
-    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, images = _key_index(gt_keys, image_keys)
-    unknown = [k for k in predict_keys if k not in index]
-    if unknown:
-        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    gt_keys, predict_keys, index, images = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
     if extra_metrics or images is not None:
         kw = dict(kw, extra_metrics=extra_metrics, image_groups=images)
     res = scanpath_saliency(gt_fix_vectors, [index[k] for k in gt_keys], predict_fix_vectors, [index[k] for k in predict_keys],
@@ -568,13 +603,8 @@ def saliency_human_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *,
     a fold counts the held-out maps of the other images.  Same (means, per_key) result; gt_dropped / pred_dropped are sums over the
     folds."""
     from .evaltools.saliency_maps import scanpath_saliency
-    gt_keys = list(gt_keys)
-    if len(gt_keys) != len(gt_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, images = _key_index(gt_keys, image_keys)
-    members = [[] for _ in index]
-    for i, k in enumerate(gt_keys):
-        members[index[k]].append(i)
+    gt_keys, _, index, images = _keyed(gt_fix_vectors, gt_keys, image_keys=image_keys)
+    members = _members(index, gt_keys)
     fold_key = np.array([index[k] for k in gt_keys], dtype=np.int64)           # fold i holds out scanpath i
     pred, pred_fold = [], []
     for i, k in enumerate(gt_keys):
@@ -666,22 +696,9 @@ def scanpath_distance_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, p
     over the keys, means[name + "_nan"] = how many keys scored NaN.  The ceiling: scanpath_distance_human_evaluation."""
     from .evaltools.visual_attention_metrics import _check_distance_args
     metrics, max_dim, radius, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
-    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
-    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, _ = _key_index(gt_keys, None)
-    unknown = [k for k in predict_keys if k not in index]
-    if unknown:
-        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys)
     paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in predict_fix_vectors]
-    humans = [[] for _ in index]
-    for i, k in enumerate(gt_keys):
-        humans[index[k]].append(i)
-    pairs, owner = [], []
-    for j, k in enumerate(predict_keys):
-        for i in humans[index[k]]:
-            pairs.append((i, len(gt_keys) + j))
-            owner.append((index[k], j))
+    pairs, owner = _model_pairs(index, gt_keys, predict_keys)
     return _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_line)
 
 
@@ -690,20 +707,8 @@ def scanpath_distance_human_evaluation(gt_fix_vectors, gt_keys, *, metrics, max_
     human side and the second as the "prediction"; a key with one scanpath scores NaN.  Same (means, per_key) result."""
     from .evaltools.visual_attention_metrics import _check_distance_args
     metrics, max_dim, radius, min_line = _check_distance_args(metrics, max_dim, radius, min_line)
-    gt_keys = list(gt_keys)
-    if len(gt_keys) != len(gt_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, _ = _key_index(gt_keys, None)
-    members = [[] for _ in index]
-    for i, k in enumerate(gt_keys):
-        members[index[k]].append(i)
-    pairs, owner = [], []
-    for q, mem in enumerate(members):
-        for j in mem:
-            for i in mem:
-                if i != j:
-                    pairs.append((i, j))
-                    owner.append((q, j))
+    gt_keys, _, index, _ = _keyed(gt_fix_vectors, gt_keys)
+    pairs, owner = _ceiling_pairs(index, gt_keys)
     return _distance_tables(index, [_xy(fv) for fv in gt_fix_vectors], pairs, owner, metrics, max_dim, radius, min_line)
 
 
@@ -728,25 +733,12 @@ def sequence_score_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, pred
     from .evaltools.sequence_score import _check_cluster_args, _check_sequence_args, keyed_sequence_scores
     _check_cluster_args(bandwidth, max_iter)
     metrics, gap = _check_sequence_args(metrics, gap)
-    gt_keys, predict_keys = list(gt_keys), list(predict_keys)
-    if len(gt_keys) != len(gt_fix_vectors) or len(predict_keys) != len(predict_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, _ = _key_index(gt_keys, None)
-    unknown = [k for k in predict_keys if k not in index]
-    if unknown:
-        raise ValueError(f"predicted key {unknown[0]!r} ({len(unknown)} in all) is not among gt_keys")
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys)
     group_of_key = _cluster_groups(index, gt_keys, cluster_keys)
     paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in predict_fix_vectors]
     path_group = np.array([group_of_key[index[k]] for k in gt_keys + predict_keys], dtype=np.int64)
     human_group = np.r_[path_group[:len(gt_keys)], np.full(len(predict_keys), -1, dtype=np.int64)]
-    humans = [[] for _ in index]
-    for i, k in enumerate(gt_keys):
-        humans[index[k]].append(i)
-    pairs, owner = [], []
-    for j, k in enumerate(predict_keys):
-        for i in humans[index[k]]:
-            pairs.append((i, len(gt_keys) + j))
-            owner.append((index[k], j))
+    pairs, owner = _model_pairs(index, gt_keys, predict_keys)
     scores = keyed_sequence_scores(paths, path_group, human_group, pairs, int(group_of_key.max()) + 1 if len(index) else 0,
                                    bandwidth=bandwidth, metrics=metrics, gap=gap, max_iter=max_iter)
     return _pair_tables(index, scores, owner, metrics, ("FED",), ("SS",))
@@ -760,22 +752,10 @@ def sequence_score_human_evaluation(gt_fix_vectors, gt_keys, *, bandwidth, metri
     from .evaltools.sequence_score import _check_cluster_args, _check_sequence_args, keyed_sequence_scores
     _check_cluster_args(bandwidth, max_iter)
     metrics, gap = _check_sequence_args(metrics, gap)
-    gt_keys = list(gt_keys)
-    if len(gt_keys) != len(gt_fix_vectors):
-        raise ValueError("one key per fixation vector is required")
-    index, _ = _key_index(gt_keys, None)
+    gt_keys, _, index, _ = _keyed(gt_fix_vectors, gt_keys)
     group_of_key = _cluster_groups(index, gt_keys, cluster_keys)
     path_group = np.array([group_of_key[index[k]] for k in gt_keys], dtype=np.int64)
-    members = [[] for _ in index]
-    for i, k in enumerate(gt_keys):
-        members[index[k]].append(i)
-    pairs, owner = [], []
-    for q, mem in enumerate(members):
-        for j in mem:
-            for i in mem:
-                if i != j:
-                    pairs.append((i, j))
-                    owner.append((q, j))
+    pairs, owner = _ceiling_pairs(index, gt_keys)
     scores = keyed_sequence_scores([_xy(fv) for fv in gt_fix_vectors], path_group, path_group, pairs,
                                    int(group_of_key.max()) + 1 if len(index) else 0, bandwidth=bandwidth, metrics=metrics, gap=gap,
                                    max_iter=max_iter)
