@@ -590,6 +590,29 @@ int sp_scan_cluster_strings(const double* fix, int ncol, const int64_t* start, c
  * read); ss NaN for n = m = 0. */
 int sp_scan_sequence(const int* labels, const int64_t* start, const int* count, const int* pairs, int npairs, double gap, double* ss,
                      double* fed, void* stream);
+/* Human scanpaths under the model's own step distributions (csrc/scanlik.hip, one wavefront per (row, step), one
+ * launch per call), float64, every operation rounded on its own.  probs [R][T][1 + P] float32, P = Hm * Wm at most the max_cells() value
+ * below: action 0 = terminate, action 1 + row * Wm + col = a cell; every p enters as the float32 value converted exactly to float64.
+ * S scanpaths in the fixation layout of sp_scan_sed_stde (x, y[, duration]); the scanpaths scored by row r of probs are
+ * order[row_first[r] .. + row_n[r]] (every scanpath once).  Fixation t of a scanpath of n fixations meets step t for t < min(n, T); its
+ * cell is col = floor(x * Wm / frame_w), row = floor(y * Hm / frame_h) (the pixel rule of sp_fixation_maps); a fixation outside the
+ * frame or with a non-finite coordinate is dropped: NaN in LL, IG, NSS, AUC, and counted in dropped [S].  With Z = sum_{c >= 1} p_c,
+ * q' = (1 - u) p_c / Z + u / P (u = uniform_mix in [0, 1)) at the fixated cell c:
+ *   LL  = log2(P q');   IG = log2 q' - log2 b', b' = (1 - u) b_c / sum b + u / P of row baseline_rows[s] of baseline [.][P] (NaN for a
+ *   row sum <= 0);   NSS = (p_c - Z / P) / std, ddof 1, two-pass (NaN for P < 2 or min p == max p);   AUC = (#{p_c' < p_c} + 0.5
+ *   #{c' != c: p_c' == p_c}) / (P - 1) on the raw float32 values (NaN for P < 2);   DLL = (-ln d - 0.5 ln(2 pi s2) - (ln d - mu)^2 /
+ *   (2 s2)) / ln 2 with mu, sigma2 [R][T] float32 of the scanpath's row (NaN for d <= 0, non-finite d or s2 <= 0; a dropped fixation
+ *   has one), each [S][T], NaN for t >= min(n, T);   CONT = log2(Z / (Z + p_0)), TERM = log2(p_0 / (Z + p_0)), each [R][T].
+ * No epsilon inside any logarithm: a zero probability scores -inf at u = 0.  Sums: every lane adds cells lane, lane + 64, .. in that
+ * order, the 64 partial sums combine by the xor butterfly 32, 16, .., 1.  Every output may be NULL (not all); IG needs baseline and
+ * baseline_rows, DLL needs mu, sigma2 and ncol >= 3.  Every element of every output given is written.  A scanpath with a count outside
+ * [0, sp_scan_max_fixations()] gets NaN everywhere and dropped 0, and none of its fixations is read. */
+int sp_scan_likelihood_max_cells(void);
+int sp_scan_likelihood(const float* probs, const float* mu, const float* sigma2, const double* baseline, const int* baseline_rows,
+                       const double* fix, const int64_t* start, const int* count, const int* row_first, const int* row_n,
+                       const int* order, int R, int T, int Hm, int Wm, int S, int ncol, double frame_w, double frame_h,
+                       double uniform_mix, double* LL, double* IG, double* NSS, double* AUC, double* DLL, double* CONT, double* TERM,
+                       int* dropped, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -70,3 +70,29 @@ def run_test_loop(model, sampling, loader: Iterable[dict], repeat_num: int = 10,
                                             "Y": list(arr[:, 1]), "T": list(arr[:, 2] * 1000), "length": len(arr)})
     cur_metrics, cur_metrics_std, scores = evaluation_performance_related(all_gt, all_pred, all_perf, all_alloc, multimatch)
     return cur_metrics, cur_metrics_std, scores, predict_results
+
+
+@torch.no_grad()
+def run_likelihood_loop(model, loader: Iterable[dict], *, uniform_mix, metrics=("LL", "NSS", "AUC"), min_length=0, baseline=None,
+                        ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None) -> Tuple[dict, List[dict]]:
+    """The loop of run_test_loop without sampling: the human scanpaths of every batch are scored under the distributions the model
+    puts out for it (utils.evaluation.likelihood_evaluation) -- per batch ONE eval-mode forward, ONE sp_scan_likelihood launch and ONE
+    small device->host copy (the scores; the distributions stay on the device).  loader yields run_test_loop's batches; "performances"
+    is read when the model has the two AiR heads ("good_all_actions_prob" in its output), and with a baseline of more than one row
+    "baseline_rows" names the row of every sample's image.  The key of a sample is its question id.
+    Returns (means, per_key of every batch): means = the batches' pooled means merged by utils.evaluation.LikelihoodTable."""
+    from .utils.evaluation import LikelihoodTable, likelihood_evaluation
+    model.eval()
+    table, per_batch = LikelihoodTable(), []
+    for batch in loader:
+        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
+        if ablate_attention_info:
+            attention_maps = attention_maps * 0
+        predict = model(images, attention_maps)
+        means, per_key = likelihood_evaluation(predict, batch["fix_vectors"], batch["question_ids"],
+                                               batch["performances"] if "good_all_actions_prob" in predict else None,
+                                               batch.get("baseline_rows"), baseline, uniform_mix=uniform_mix, metrics=metrics,
+                                               min_length=min_length, frame_size=frame_size, map_shape=map_shape)
+        table.add(means)
+        per_batch.append(per_key)
+    return table.result(), per_batch

@@ -15,6 +15,9 @@ csrc/scanmetrics.hip, plus the batched form the validation loops need:
     d = scanpath_distances_pairs(scanpaths, pairs, metrics=("DTW", "REC", "DET"), radius=30.0)   # {metric: float64 numpy [npairs]}
     DTW(h, s), frechet_distance(h, s), hausdorff_distance(h, s), eyenalysis_distance(h, s), cross_recurrence(h, s, radius=30.0)
 
+    lik = scanpath_likelihood(probs, scanpaths, rows, frame_size, uniform_mix=0.01)              # scanpath_likelihood.py, re-exported here:
+    # {"LL", "NSS", "AUC": float64 numpy [S, T], "n", "dropped"}: human fixations under the model's own step distributions
+
 SED is bit-exact; STDE follows numpy's float64 evaluation order (differences only in the last bit of exp()).  No CPU path."""
 from __future__ import annotations
 
@@ -531,3 +534,4 @@ def cross_recurrence(human_scanpath, simulated_scanpath, *, radius, min_line=2):
 
 
 from .saliency_maps import density_maps, fixation_maps, gaussian_weights, scanpath_saliency  # noqa: E402,F401  (producers of the maps above)
+from .scanpath_likelihood import cell_baselines, scanpath_likelihood  # noqa: E402,F401  (human scanpaths under the model's distributions)

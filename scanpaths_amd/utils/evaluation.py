@@ -760,3 +760,101 @@ def sequence_score_human_evaluation(gt_fix_vectors, gt_keys, *, bandwidth, metri
                                    int(group_of_key.max()) + 1 if len(index) else 0, bandwidth=bandwidth, metrics=metrics, gap=gap,
                                    max_iter=max_iter)
     return _pair_tables(index, scores, owner, metrics, ("FED",), ("SS",))
+
+
+# ---- human scanpaths under the model's own step distributions (evaltools/scanpath_likelihood.py, csrc/scanlik.hip) ------
+def likelihood_evaluation(predict, fix_vectors, keys, performances=None, image_keys=None, baseline=None, *, uniform_mix,
+                          metrics=("LL", "NSS", "AUC"), min_length=0, frame_size=(240, 320), map_shape=None):
+    """Per-fixation log-likelihood, information gain, NSS, AUC, duration log-likelihood and length log-probability (metrics: any of
+    evaltools.scanpath_likelihood.METRICS) of the human scanpaths of ONE batch under the distributions the model put out for it -- no
+    sampling.  predict: the model's eval-mode output on the device; fix_vectors[i]: the list of the subjects' fixation vectors of
+    sample i (the reference's evaluation layout), keys[i]: its key (a question id, an image name: any hashable).  With performances
+    (AiR: performances[i][k] = subject k of sample i answered correctly) predict["good_all_actions_prob"] / ["good_log_normal_*"]
+    score the subjects who answered correctly and the "poor_" outputs the others, as training assigns the heads; without it the
+    unprefixed outputs score everybody.  "IG": baseline [NB, P] (evaltools.scanpath_likelihood.cell_baselines) and image_keys[i] = the
+    baseline row of sample i's image (default: the only row of a one-row baseline).  uniform_mix is required (0 is allowed);
+    min_length: the sampler's, for "STOP".  One launch and one copy back for the whole batch.
+    Returns (means, per_key): per_key[m] = the mean over the key's scored fixations ("STOP": over its scanpaths), float64 [G] in
+    first-appearance order of keys (per_key["keys"]), NaN for a key without one; means[m] = the mean pooled over all scored fixations
+    of the call -- bits per fixation, the convention of the papers -- with means[m + "_sum"] / [m + "_count"] = the sum and number of
+    the values it is the mean of (what LikelihoodTable merges), means[m + "_nan"] = the NaN values left out (dropped fixations, NSS on
+    a constant map, ...), means[m + "_nan_keys"] = the keys that scored NaN, means["dropped"] = the dropped fixations.  A value of
+    -inf is a score, not a gap: it is kept and makes the means -inf."""
+    from .evaltools.scanpath_likelihood import _check_args, scanpath_likelihood
+    metrics, _, min_length = _check_args(metrics, uniform_mix, min_length)
+    keys = list(keys)
+    N = len(keys)
+    if len(fix_vectors) != N:
+        raise ValueError("one key per sample is required")
+    if performances is not None and (len(performances) != N or any(len(p) != len(f) for p, f in zip(performances, fix_vectors))):
+        raise ValueError("one performance per subject of every sample is required")
+    if image_keys is not None and len(image_keys) != N:
+        raise ValueError("one image key (baseline row) per sample is required")
+    if "IG" in metrics and baseline is not None and image_keys is None:
+        if len(baseline) != 1:
+            raise ValueError(f"image_keys is required to choose among the {len(baseline)} baseline rows")
+        image_keys = [0] * N
+    import torch
+    heads = ("",) if performances is None else ("good_", "poor_")
+    names = [h + k for h in heads for k in ("all_actions_prob",) + (("log_normal_mu", "log_normal_sigma2") if "DLL" in metrics else ())]
+    missing = [k for k in names if k not in predict]
+    if missing:
+        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
+                                                            else ""))
+    if any(predict[k].shape[0] != N for k in names):
+        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
+    index, _ = _key_index(keys, None)
+    paths, rows, brows, key_of = [], [], [], []
+    for i, subjects in enumerate(fix_vectors):
+        for k, fv in enumerate(subjects):
+            paths.append(fv)
+            rows.append(i if performances is None or performances[i][k] == True else N + i)           # noqa: E712  (as the reference)
+            key_of.append(index[keys[i]])
+            if image_keys is not None:
+                brows.append(image_keys[i])
+
+    def both(name):
+        return predict[name] if performances is None else torch.cat([predict["good_" + name], predict["poor_" + name]], 0)
+
+    dll = "DLL" in metrics
+    res = scanpath_likelihood(both("all_actions_prob"), paths, rows, frame_size, uniform_mix=uniform_mix, metrics=metrics,
+                              map_shape=map_shape, baseline=baseline, baseline_rows=brows if "IG" in metrics else None,
+                              log_normal_mu=both("log_normal_mu") if dll else None,
+                              log_normal_sigma2=both("log_normal_sigma2") if dll else None, min_length=min_length)
+    G, key_of = len(index), np.asarray(key_of, dtype=np.int64)
+    T = predict[names[0]].shape[1]
+    met = np.arange(T)[None, :] < res["n"][:, None]                          # [S, T]: fixation t met a step
+    per_key, means = {"keys": list(index)}, {}
+    for m in metrics:
+        v, owner = (res[m], key_of) if m == "STOP" else (res[m][met], np.broadcast_to(key_of[:, None], met.shape)[met])
+        ok = ~np.isnan(v)
+        ksum, kcnt = np.bincount(owner[ok], weights=v[ok], minlength=G), np.bincount(owner[ok], minlength=G)
+        per_key[m] = np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan)
+        total, count = float(v[ok].sum()), int(ok.sum())
+        means.update({m: total / count if count else float("nan"), m + "_sum": total, m + "_count": count,
+                      m + "_nan": int((~ok).sum()), m + "_nan_keys": int(np.isnan(per_key[m]).sum())})
+    per_key["dropped"] = np.bincount(key_of, weights=res["dropped"], minlength=G).astype(np.int64)
+    means["dropped"] = int(res["dropped"].sum())
+    return means, per_key
+
+
+class LikelihoodTable:
+    """The pooled means of likelihood_evaluation over several batches, merged exactly: add(means) sums every metric's "_sum",
+    "_count", "_nan" and "_nan_keys" entry and "dropped"; result() = the means dict of all batches as one call would give it (a key
+    that appears in two batches counts in each for "_nan_keys")."""
+
+    def __init__(self):
+        self.parts = {}
+
+    def add(self, means) -> None:
+        for k, v in means.items():
+            if k == "dropped" or k.endswith(("_sum", "_count", "_nan", "_nan_keys")):
+                self.parts[k] = self.parts.get(k, 0) + v
+
+    def result(self) -> dict:
+        out = dict(self.parts)
+        for k in self.parts:
+            if k.endswith("_count"):
+                m = k[:-len("_count")]
+                out[m] = self.parts[m + "_sum"] / self.parts[k] if self.parts[k] else float("nan")
+        return out
