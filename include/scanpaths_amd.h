@@ -518,20 +518,23 @@ int sp_scanmatch_align(const int* A, int n, const int* B, int m, const double* s
  * (human index, simulated index).  sed[p] = Levenshtein distance of the ngrid x ngrid cell strings (cell = int32(x) //
  * (width // ngrid) + int32(y) // (height // ngrid) * ngrid), bit-exact; stde[p] = mean over k = 1..min(len) of
  * exp(-mean_s min_h sum_i ||s_i - h_i|| / k) on coordinates / max_dim, numpy summation order, NaN when a scanpath is empty
- * (the reference returns None).  Either output may be NULL. */
+ * (the reference returns None).  Either output may be NULL.  The kernel guards itself: a pair with a count outside
+ * [0, sp_scan_max_fixations()] reads no fixation and gets sed -1 and stde NaN. */
 int sp_scan_max_fixations(void);
 int sp_scan_sed_stde(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, int height,
                      int width, int ngrid, double max_dim, int* sed, double* stde, void* stream);
 /* Time-delay-embedding distances and the Euclidean distance of scanpath pairs (visual_attention_metrics.py:205-218, :332-388,
  * :444-476), same fixation layout as sp_scan_sed_stde.  k >= 1: time_delay_embedding_distance at k ('Mean', or 'Hausdorff' when
  * hausdorff != 0), NaN where the reference returns False; k == 0: scaled_time_delay_embedding_distance (coordinates / max_dim, mean
- * over every k), NaN where it returns None.  eucl (may be NULL): euclidean_distance of the unscaled pair, NaN where it returns False. */
+ * over every k), NaN where it returns None.  eucl (may be NULL): euclidean_distance of the unscaled pair, NaN where it returns False.
+ * A pair with a count outside [0, sp_scan_max_fixations()] reads no fixation and gets NaN in both. */
 int sp_scan_tde(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs, int k, int hausdorff,
                 double max_dim, double* tde, double* eucl, void* stream);
 /* MultiMatch (the five similarities the reference obtains per pair from multimatch_gaze.docomparison, AiR/utils/evaluation.py:7,44-45,213;
  * multimatch_gaze==0.1.2 is not vendored: the published algorithm, restated on the host in utils/evaltools/multimatch.py, is this
  * kernel's checker): fix [total][ncol >= 3] = (x, y, duration), scanpaths of at most sp_scan_max_fixations() fixations; out [npairs][5]
- * = (vector, direction, length, position, duration), five NaNs for a pair with a scanpath of fewer than 3 fixations. */
+ * = (vector, direction, length, position, duration), five NaNs for a pair with a scanpath of fewer than 3 fixations -- or of more
+ * than sp_scan_max_fixations(), of which no fixation is read (sp_scan_multimatch_gated likewise). */
 int sp_scan_multimatch(const double* fix, int ncol, const int64_t* start, const int* count, const int* pairs, int npairs,
                        double screen_w, double screen_h, double* out, void* stream);
 /* MultiMatch scanpath simplification (Jarodzka et al. 2010, Dewhurst et al. 2012; csrc/scansimplify.hip, one

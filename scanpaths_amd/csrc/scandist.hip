@@ -2,10 +2,7 @@
 // Frechet distance (Eiter & Mannila 1994), the Hausdorff distance, Eyenalysis (Mathot et al. 2012, position only) and the four
 // cross-recurrence measures REC / DET / LAM / CORM (Anderson et al. 2015), of npairs scanpath pairs in the fixation layout of
 // scanmetrics.hip.  P is the first scanpath of a pair, Q the second; coordinates are divided by max_dim first;
-// d(i,j) = sqrt(dx*dx + dy*dy) with every operation rounded on its own: this file is compiled with floating-point contraction OFF
-// (the pragma below) and uses the plain operators.  __dmul_rn / __dadd_rn do not give that here: the compiler's header defines them
-// as `x * y` / `x + y` compiled under the default -ffp-contract=fast, so after inlining dx*dx + dy*dy becomes one v_fma_f64 -- which
-// changes the last bit as soon as dx*dx is not exact (it is on integer pixel grids, which is why only off-grid data shows it).
+// d(i,j) = sqrt(dx*dx + dy*dy) with every operation rounded on its own (scan_dist and the arithmetic rule of scan_common.h).
 //
 // One WAVEFRONT per pair, four pairs per 256-thread block; no LDS, no per-thread arrays, no atomics.  Lane j owns Q_j (and, for the
 // row minima, P_j).
@@ -20,40 +17,23 @@
 // The kernels guard themselves: a pair with a scanpath of more than MAXFIX (or fewer than 0) fixations gets NaN in every output and
 // none of its fixations is read.
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "scan_common.h"
 
 namespace {
 
-constexpr int MAXFIX = 64;        // = sp_scan_max_fixations() (scanmetrics.hip): one lane per fixation
-
-__device__ __forceinline__ double sd_dist(double ax, double ay, double bx, double by) {
-    const double dx = ax - bx, dy = ay - by;
-    return __builtin_sqrt(dx * dx + dy * dy);      // three roundings and the correctly rounded root
-}
 __device__ __forceinline__ double sd_min(double a, double b) { return b < a ? b : a; }
 __device__ __forceinline__ double sd_max(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = sd_max(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 __global__ __launch_bounds__(256) void scan_distances_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
                                                              const int* __restrict__ count, const int* __restrict__ pairs, int npairs,
                                                              double max_dim, double* __restrict__ dtw, double* __restrict__ frechet,
                                                              double* __restrict__ hausdorff, double* __restrict__ eyenalysis) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= npairs) return;                                   // the whole wave leaves
-    const int ip = pairs[2 * p], iq = pairs[2 * p + 1];
-    const int n = count[ip], m = count[iq];
-    if (n < 1 || m < 1 || n > MAXFIX || m > MAXFIX) {          // empty, or beyond the kernel limit: NaN, nothing else is read
+    int lane;
+    int64_t p;
+    if (!scan_wave_item(npairs, lane, p)) return;
+    const ScanPair<double> q = scan_pair(pairs, count, start, fix, ncol, p);
+    const int n = q.na, m = q.nb;
+    if (q.bad() || n < 1 || m < 1) {                           // beyond the kernel limit, or empty: NaN, no fixation is read
         if (lane == 0) {
             if (dtw) dtw[p] = NAN;
             if (frechet) frechet[p] = NAN;
@@ -62,8 +42,7 @@ __global__ __launch_bounds__(256) void scan_distances_kernel(const double* __res
         }
         return;
     }
-    const double* fp = fix + start[ip] * ncol;
-    const double* fq = fix + start[iq] * ncol;
+    const double *fp = q.ra, *fq = q.rb;
     double px = 0.0, py = 0.0, qx = 0.0, qy = 0.0;             // P_lane, Q_lane
     if (lane < n) { px = fp[(int64_t)lane * ncol] / max_dim; py = fp[(int64_t)lane * ncol + 1] / max_dim; }
     if (lane < m) { qx = fq[(int64_t)lane * ncol] / max_dim; qy = fq[(int64_t)lane * ncol + 1] / max_dim; }
@@ -75,7 +54,7 @@ __global__ __launch_bounds__(256) void scan_distances_kernel(const double* __res
             const int i = k - lane;
             const bool live = lane < m && i >= 0 && i < n;
             const int src = live ? i : 0;
-            const double d = sd_dist(__shfl(px, src, 64), __shfl(py, src, 64), qx, qy);
+            const double d = scan_dist(__shfl(px, src, 64) - qx, __shfl(py, src, 64) - qy);
             const double dl = __shfl_up(dv, 1, 64), fl = __shfl_up(fv, 1, 64);
             if (live) {
                 const bool top = i == 0, first = lane == 0;
@@ -103,8 +82,8 @@ __global__ __launch_bounds__(256) void scan_distances_kernel(const double* __res
 
     if (hausdorff || eyenalysis) {
         double colmin = INFINITY, rowmin = INFINITY;           // min_i d(i, lane), min_j d(lane, j)
-        for (int i = 0; i < n; ++i) colmin = sd_min(colmin, sd_dist(__shfl(px, i, 64), __shfl(py, i, 64), qx, qy));
-        for (int j = 0; j < m; ++j) rowmin = sd_min(rowmin, sd_dist(px, py, __shfl(qx, j, 64), __shfl(qy, j, 64)));
+        for (int i = 0; i < n; ++i) colmin = sd_min(colmin, scan_dist(__shfl(px, i, 64) - qx, __shfl(py, i, 64) - qy));
+        for (int j = 0; j < m; ++j) rowmin = sd_min(rowmin, scan_dist(px - __shfl(qx, j, 64), py - __shfl(qy, j, 64)));
         if (hausdorff) {
             const double h = wave_max_d(sd_max(lane < n ? rowmin : 0.0, lane < m ? colmin : 0.0));     // d >= 0
             if (lane == 0) hausdorff[p] = h;
@@ -131,19 +110,17 @@ __device__ __forceinline__ int run_points(unsigned long long mask, int L) {
 __global__ __launch_bounds__(256) void scan_recurrence_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
                                                               const int* __restrict__ count, const int* __restrict__ pairs, int npairs,
                                                               double max_dim, double radius, int L, double* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= npairs) return;
-    const int ip = pairs[2 * p], iq = pairs[2 * p + 1];
-    const int n = count[ip], m = count[iq];
-    const int N = min(n, m);
+    int lane;
+    int64_t p;
+    if (!scan_wave_item(npairs, lane, p)) return;
+    const ScanPair<double> q = scan_pair(pairs, count, start, fix, ncol, p);
+    const int N = min(q.na, q.nb);
     double* o = out + 4 * p;
-    if (N < 1 || n > MAXFIX || m > MAXFIX) {
+    if (q.bad() || N < 1) {
         if (lane < 4) o[lane] = NAN;
         return;
     }
-    const double* fp = fix + start[ip] * ncol;
-    const double* fq = fix + start[iq] * ncol;
+    const double *fp = q.ra, *fq = q.rb;
     double px = 0.0, py = 0.0, qx = 0.0, qy = 0.0;
     if (lane < N) {
         px = fp[(int64_t)lane * ncol] / max_dim; py = fp[(int64_t)lane * ncol + 1] / max_dim;
@@ -152,7 +129,7 @@ __global__ __launch_bounds__(256) void scan_recurrence_kernel(const double* __re
     int R = 0, HL = 0;                                         // wave-uniform
     int vrun = 0, VL = 0, drun = 0, DL = 0, corm = 0;          // per lane (column lane; the diagonal through (i, lane))
     for (int i = 0; i < N; ++i) {
-        const bool c = lane < N && sd_dist(__shfl(px, i, 64), __shfl(py, i, 64), qx, qy) <= radius;
+        const bool c = lane < N && scan_dist(__shfl(px, i, 64) - qx, __shfl(py, i, 64) - qy) <= radius;
         const unsigned long long mask = __ballot(c);
         R += __popcll(mask);
         HL += run_points(mask, L);

@@ -1,8 +1,8 @@
 // Human scanpaths under the model's own step distributions: per-fixation log-likelihood, information gain over a
 // baseline, NSS and AUC of each decode step's conditional map at the human fixation of that step, the log-normal duration density, and
 // the per-step continue / terminate log-probabilities.  probs [R][T][1 + P] float32 (action 0 = terminate, action 1 + row * Wm + col =
-// a cell, models/sampling.py); every probability enters the arithmetic as the float32 value converted exactly to float64.  This file is
-// compiled with floating-point contraction OFF (scandist.hip says why the pragma and not the __dmul_rn intrinsics).
+// a cell, models/sampling.py); every probability enters the arithmetic as the float32 value converted exactly to float64, and every
+// operation is rounded on its own (the arithmetic rule of scan_common.h: contraction OFF, plain operators).
 //
 //   scan_likelihood_kernel: ONE WAVEFRONT PER (row, step), four per block.  The wave loads the step's P <= 2048 cell values once into
 //     32 registers per lane (cell c in lane c % 64, slot c / 64; fully unrolled and predicated, no dynamically indexed array, no LDS, no
@@ -16,20 +16,12 @@
 // buffers, and it guards itself: a scanpath of more than MAXFIX (or fewer than 0) fixations gets NaN everywhere and none of its rows
 // is read.
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "scan_common.h"
 
 namespace {
 
-constexpr int MAXFIX = 64;        // = sp_scan_max_fixations() (scanmetrics.hip)
 constexpr int SLOTS = 32;         // registers per lane that hold a step's map
 constexpr int MAXCELLS = SLOTS * 64;
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 struct LikArgs {
     const float *probs, *mu, *sigma2;
@@ -45,9 +37,9 @@ struct LikArgs {
 };
 
 __global__ __launch_bounds__(256) void scan_likelihood_kernel(const LikArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t rt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (rt >= (int64_t)a.R * a.T) return;                      // the whole wave leaves
+    int lane;
+    int64_t rt;
+    if (!scan_wave_item((int64_t)a.R * a.T, lane, rt)) return;
     const int r = (int)(rt / a.T), t = (int)(rt % a.T);
     const int P = a.Hm * a.Wm;
     const float* __restrict__ p = a.probs + rt * (int64_t)(P + 1);
@@ -99,8 +91,7 @@ __global__ __launch_bounds__(256) void scan_likelihood_kernel(const LikArgs a) {
         const int s = a.order[first + i];
         const int n = a.count[s];
         const int64_t o = (int64_t)s * a.T + t;
-        const bool guarded = n < 0 || n > MAXFIX;
-        const int m = guarded ? 0 : min(n, a.T);               // fixations that meet a step
+        const int m = scan_count_bad(n) ? 0 : min(n, a.T);     // fixations that meet a step
         const double* __restrict__ f = a.fix + (a.start[s] + t) * a.ncol;      // read only where t < m
         if (a.dropped && t == 0) {                             // one lane per fixation
             bool out = false;

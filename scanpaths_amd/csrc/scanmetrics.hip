@@ -4,15 +4,15 @@
 // Levenshtein), :332-441 (time-delay embedding, 'Mean' mode, all window lengths, mean of exp(-d)).
 //
 // One thread per pair (scanpaths have <= 64 fixations; validation scores ~10^5 pairs at once).  SED is integer work and
-// bit-exact.  STDE follows numpy's float64 evaluation order exactly -- products and sums are NOT contracted into FMAs
-// (__dmul_rn / __dadd_rn), a window's distances are added with numpy's pairwise-summation scheme (sequential below 8
+// bit-exact.  STDE follows numpy's float64 evaluation order exactly -- no product and sum is contracted into an FMA (the rule and the
+// pragma of scan_common.h, plain operators), a window's distances are added with numpy's pairwise-summation scheme (sequential below 8
 // terms, 8 interleaved partial sums above), means are left-to-right python sums -- so the only possible difference to the
 // reference is the last bit of exp().
+// The kernels guard themselves: a pair with a count outside 0 .. MAXFIX reads no fixation and gets NaN in its float outputs, -1 in sed.
 #include "common.h"
+#include "scan_common.h"
 
 namespace {
-
-constexpr int MAXFIX = 64;
 
 __device__ __forceinline__ int floordiv(int a, int b) {
     int q = a / b;
@@ -25,7 +25,7 @@ template <typename F>
 __device__ __forceinline__ double numpy_sum(int n, F term) {
     if (n < 8) {
         double res = 0.0;
-        for (int i = 0; i < n; ++i) res = __dadd_rn(res, term(i));
+        for (int i = 0; i < n; ++i) res = res + term(i);
         return res;
     }
     double r[8];
@@ -34,12 +34,34 @@ __device__ __forceinline__ double numpy_sum(int n, F term) {
     int i = 8;
     for (; i < n - (n % 8); i += 8) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] = __dadd_rn(r[j], term(i + j));
+        for (int j = 0; j < 8; ++j) r[j] = r[j] + term(i + j);
     }
-    double res = __dadd_rn(__dadd_rn(__dadd_rn(r[0], r[1]), __dadd_rn(r[2], r[3])),
-                           __dadd_rn(__dadd_rn(r[4], r[5]), __dadd_rn(r[6], r[7])));
-    for (; i < n; ++i) res = __dadd_rn(res, term(i));
+    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res = res + term(i);
     return res;
+}
+
+// x and y of a scanpath's n <= MAXFIX fixations, divided by max_dim
+__device__ __forceinline__ void scaled_xy(const double* f, int n, int ncol, double max_dim, double* x, double* y) {
+    for (int i = 0; i < n; ++i) { x[i] = f[i * ncol] / max_dim; y[i] = f[i * ncol + 1] / max_dim; }
+}
+
+// time_delay_embedding_distance(h, s, k) in 'Mean' or (haus) 'Hausdorff' mode; 1 <= k <= min(nh, ns)
+__device__ __forceinline__ double dist_k(const double* hx, const double* hy, int nh, const double* sx, const double* sy, int ns, int k,
+                                         bool haus) {
+    double acc = 0.0, worst = -INFINITY;
+    const int nsw = ns - k + 1, nhw = nh - k + 1;
+    for (int s0 = 0; s0 < nsw; ++s0) {
+        double best = INFINITY;
+        for (int h0 = 0; h0 < nhw; ++h0) {
+            const double d = numpy_sum(k, [&](int i) { return scan_dist(sx[s0 + i] - hx[h0 + i], sy[s0 + i] - hy[h0 + i]); });
+            best = d < best ? d : best;
+        }
+        const double v = best / (double)k;
+        acc = acc + v;
+        worst = v > worst ? v : worst;
+    }
+    return haus ? worst : acc / (double)nsw;
 }
 
 __global__ __launch_bounds__(64) void sed_stde_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
@@ -48,10 +70,14 @@ __global__ __launch_bounds__(64) void sed_stde_kernel(const double* __restrict__
                                                       double* __restrict__ stde) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= npairs) return;
-    const int ih = pairs[2 * p], is = pairs[2 * p + 1];
-    const int nh = count[ih], ns = count[is];
-    const double* fh = fix + start[ih] * ncol;
-    const double* fs = fix + start[is] * ncol;
+    const ScanPair<double> q = scan_pair(pairs, count, start, fix, ncol, p);
+    if (q.bad()) {
+        if (sed) sed[p] = -1;
+        if (stde) stde[p] = NAN;
+        return;
+    }
+    const int nh = q.na, ns = q.nb;
+    const double *fh = q.ra, *fs = q.rb;
     // ---- SED: Levenshtein over the n x n grid strings ----
     if (sed) {
         const int ws = width / ngrid, hs = height / ngrid;
@@ -71,33 +97,18 @@ __global__ __launch_bounds__(64) void sed_stde_kernel(const double* __restrict__
         }
         sed[p] = row[nh];
     }
-    // ---- STDE ----
+    // ---- STDE: the mean over k of exp(-the 'Mean' distance at k) ----
     if (stde) {
         double hx[MAXFIX], hy[MAXFIX], sx[MAXFIX], sy[MAXFIX];
-        for (int i = 0; i < nh; ++i) { hx[i] = fh[i * ncol] / max_dim; hy[i] = fh[i * ncol + 1] / max_dim; }
-        for (int i = 0; i < ns; ++i) { sx[i] = fs[i * ncol] / max_dim; sy[i] = fs[i * ncol + 1] / max_dim; }
+        scaled_xy(fh, nh, ncol, max_dim, hx, hy);
+        scaled_xy(fs, ns, ncol, max_dim, sx, sy);
         const int kmax = min(nh, ns);
         if (kmax == 0) {
             stde[p] = NAN;          // the reference returns None
             return;
         }
         double simsum = 0.0;
-        for (int k = 1; k <= kmax; ++k) {
-            double dsum = 0.0;
-            const int nsw = ns - k + 1, nhw = nh - k + 1;
-            for (int s0 = 0; s0 < nsw; ++s0) {
-                double best = INFINITY;
-                for (int h0 = 0; h0 < nhw; ++h0) {
-                    const double d = numpy_sum(k, [&](int i) {
-                        const double dx = sx[s0 + i] - hx[h0 + i], dy = sy[s0 + i] - hy[h0 + i];
-                        return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-                    });
-                    best = d < best ? d : best;
-                }
-                dsum = __dadd_rn(dsum, best / (double)k);
-            }
-            simsum = __dadd_rn(simsum, exp(-(dsum / (double)nsw)));
-        }
+        for (int k = 1; k <= kmax; ++k) simsum = simsum + exp(-dist_k(hx, hy, nh, sx, sy, ns, k, false));
         stde[p] = simsum / (double)kmax;
     }
 }
@@ -111,9 +122,9 @@ __global__ __launch_bounds__(64) void sed_stde_kernel(const double* __restrict__
 // and four of the five values are bit-identical with the host restatement utils/evaltools/multimatch.py (its checker); the direction
 // value depends on atan2's last bit.  The DP keeps one row of costs and 2 bits of back-pointer per cell in per-thread scratch.
 // gate (may be NULL; sp_scan_multimatch_gated): the scanpaths' fixation counts BEFORE simplification.  With it the
-// "fewer than 3" rule looks at gate, and a simplified scanpath of 2 fixations = 1 saccade is scored (count < 2 or > MAXFIX: NaNs).
+// "fewer than 3" rule looks at gate, and a simplified scanpath of 2 fixations = 1 saccade is scored (count < 2: NaNs).  With or
+// without it, a count beyond MAXFIX (or below 0) gives five NaNs and reads no fixation.
 constexpr int MMSAC = MAXFIX - 1;                 // saccades per scanpath
-__device__ __forceinline__ double mm_hyp(double a, double b) { return __dsqrt_rn(__dadd_rn(__dmul_rn(a, a), __dmul_rn(b, b))); }
 __device__ double mm_median(double* v, int n) {   // numpy.median: sort, mean of the two middle values for an even count
     for (int i = 1; i < n; ++i) {
         const double x = v[i];
@@ -124,7 +135,7 @@ __device__ double mm_median(double* v, int n) {   // numpy.median: sort, mean of
         }
         v[j + 1] = x;
     }
-    return (n & 1) ? v[n / 2] : __dadd_rn(v[n / 2 - 1], v[n / 2]) / 2.0;
+    return (n & 1) ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2.0;
 }
 
 __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
@@ -133,19 +144,18 @@ __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict
                                                         const int* __restrict__ gate) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= npairs) return;
-    const int i1 = pairs[2 * p], i2 = pairs[2 * p + 1];
-    const int n1 = count[i1], n2 = count[i2];
+    const ScanPair<double> q = scan_pair(pairs, count, start, fix, ncol, p);
+    const int n1 = q.na, n2 = q.nb;
     double* o = out + 5 * (int64_t)p;
-    if (gate ? (gate[i1] < 3 || gate[i2] < 3 || n1 < 2 || n2 < 2 || n1 > MAXFIX || n2 > MAXFIX) : (n1 < 3 || n2 < 3)) {
+    if (q.bad() || (gate ? (gate[q.ia] < 3 || gate[q.ib] < 3 || n1 < 2 || n2 < 2) : (n1 < 3 || n2 < 3))) {
         for (int k = 0; k < 5; ++k) o[k] = NAN;
         return;
     }
-    const double* f1 = fix + start[i1] * ncol;
-    const double* f2 = fix + start[i2] * ncol;
+    const double *f1 = q.ra, *f2 = q.rb;
     const int n = n1 - 1, m = n2 - 1;             // saccades
     auto lenx = [&](const double* f, int i) { return f[(i + 1) * ncol] - f[i * ncol]; };
     auto leny = [&](const double* f, int i) { return f[(i + 1) * ncol + 1] - f[i * ncol + 1]; };
-    auto cost = [&](int i, int j) { return mm_hyp(lenx(f1, i) - lenx(f2, j), leny(f1, i) - leny(f2, j)); };
+    auto cost = [&](int i, int j) { return scan_dist(lenx(f1, i) - lenx(f2, j), leny(f1, i) - leny(f2, j)); };
     double row[MMSAC];                            // D of the current row (left part) / the previous row (right part)
     unsigned char prev[MMSAC * MMSAC];            // 0: came from (i, j-1), 1: (i-1, j), 2: (i-1, j-1)
     for (int i = 0; i < n; ++i) {
@@ -161,15 +171,15 @@ __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict
             double best = INFINITY;
             unsigned char arg = 0;
             if (j > 0) {
-                const double v = __dadd_rn(row[j - 1], c);
+                const double v = row[j - 1] + c;
                 if (v < best) { best = v; arg = 0; }
             }
             if (i > 0) {
-                const double v = __dadd_rn(up, c);
+                const double v = up + c;
                 if (v < best) { best = v; arg = 1; }
             }
             if (i > 0 && j > 0) {
-                const double v = __dadd_rn(diag, c);
+                const double v = diag + c;
                 if (v < best) { best = v; arg = 2; }
             }
             row[j] = best;
@@ -182,14 +192,14 @@ __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict
     int cnt = 0, i = n - 1, j = m - 1;
     while (true) {
         const double ax = lenx(f1, i), ay = leny(f1, i), bx = lenx(f2, j), by = leny(f2, j);
-        vec[cnt] = mm_hyp(ax - bx, ay - by);
+        vec[cnt] = scan_dist(ax - bx, ay - by);
         double t0 = atan2(ay, ax), t1 = atan2(by, bx);
         t0 = t0 < 0 ? PI + (PI + t0) : t0;
         t1 = t1 < 0 ? PI + (PI + t1) : t1;
         const double d = fabs(t0 - t1);
         ang[cnt] = d > PI ? 2 * PI - d : d;
-        ln[cnt] = fabs(mm_hyp(ax, ay) - mm_hyp(bx, by));
-        pos[cnt] = mm_hyp(f1[i * ncol] - f2[j * ncol], f1[i * ncol + 1] - f2[j * ncol + 1]);
+        ln[cnt] = fabs(scan_dist(ax, ay) - scan_dist(bx, by));
+        pos[cnt] = scan_dist(f1[i * ncol] - f2[j * ncol], f1[i * ncol + 1] - f2[j * ncol + 1]);
         const double d1 = f1[i * ncol + 2], d2 = f2[j * ncol + 2];
         dur[cnt] = fabs(d1 - d2) / fmax(d1, d2);
         ++cnt;
@@ -199,7 +209,7 @@ __global__ __launch_bounds__(64) void multimatch_kernel(const double* __restrict
         else if (a == 1) --i;
         else { --i; --j; }
     }
-    const double diagl = __dsqrt_rn(__dadd_rn(__dmul_rn(screen_w, screen_w), __dmul_rn(screen_h, screen_h)));
+    const double diagl = scan_dist(screen_w, screen_h);
     o[0] = 1 - mm_median(vec, cnt) / (2 * diagl);
     o[1] = 1 - mm_median(ang, cnt) / PI;
     o[2] = 1 - mm_median(ln, cnt) / diagl;
@@ -218,40 +228,25 @@ __global__ __launch_bounds__(64) void tde_kernel(const double* __restrict__ fix,
                                                  int hausdorff, double max_dim, double* __restrict__ tde, double* __restrict__ eucl) {
     const int p = blockIdx.x * 64 + threadIdx.x;
     if (p >= npairs) return;
-    const int ih = pairs[2 * p], is = pairs[2 * p + 1];
-    const int nh = count[ih], ns = count[is];
-    const double* fh = fix + start[ih] * ncol;
-    const double* fs = fix + start[is] * ncol;
+    const ScanPair<double> q = scan_pair(pairs, count, start, fix, ncol, p);
+    if (q.bad()) {
+        if (eucl) eucl[p] = NAN;
+        if (tde) tde[p] = NAN;
+        return;
+    }
+    const int nh = q.na, ns = q.nb;
+    const double *fh = q.ra, *fs = q.rb;
     if (eucl) {
         eucl[p] = nh != ns ? NAN : numpy_sum(nh, [&](int i) {
-            const double dx = fh[i * ncol] - fs[i * ncol], dy = fh[i * ncol + 1] - fs[i * ncol + 1];
-            return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
+            return scan_dist(fh[i * ncol] - fs[i * ncol], fh[i * ncol + 1] - fs[i * ncol + 1]);
         });
     }
     if (!tde) return;
     double hx[MAXFIX], hy[MAXFIX], sx[MAXFIX], sy[MAXFIX];
-    for (int i = 0; i < nh; ++i) { hx[i] = fh[i * ncol] / max_dim; hy[i] = fh[i * ncol + 1] / max_dim; }
-    for (int i = 0; i < ns; ++i) { sx[i] = fs[i * ncol] / max_dim; sy[i] = fs[i * ncol + 1] / max_dim; }
-    auto dist_k = [&](int kk, bool haus) {        // time_delay_embedding_distance(h, s, kk)
-        double acc = 0.0, worst = -INFINITY;
-        const int nsw = ns - kk + 1, nhw = nh - kk + 1;
-        for (int s0 = 0; s0 < nsw; ++s0) {
-            double best = INFINITY;
-            for (int h0 = 0; h0 < nhw; ++h0) {
-                const double d = numpy_sum(kk, [&](int i) {
-                    const double dx = sx[s0 + i] - hx[h0 + i], dy = sy[s0 + i] - hy[h0 + i];
-                    return __dsqrt_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)));
-                });
-                best = d < best ? d : best;
-            }
-            const double v = best / (double)kk;
-            acc = __dadd_rn(acc, v);
-            worst = v > worst ? v : worst;
-        }
-        return haus ? worst : acc / (double)nsw;
-    };
+    scaled_xy(fh, nh, ncol, max_dim, hx, hy);
+    scaled_xy(fs, ns, ncol, max_dim, sx, sy);
     if (k > 0) {
-        tde[p] = (nh < k || ns < k) ? NAN : dist_k(k, hausdorff != 0);
+        tde[p] = (nh < k || ns < k) ? NAN : dist_k(hx, hy, nh, sx, sy, ns, k, hausdorff != 0);
         return;
     }
     const int kmax = min(nh, ns);
@@ -260,7 +255,7 @@ __global__ __launch_bounds__(64) void tde_kernel(const double* __restrict__ fix,
         return;
     }
     double sum = 0.0;
-    for (int kk = 1; kk <= kmax; ++kk) sum = __dadd_rn(sum, dist_k(kk, false));
+    for (int kk = 1; kk <= kmax; ++kk) sum = sum + dist_k(hx, hy, nh, sx, sy, ns, kk, false);
     tde[p] = sum / (double)kmax;
 }
 

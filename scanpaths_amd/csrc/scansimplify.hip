@@ -1,8 +1,8 @@
 // MultiMatch scanpath simplification (Jarodzka et al. 2010, Dewhurst et al. 2012): successive saccades that point the
 // same way, and successive short saccades, are merged unless the fixation between them is long, until nothing changes.  Merging
 // saccades i and i + 1 DELETES fixation i + 1; the merged saccade is the difference of the two kept neighbours.  The result is an
-// ordinary, shorter scanpath in the fixation layout of scanmetrics.hip.  float64, every operation rounded on its own: this file is
-// compiled with floating-point contraction OFF (the pragma below) and uses the plain operators (scandist.hip says why).
+// ordinary, shorter scanpath in the fixation layout of scanmetrics.hip.  float64, every operation rounded on its own (the arithmetic
+// rule of scan_common.h: contraction OFF, plain operators).
 //
 // With n saccades, l_i = fixation i + 1 - fixation i and rho_i = sqrt(lx_i*lx_i + ly_i*ly_i), for 0 <= i <= n - 2:
 //   direction candidate  (lx_i*lx_{i+1} + ly_i*ly_{i+1}) > cos_tdir * (rho_i * rho_{i+1})  and  duration_{i+1} < tdur
@@ -19,12 +19,10 @@
 // The kernel guards itself: a wave whose index is >= nscan leaves before reading anything, a count outside 0 .. MAXFIX gives
 // count_out 0 and reads no fixation, lane l reads row l only for l < count.
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "scan_common.h"
 
 namespace {
 
-constexpr int MAXFIX = 64;        // = sp_scan_max_fixations() (scanmetrics.hip): one lane per fixation
 constexpr int MAXROUNDS = 64;     // 62 rounds can delete something, one more finds nothing to do
 
 // position of the j-th (from 0) set bit of mask; 63 at the most when there are fewer (callers do not use that lane)
@@ -63,11 +61,11 @@ __device__ __forceinline__ int simplify_pass(bool cand, int lane, int& cnt, doub
 __global__ __launch_bounds__(256) void scan_simplify_kernel(const double* __restrict__ fix, int ncol, const int64_t* __restrict__ start,
                                                             const int* __restrict__ count, int nscan, double cos_tdir, double tdur,
                                                             double tamp, double* __restrict__ fix_out, int* __restrict__ count_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= nscan) return;                                    // the whole wave leaves
+    int lane;
+    int64_t s;
+    if (!scan_wave_item(nscan, lane, s)) return;
     int cnt = count[s];
-    if (cnt < 0 || cnt > MAXFIX) {                             // beyond the kernel limit: no fixation is read
+    if (scan_count_bad(cnt)) {                                 // beyond the kernel limit: no fixation is read
         if (lane == 0) count_out[s] = 0;
         return;
     }
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(256) void scan_simplify_kernel(const double* __rest
         int gone = 0;
         if (use_dir && cnt >= 3) {
             const double lx = __shfl_down(x, 1, 64) - x, ly = __shfl_down(y, 1, 64) - y;
-            const double rho = __builtin_sqrt(lx * lx + ly * ly);
+            const double rho = scan_dist(lx, ly);
             const double nx = __shfl_down(lx, 1, 64), ny = __shfl_down(ly, 1, 64), nrho = __shfl_down(rho, 1, 64);
             const double nd = __shfl_down(d, 1, 64);           // the duration of fixation lane + 1
             const bool cand = lane <= cnt - 3 && (lx * nx + ly * ny) > cos_tdir * (rho * nrho) && nd < tdur;
@@ -92,7 +90,7 @@ __global__ __launch_bounds__(256) void scan_simplify_kernel(const double* __rest
         }
         if (cnt >= 3) {
             const double lx = __shfl_down(x, 1, 64) - x, ly = __shfl_down(y, 1, 64) - y;
-            const double rho = __builtin_sqrt(lx * lx + ly * ly);
+            const double rho = scan_dist(lx, ly);
             const double nd = __shfl_down(d, 1, 64);
             const bool cand = lane <= cnt - 3 && rho < tamp && nd < tdur;
             gone += simplify_pass(cand, lane, cnt, x, y, d);

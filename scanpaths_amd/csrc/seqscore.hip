@@ -1,8 +1,8 @@
 // Sequence score (Yang et al. 2020) and fixation edit distance (Mondal et al. 2023) on mean-shift clusters: flat-kernel
 // mean shift (Comaniciu & Meer 2002) of groups of fixations, the cluster-label strings of scanpaths under a group's centres, and the
 // Needleman-Wunsch score / Levenshtein distance of pairs of such strings.  Everything is float64 and follows the definitions of §17
-// operation by operation: this file is compiled with floating-point contraction OFF (the pragma below) and uses the plain operators
-// (scandist.hip says why the __dmul_rn intrinsics do not give that), and every sum runs left to right in index order.
+// operation by operation (the arithmetic rule of scan_common.h: contraction OFF, plain operators), and every sum runs left to right in
+// index order.
 //
 //   meanshift_kernel: one 256-thread block per group.  x and y are staged once into LDS; ONE THREAD PER SEED (seeds tid, tid + 256, ..)
 //     walks the points serially, which is the definition's index-order sum; all lanes read the same LDS address in the same step
@@ -18,12 +18,10 @@
 // The kernels guard themselves: a group of more than MAXPTS (or fewer than 0) points gets ncentres -1 and labels -1 and none of its
 // points is read; a scanpath of more than MAXFIX (or fewer than 0) fixations gets no labels and NaN for its pairs.
 #include "common.h"
-
-#pragma clang fp contract(off)
+#include "scan_common.h"
 
 namespace {
 
-constexpr int MAXFIX = 64;        // = sp_scan_max_fixations(): one lane per fixation
 constexpr int MAXPTS = 1024;      // = sp_meanshift_max_points(): x, y (16 KB) + the seeds' results (20 KB) + order and kept lists (8 KB) + flags
 
 __device__ __forceinline__ double sq_max(double a, double b) { return b > a ? b : a; }
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(256) void meanshift_kernel(const double* __restrict
             const double dx = nx - cx, dy = ny - cy;
             cx = nx;
             cy = ny;
-            if (__builtin_sqrt(dx * dx + dy * dy) <= stop || it == max_iter) break;
+            if (scan_dist(dx, dy) <= stop || it == max_iter) break;
         }
         ek[s] = k;
         ecx[s] = k ? cx : 0.0;                         // an entry without a result sorts last and ends the walk below
@@ -142,11 +140,11 @@ __global__ __launch_bounds__(256) void cluster_strings_kernel(const double* __re
                                                               const int* __restrict__ count, const int* __restrict__ group, int nscan,
                                                               const double* __restrict__ centres, const int64_t* __restrict__ gstart,
                                                               const int* __restrict__ ncentres, int* __restrict__ labels_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t s = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (s >= nscan) return;
+    int lane;
+    int64_t s;
+    if (!scan_wave_item(nscan, lane, s)) return;
     const int n = count[s];
-    if (n > MAXFIX || lane >= n) return;               // beyond the limit: nothing is read or written (its pairs score NaN)
+    if (scan_count_bad(n) || lane >= n) return;        // beyond the limit: nothing is read or written (its pairs score NaN)
     const int64_t row = start[s] + lane;
     const int g = group[s];
     const int K = ncentres[g];
@@ -170,16 +168,16 @@ __global__ __launch_bounds__(256) void cluster_strings_kernel(const double* __re
 __global__ __launch_bounds__(256) void sequence_kernel(const int* __restrict__ labels, const int64_t* __restrict__ start,
                                                        const int* __restrict__ count, const int* __restrict__ pairs, int npairs, double gap,
                                                        double* __restrict__ ss, double* __restrict__ fed) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= npairs) return;                                   // the whole wave leaves
-    const int ia = pairs[2 * p], ib = pairs[2 * p + 1];
-    const int n = count[ia], m = count[ib];
-    bool bad = n < 0 || m < 0 || n > MAXFIX || m > MAXFIX;     // beyond the kernel limit: NaN, nothing else is read
+    int lane;
+    int64_t p;
+    if (!scan_wave_item(npairs, lane, p)) return;
+    const ScanPair<int> q = scan_pair(pairs, count, start, labels, 1, p);      // rows of one label
+    const int n = q.na, m = q.nb;
+    bool bad = q.bad();                                        // beyond the kernel limit: NaN, no label is read
     int a = 0, b = 0;                                          // a[lane], b[lane]
     if (!bad) {
-        if (lane < n) a = labels[start[ia] + lane];
-        if (lane < m) b = labels[start[ib] + lane];
+        if (lane < n) a = q.ra[lane];
+        if (lane < m) b = q.rb[lane];
         bad = __ballot(a < 0 || b < 0) != 0ull;                // a fixation without a cluster
     }
     if (bad) {
