@@ -620,7 +620,13 @@ int sp_scan_likelihood(const float* probs, const float* mu, const float* sigma2,
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.
  * sp_sample_actions: per (b,t) masked categorical draw (terminate action 0 excluded for t < min_length), probability of the
- *   chosen action from the unmasked distribution, duration = exp(eps*sigma2 + mu); Philox4x32-10(seed; row).
+ *   chosen action from the unmasked distribution, duration = exp(eps*sigma2 + mu); Philox4x32-10(seed; row): counter
+ *   (row & 0xffffffff, row >> 32, 0, 0), key (seed & 0xffffffff, seed >> 32), u = min(((word >> 8) + 0.5f) * 2^-24, 1 - 2^-24)
+ *   in (0,1); word 0 draws the action, words 1 and 2 are eps' Box-Muller pair sqrt(-2 ln u1) * cos(2 pi u2).
+ *   The draw is an inverse CDF in float32: the first allowed entry a with p[a] > 0 whose running sum reaches u * (sum of the
+ *   allowed entries); a row without allowed mass yields the first allowed action (1 while terminate is masked, else 0).
+ *   A scan that leaves its 1/256th segment of the row short of the target by rounding goes on to the next positive entry;
+ *   only a scan that reaches the end of the row takes the row's last positive entry.
  * sp_generate_scanpath: first-terminate scan -> length [B] (0 -> T quirk), masks [B][T], fix [B][T][3] = (x, y, duration) in
  *   pixels for the nfix[b] leading fixations.
  * ---------------------------------------------------------------------------------------------- */

@@ -5,8 +5,15 @@
 //                     reference's quirk, :26-27), and the first-terminate scan for the scanpath length (:29-34, incl. the
 //                     "terminate at t=0 -> T" quirk).
 //   generate_scanpath: index -> pixel mapping ((a-1)%Wm+0.5)*W/Wm, ((a-1)/Wm+0.5)*H/Hm, masks (:48-77).
-// RNG: Philox4x32-10 keyed by (seed), counter = (row, draw) -- reproducible for a given seed on any device count; the
-// stream necessarily differs from torch's (the reference's CPU and CUDA streams differ from each other too).
+//                     The draw is an inverse CDF: with u in (0,1) and total = the sum of the allowed entries, the chosen action
+//                     is the first allowed entry a with p[a] > 0 whose running sum reaches u * total (float32 sums: a 256-way
+//                     coarse scan over segment sums, then a serial scan from the chosen segment's first entry).  A row without
+//                     allowed mass yields the first allowed action (1 while terminate is masked, else 0).  A scan that leaves
+//                     its segment short of the target by rounding goes on to the next positive entry; only a scan that
+//                     reaches the end of the row takes the row's last positive entry.
+// RNG: Philox4x32-10 keyed by (seed), counter = (row, 0, 0): word 0 draws the action, words 1 and 2 the duration's Box-Muller
+// pair -- reproducible for a given seed on any device count; the stream necessarily differs from torch's (the reference's CPU
+// and CUDA streams differ from each other too).
 #include "common.h"
 
 namespace {
@@ -27,7 +34,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uin
         k1 += 0xBB67AE85u;
     }
 }
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f); }   // (0,1)
+// (0,1).  From x >> 8 = 2^23 on the "+ 0.5f" is a tie of float32 and rounds to even; for x >> 8 = 2^24 - 1 that is 2^24, i.e. 1.0f:
+// the min keeps that one value (256 of the 2^32 words) at the largest float below 1, every other word keeps its value
+__device__ __forceinline__ float u01(uint32_t x) { return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f); }
 
 // one block per (b,t) row
 __global__ __launch_bounds__(256) void sample_rows_kernel(const float* probs, const float* mu, const float* sigma2, int T, int A,
@@ -55,13 +64,15 @@ __global__ __launch_bounds__(256) void sample_rows_kernel(const float* probs, co
             if (run + part[i] >= target) { seg = i; break; }
             run += part[i];
         }
+        // fine search from the segment's first entry.  It re-adds the entries one by one onto `run`, which rounds differently from
+        // adding the segment's own sum part[seg]: the scan can leave the segment an ulp short of target.  The draw then belongs to
+        // the next positive entry, so the scan simply runs on to the end of the row.
         int chosen = -1;
-        const int b0 = seg * per, b1 = min(A, b0 + per);
-        for (int a = max(b0, a_lo); a < b1; ++a) {
+        for (int a = max(seg * per, a_lo); a < A; ++a) {
             run += p[a];
             if (run >= target && p[a] > 0.f) { chosen = a; break; }
         }
-        if (chosen < 0) {                                        // rounding fell off the end: last positive entry
+        if (chosen < 0) {                                        // rounding fell off the end of the ROW: last positive entry
             for (int a = A - 1; a >= a_lo; --a)
                 if (p[a] > 0.f) { chosen = a; break; }
             if (chosen < 0) chosen = a_lo;
