@@ -122,7 +122,7 @@ FUSION_COUNTS = {"lstm_bwd_split": 0, "bn_bwd_split_operand": 0, "gateconv_lstm"
                  "bn_fwd_split": 0, "bn_fwd_split_operand": 0, "bn_skip_z": 0, "bn_bwd_split": 0, "bn_skip_dx": 0,
                  "conv_bn_stats": 0, "grad_merge": 0, "rank1_dsp_split": 0, "rank1_dwc_split": 0, "lstm_skip_dpre": 0, "wgrad_multi": 0,
                  "row_sparse_bwd": 0, "fan_in_rows": 0, "direct_grad": 0, "output_gate": 0, "skinny_gemm": 0, "async_dgrad": 0,
-                 "drt_fwd_batched": 0, "rank1_fused": 0}
+                 "drt_fwd_batched": 0, "drt_live_rows": 0, "rank1_fused": 0}
 
 
 # ---- parameter gradients written straight into the optimizer's flat gradient buffer -------------------------------------------------
@@ -344,6 +344,18 @@ def _one(device) -> torch.Tensor:
     t = _ONES.get(key)
     if t is None:
         t = _ONES[key] = torch.ones(2, dtype=torch.float32, device=device)
+    return t
+
+
+_NANS = {}
+
+
+def _nan(device) -> torch.Tensor:
+    """device scalar NaN: what a deferred drt_direct node's placeholder output expands (stride 0; never written)"""
+    key = hip.device_index(device)
+    t = _NANS.get(key)
+    if t is None:
+        t = _NANS[key] = torch.full((), float("nan"), dtype=torch.float32, device=device)
     return t
 
 
@@ -1562,13 +1574,20 @@ def lstm_cell(xg, hg, c_prev):
     return _LstmCell.apply(xg, hg, c_prev)
 
 
+def _h_dest(h_out, like):
+    """the caller's buffer for a cell's hidden state (decode(): slice t of the [T, B, Hm, Wm, C] buffer that drt_heads_batched reads in one
+    launch), as a fresh alias: autograd hands an INPUT that a Function returns back as a new tensor object, without the _sp_ marks"""
+    if h_out.shape != like.shape or h_out.dtype != like.dtype or h_out.device != like.device or not h_out.is_contiguous():
+        raise RuntimeError(f"scanpaths_amd: h_out must be a contiguous {tuple(like.shape)} {like.dtype} tensor on {like.device}")
+    return h_out.view(like.shape)
+
+
 class _LstmCellRank1(Function):
     """ConvLSTM cell with the rank-1 gate terms fused into the pointwise kernel (sp_lstm_rank1_fwd):
          pre[b,p,n] = xg + hg + sum_k spcol[b,p,k] * wc[b,n,k]   (n < 3C: the i/f/o gates)
     xg / hg [B,Hm,Wm,4C] (hg may be None at step 0), spcol [B,P,KP], wc [B,3C,KP]."""
     @staticmethod
-    def forward(ctx, xg, hg, c_prev, spcol, wc, step=None, hslot=None):
-        # hslot: (DrtBatch, t) -- the hidden state is written into slot t of the batch's [T, B, Hm, Wm, C] buffer (see DrtBatch)
+    def forward(ctx, xg, hg, c_prev, spcol, wc, step=None, h_out=None):
         ctx.step = step
         xg = xg.contiguous()
         hg = hg.contiguous() if hg is not None else None
@@ -1582,7 +1601,7 @@ class _LstmCellRank1(Function):
         shp = xg.shape[:-1] + (Cc,)
         gates = torch.empty_like(xg)
         c = torch.empty(shp, dtype=torch.float32, device=xg.device)
-        h = torch.empty(shp, dtype=torch.float32, device=xg.device) if hslot is None else hslot[0].hbuf(hslot[1], c)
+        h = torch.empty(shp, dtype=torch.float32, device=xg.device) if h_out is None else _h_dest(h_out, c)
         hint = _amax_hint(xg.device)
         check(hip.lib().sp_lstm_rank1_fwd(ptr(xg), ptr(hg), ptr(c_prev), ptr(spcol), ptr(wc), B, P, Cc, KP, ptr(gates), ptr(c),
                                           ptr(h), _hint_ptr(hint), hip.stream()), "sp_lstm_rank1_fwd")
@@ -1733,8 +1752,8 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
     return dpre, dcp, dsp, dwc
 
 
-def lstm_cell_rank1(xg, hg, c_prev, spcol, wc, step=None, hslot=None):
-    return _LstmCellRank1.apply(xg, hg, c_prev, spcol, wc, step, hslot)
+def lstm_cell_rank1(xg, hg, c_prev, spcol, wc, step=None, h_out=None):
+    return _LstmCellRank1.apply(xg, hg, c_prev, spcol, wc, step, h_out)
 
 
 
@@ -1755,7 +1774,7 @@ class _GateConvLstm(Function):
     (sp_gateconv_lstm_f16x2), so the [B,Hm,Wm,4C] h-gate tensor is never materialised.  Backward = _LstmCellRank1's followed by
     _Conv2d's (same kernels as the unfused pair)."""
     @staticmethod
-    def forward(ctx, h_prev, w_h, xg, c_prev, spcol, wc, wcache, step=None, hslot=None):
+    def forward(ctx, h_prev, w_h, xg, c_prev, spcol, wc, wcache, step=None, h_out=None):
         ctx.step = step
         h_prev, xg, c_prev = h_prev.contiguous(), xg.contiguous(), c_prev.contiguous()
         spcol, wc = spcol.contiguous(), wc.contiguous()
@@ -1770,7 +1789,7 @@ class _GateConvLstm(Function):
             raise RuntimeError("scanpaths_amd: the fused gate conv expects the hidden state's operand with a per-tensor scale")
         gates = torch.empty_like(xg)
         c = torch.empty_like(c_prev)
-        h = torch.empty_like(c_prev) if hslot is None else hslot[0].hbuf(hslot[1], c_prev)          # (DrtBatch, t): see _LstmCellRank1
+        h = torch.empty_like(c_prev) if h_out is None else _h_dest(h_out, c_prev)
         hint = _amax_hint(xg.device)
         d = g.fwd_desc(w_scale_rows=int(wsplit.kind == "rows"))
         cbounds = _cell_bounds(c_prev, c)
@@ -1866,8 +1885,8 @@ class _GateConvLstm(Function):
         return dhp, dw, dpre, dcp, dsp, dwc, None, None, None
 
 
-def gateconv_lstm(h_prev, w_h, xg, c_prev, spcol, wc, wcache=None, step=None, hslot=None):
-    return _GateConvLstm.apply(h_prev, w_h, xg, c_prev, spcol, wc, wcache, step, hslot)
+def gateconv_lstm(h_prev, w_h, xg, c_prev, spcol, wc, wcache=None, step=None, h_out=None):
+    return _GateConvLstm.apply(h_prev, w_h, xg, c_prev, spcol, wc, wcache, step, h_out)
 
 
 class _Im2col(Function):
@@ -2224,22 +2243,23 @@ def sal_gather(T, hmap, nsel, nsrc, step=None):
 class _DrtDirect(Function):
     """h [B,Hm,Wm,C], W11 [nheads,ncls,121,C], cbsum [nheads,ncls] -> Dpre [nsel,B,dh*dw]"""
     @staticmethod
-    def forward(ctx, h, W11, cbsum, hmap, nsel, step=None, batch=None):
-        # batch (DrtBatch): the forward values of ALL decode steps are computed in one launch behind the loop (drt_heads_batched): this
-        # node then only reserves the step's output and keeps what its backward -- which stays a per-step launch inside the backward
-        # recurrence, beside the h-gate conv's data gradient -- needs
-        ctx.step, ctx.batch = step, batch
+    def forward(ctx, h, W11, cbsum, hmap, nsel, step=None, deferred=False):
+        # deferred: the forward values of ALL decode steps are computed in one launch behind the loop (drt_heads_batched).  This node then
+        # launches nothing and returns a placeholder that nothing ever writes -- every element reads NaN -- whose only job is to be the graph
+        # edge that carries the step's site gradient to this backward, which stays a per-step launch inside the backward recurrence,
+        # beside the h-gate conv's data gradient
+        ctx.step = step
         h = h.contiguous()
         W11 = W11.contiguous()
         cbsum = cbsum.contiguous()
         B, Hm, Wm, C_ = h.shape
         S = ((Hm + 4 - 7) // 5 + 1) * ((Wm + 4 - 7) // 5 + 1)
-        if batch is None:
+        if deferred:
+            Dpre = _nan(h.device).expand(nsel, B, S)
+        else:
             Dpre = torch.empty((nsel, B, S), dtype=torch.float32, device=h.device)
             check(hip.lib().sp_drt_direct_fwd(ptr(h), ptr(W11), ptr(cbsum), ptr(hmap), B, Hm, Wm, C_, nsel, ptr(Dpre), hip.stream()),
                   "sp_drt_direct_fwd")
-        else:
-            ctx.slot, Dpre = batch.add(h, W11, cbsum, hmap, nsel, S)          # this step's slice of the batch's [T, nsel, B, S] buffer
         ctx.cfg = (B, Hm, Wm, C_, nsel, W11.shape[0], tuple(W11.shape), tuple(cbsum.shape))
         ctx.save_for_backward(h, W11, hmap)
         return Dpre
@@ -2248,13 +2268,15 @@ class _DrtDirect(Function):
     def backward(ctx, dD):
         B, Hm, Wm, C_, nsel, nheads, wshape, cshape = ctx.cfg
         h, W11, hmap = ctx.saved_tensors
+        # (slot, sample) pairs whose duration gradient is exactly zero -- AiR's unselected head, the step at a scanpath's end -- as the
+        # batched duration backward found them for THIS gradient tensor (_sp_live, a hint: a hook that replaces the gradient drops it and
+        # the launches are dense again): skipped like the dead samples, bit-identical sums
+        live = getattr(dD, "_sp_live", None) if ROW_SPARSITY else None
+        FUSION_COUNTS["drt_live_rows"] += int(live is not None)
         dD = dD.contiguous()
         L = hip.lib()
         dh = dW = dcs = None
         rc = rows_ctx(ctx.step, B)      # samples behind their last loss step: exactly-zero dD -> nothing computed for them, h not read
-        # (slot, sample) pairs whose duration gradient is exactly zero -- AiR's unselected head, the step at a scanpath's end -- as the
-        # batched duration backward found them (drt_heads_batched): skipped like the dead samples, bit-identical sums
-        live = ctx.batch.live_of(ctx.slot) if (ctx.batch is not None and ROW_SPARSITY) else None
         rl, rs = (ptr(rc.last), int(ctx.step)) if rc is not None else (None, 0)
         if ctx.needs_input_grad[0]:
             dh = torch.empty_like(h)
@@ -2269,71 +2291,35 @@ class _DrtDirect(Function):
         return dh, dW, dcs, None, None, None, None
 
 
-def drt_direct(h, W11, cbsum, hmap, nsel, step=None, batch=None):
-    return _DrtDirect.apply(h, W11, cbsum, hmap, nsel, step, batch)
-
-
-class DrtBatch:
-    """The duration sites of ALL decode steps in one forward launch (round 6).  Nothing in the recurrence reads the duration branch of
-    predict_head (AiR/models/baseline_attention.py:155-159: mu and sigma2 only leave the model), but per step its window kernel stood in
-    the serial gap between two fused h-gate launches (112 us of 468, L2-bound).  The decode loop's drt_direct(..., batch=this) nodes only
-    register their operands; drt_heads_batched() then runs sp_drt_direct_fwd ONCE over the T x B hidden states -- contiguous when the cell
-    kernels wrote them into hbuf() -- and the duration part of the head epilogue once over T x nheads virtual heads.  Backward: the batched
-    node turns d(mu), d(sigma2) into the site gradients of every step (one launch) and into `live` flags; the per-step nodes' data / weight
-    gradient launches stay where they were, inside the backward recurrence beside the h-gate conv's data gradient."""
-
-    def __init__(self, T):
-        self.T, self.items, self.live, self.buf, self.D = T, [], None, None, None
-
-    def hbuf(self, t, like):
-        """the slot of decode step t in ONE [T, B, Hm, Wm, C] buffer for the hidden states (cell kernels write h_t there)"""
-        if self.buf is None:
-            self.buf = torch.empty((self.T,) + tuple(like.shape), dtype=torch.float32, device=like.device)
-        return self.buf[t]
-
-    def add(self, h, W11, cbsum, hmap, nsel, S):
-        """register decode step len(items); returns (slot, its [nsel, B, S] slice of the site buffer drt_heads_batched fills)"""
-        if self.D is None:
-            self.D = torch.empty((self.T, nsel, h.shape[0], S), dtype=torch.float32, device=h.device)
-        slot = len(self.items)
-        if slot >= self.T:
-            raise RuntimeError("scanpaths_amd: DrtBatch got more decode steps than it was built for")
-        self.items.append((h, W11, cbsum, hmap, nsel))
-        return slot, self.D[slot]
-
-    def live_of(self, slot):
-        return None if self.live is None else self.live[slot]
+def drt_direct(h, W11, cbsum, hmap, nsel, step=None, deferred=False):
+    return _DrtDirect.apply(h, W11, cbsum, hmap, nsel, step, deferred)
 
 
 class _DrtHeadsBatched(Function):
-    """placeholders Dpre_t [nsel,B,S] of the T per-step drt_direct nodes (graph edges; their contents are produced HERE) + cb, w2, b2 ->
-    mu, sigma2 [nsel, B, T]"""
+    """The duration sites of ALL decode steps in one forward launch (round 6).  Nothing in the recurrence reads the duration branch of
+    predict_head (AiR/models/baseline_attention.py:155-159: mu and sigma2 only leave the model), but per step its window kernel stood in
+    the serial gap between two fused h-gate launches (112 us of 468, L2-bound).  h_all [T,B,Hm,Wm,C] (the cell kernels wrote h_t into its
+    slices), W11, cbsum, hmap (values only: their gradients and h's go through the per-step nodes), cb, w2, b2 + the placeholders
+    Dpre_t [nsel,B,S] of the T deferred drt_direct nodes (graph edges, never read) -> mu, sigma2 [nsel, B, T]: sp_drt_direct_fwd ONCE over
+    the T x B hidden states, the duration part of the head epilogue once over T x nsel virtual heads.  Backward: d(mu), d(sigma2) ->
+    the site gradients of every step (one launch), each carrying its `live` flags (_sp_live); the per-step nodes' data / weight gradient
+    launches stay where they were."""
     @staticmethod
-    def forward(ctx, batch, cb, w2, b2, HC, per_sample, *dpres):
-        items = batch.items
-        Tn = len(items)
-        assert Tn == len(dpres) and Tn >= 1
-        h0, W11, cbsum, hmap, nsel = items[0]
-        B, Hm, Wm, C_ = h0.shape
-        S = dpres[0].shape[-1]
-        dev = h0.device
+    def forward(ctx, h_all, W11, cbsum, hmap, cb, w2, b2, HC, per_sample, *dpres):
+        Tn, B, Hm, Wm, C_ = h_all.shape
+        if len(dpres) != Tn or Tn < 1:
+            raise RuntimeError(f"scanpaths_amd: drt_heads_batched got {len(dpres)} duration-site placeholders for {Tn} hidden states")
+        nsel, _, S = dpres[0].shape
+        dev = h_all.device
         L = hip.lib()
-        hs = [it[0] for it in items]
-        nb = h0.numel() * 4
-        contiguous = all(h.is_contiguous() and h.data_ptr() == hs[0].data_ptr() + t * nb for t, h in enumerate(hs))
-        same_w = all(it[1].data_ptr() == W11.data_ptr() and it[2].data_ptr() == cbsum.data_ptr() for it in items)
-        D = batch.D[:Tn]          # [T, nsel, B, S]: the per-step nodes' outputs are its slices
-        if contiguous and same_w and Tn > 1:
-            Dall = torch.empty((nsel, Tn * B, S), dtype=torch.float32, device=dev)
-            hm = hmap.repeat(Tn, 1).contiguous()
-            check(L.sp_drt_direct_fwd(ptr(hs[0]), ptr(W11), ptr(cbsum), ptr(hm), Tn * B, Hm, Wm, C_, nsel, ptr(Dall), hip.stream()),
-                  "sp_drt_direct_fwd (batched)")
-            D.copy_(Dall.view(nsel, Tn, B, S).permute(1, 0, 2, 3))
-            FUSION_COUNTS["drt_fwd_batched"] += 1
-        else:          # (hidden states that were not written into DrtBatch.hbuf: one launch per step, still behind the loop)
-            for t, (h, w11, cs, hm_, _) in enumerate(items):
-                check(L.sp_drt_direct_fwd(ptr(h.contiguous()), ptr(w11), ptr(cs), ptr(hm_), B, Hm, Wm, C_, nsel, ptr(D[t]), hip.stream()),
-                      "sp_drt_direct_fwd")
+        h_all, W11, cbsum = h_all.contiguous(), W11.contiguous(), cbsum.contiguous()
+        Dall = torch.empty((nsel, Tn * B, S), dtype=torch.float32, device=dev)
+        hm = hmap.repeat(Tn, 1).contiguous()
+        check(L.sp_drt_direct_fwd(ptr(h_all), ptr(W11), ptr(cbsum), ptr(hm), Tn * B, Hm, Wm, C_, nsel, ptr(Dall), hip.stream()),
+              "sp_drt_direct_fwd (batched)")
+        D = torch.empty((Tn, nsel, B, S), dtype=torch.float32, device=dev)
+        D.copy_(Dall.view(nsel, Tn, B, S).permute(1, 0, 2, 3))
+        FUSION_COUNTS["drt_fwd_batched"] += 1
         cb = cb.contiguous()
         w2c = w2.detach().contiguous()
         b2 = b2.contiguous()
@@ -2344,7 +2330,6 @@ class _DrtHeadsBatched(Function):
         drt = torch.empty((NH, B, S), dtype=torch.float32, device=dev)
         check(L.sp_head_finish_fwd(None, B, Hm, Wm, 0, NH, HC, ptr(cb_all), int(per_sample), ptr(w2c), ptr(b2), 0, None, None, ptr(mu),
                                    ptr(s2), ptr(drt), ptr(D), 2, 2, hip.stream()), "sp_head_finish_fwd (duration)")
-        ctx.batch = batch
         ctx.cfg = (Tn, nsel, B, Hm, Wm, S, HC, per_sample, tuple(w2.shape), tuple(cb.shape))
         ctx.save_for_backward(s2, drt, w2c)
         to_bt = lambda v: v.view(Tn, nsel, B).permute(1, 2, 0).contiguous()          # [nsel, B, T]
@@ -2366,7 +2351,6 @@ class _DrtHeadsBatched(Function):
         check(hip.lib().sp_head_finish_bwd(None, 0, None, ptr(dmu), ptr(ds2), None, None, ptr(s2), ptr(drt), B, Hm, Wm, 0, NH, HC, ptr(w2c), 0,
                                            None, ptr(dcbp), ptr(dw2p), ptr(db2p), ptr(ddpre), 2, 2, ptr(live), hip.stream()),
               "sp_head_finish_bwd (duration)")
-        ctx.batch.live = live.view(Tn, nsel * B)          # row t: the flags [nsel][B] of decode step t's drt_direct node
         # partial sums over the samples (and the T steps): composed bias (only drt_layer_1.bias' entry is non-zero), drt_layer_2
         if per_sample:
             dcb = dcbp.view(B, Tn, nsel * HC).sum(1).view(cbshape)
@@ -2374,13 +2358,15 @@ class _DrtHeadsBatched(Function):
             dcb = _colsum_any(dcbp, NH * HC).view(Tn, nsel * HC).sum(0).view(cbshape)
         dw2 = _colsum_any(dw2p, NH * 2 * S).view(NH, 2 * S).sum(0)
         db2 = _colsum_any(db2p, NH * 2).view(NH, 2).sum(0)
-        dd = ddpre.view(Tn, nsel, B, S)
-        return (None, dcb, dw2.reshape(w2shape), db2.reshape(2), None, None) + tuple(dd[t] for t in range(Tn))
+        dd = list(ddpre.view(Tn, nsel, B, S).unbind(0))
+        for d, lv in zip(dd, live.view(Tn, nsel * B).unbind(0)):
+            d._sp_live = lv          # the flags [nsel][B] of THIS gradient ride on it to decode step t's drt_direct node
+        return (None, None, None, None, dcb, dw2.reshape(w2shape), db2.reshape(2), None, None) + tuple(dd)
 
 
-def drt_heads_batched(batch: DrtBatch, dpres, cb, w2, b2, HC, per_sample=False):
-    """mu, sigma2 [nsel, B, T] of all decode steps registered with `batch` (see DrtBatch)"""
-    return _DrtHeadsBatched.apply(batch, cb, w2, b2, HC, per_sample, *dpres)
+def drt_heads_batched(dpres, h_all, W11, cbsum, hmap, cb, w2, b2, HC, per_sample=False):
+    """mu, sigma2 [nsel, B, T] of all decode steps: dpres = the T deferred drt_direct outputs, h_all [T,B,Hm,Wm,C] their hidden states"""
+    return _DrtHeadsBatched.apply(h_all, W11.detach(), cbsum.detach(), hmap, cb, w2, b2, HC, per_sample, *dpres)
 
 
 # ----------------------------------------------------------------------------------------------------

@@ -944,6 +944,7 @@ def test_batched_duration_branch_equals_the_per_step_form(task, monkeypatch):
             loss.backward()
             torch.cuda.synchronize()
             assert F.FUSION_COUNTS["drt_fwd_batched"] == (1 if batched else 0), F.FUSION_COUNTS
+            assert F.FUSION_COUNTS["drt_live_rows"] == (T if batched and sparse else 0), F.FUSION_COUNTS
             res[(batched, sparse)] = ({k: v.detach().clone() for k, v in pred.items()}, float(loss), _grads(model))
     for sparse in (True, False):
         pa, la, ga = res[(False, sparse)]

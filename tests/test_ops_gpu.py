@@ -454,6 +454,152 @@ def test_direct_head_matches_two_conv_formulation(hw, per_sample):
     _close(b2d.grad, b2r.grad, 3e-5, "db2")
 
 
+_DRT_CASES = [((12, 13), True), ((30, 40), False)]          # nsel 1 (S = 6), nsel 2: the two smallest of the cases above
+
+
+def _drt_case(hw, per_sample):
+    """operands of the duration branch as test_direct_head_matches_two_conv_formulation sets them up, for T = 3 hidden states"""
+    from scanpaths_amd import functional as F
+    Hm, Wm = hw
+    T, B, C_, HC = 3, 3, 32, 64
+    nsrc, nsel = (3, 1) if per_sample else (2, 2)
+    S = ((Hm + 4 - 7) // 5 + 1) * ((Wm + 4 - 7) // 5 + 1)
+    dev = _dev()
+    G = _rand(nsrc * HC, 5, 5, C_, seed=2, scale=1.0 / math.sqrt(25 * C_))
+    G.view(nsrc, HC, 5, 5, C_)[:, 51:] = 0
+    cbh = _rand(nsrc, HC, seed=3, scale=0.1).to(dev)
+    src = torch.tensor([[2], [0], [2]]) if per_sample else torch.arange(2).repeat(B, 1)      # [B, nsel]
+    hmap = src.to(torch.int32).to(dev).contiguous()
+    Gd = G.to(dev).permute(0, 3, 1, 2)
+    Gp = Gd.permute(0, 2, 3, 1).reshape(nsrc, HC, 25, C_)
+    R = (nsrc * 50 + 63) // 64 * 64
+    Wsal = torch.cat([Gp[:, :2].reshape(nsrc * 50, C_), torch.zeros(R - nsrc * 50, C_, device=dev)], 0).view(R, C_, 1, 1)
+    with torch.no_grad():
+        W11, cbsum = F.compose11(Gd, cbh, nsrc, HC, (Hm, Wm))
+    cb = cbh.index_select(0, hmap[:, 0].long()).view(B, 1, HC) if per_sample else cbh
+    return dict(T=T, B=B, HC=HC, nsrc=nsrc, nsel=nsel, S=S, per_sample=per_sample, hmap=hmap, Wsal=Wsal, W11=W11, cbsum=cbsum, cb=cb,
+                h=_rand(T, B, Hm, Wm, C_, seed=1).to(dev), w2=_rand(2, S, seed=4, scale=0.2).to(dev), b2=_rand(2, seed=5, scale=0.1).to(dev))
+
+
+def _drt_zero_pattern(c, g, which):
+    """upstream gradient [nsel, B, T] with exact zeros: one whole slot (where there are two) and single (sample, step) pairs"""
+    g = g.clone()
+    if c["nsel"] == 2:
+        g[1 - which] = 0
+    for b, t in (((0, 1),), ((2, 0), (1, 2)))[which]:
+        g[:, b, t] = 0
+    return g.to(_dev())
+
+
+def _drt_graph(c, batched, per_step_weights=False):
+    """mu, sigma2 [nsel, B, T] of T hidden states -- leaves that alias the slices of one [T, B, Hm, Wm, C] buffer -- in the batched form
+    (deferred drt_direct x T + drt_heads_batched) or the per-step form, built as ScanpathModel._heads_step builds its duration half"""
+    from scanpaths_amd import functional as F
+    T, nsel, HC = c["T"], c["nsel"], c["HC"]
+    leaf = lambda v: v.detach().clone().requires_grad_(True)
+    h_all = c["h"].clone()
+    hs = [h_all[t].requires_grad_(True) for t in range(T)]
+    W11, cbsum, cb, w2, b2 = (leaf(c[k]) for k in ("W11", "cbsum", "cb", "w2", "b2"))
+    W11s = [leaf(W11) for _ in range(T)] if per_step_weights else [W11] * T
+    cbsums = [leaf(cbsum) for _ in range(T)] if per_step_weights else [cbsum] * T
+    g = dict(hs=hs, h_all=h_all, W11s=W11s, cbsums=cbsums, leaves=hs + ([W11, cbsum] if not per_step_weights else []) + [cb, w2, b2])
+    if batched:
+        g["dpres"] = [F.drt_direct(hs[t], W11s[t], cbsums[t], c["hmap"], nsel, step=None, deferred=True) for t in range(T)]
+        g["heads"] = lambda dpres: F.drt_heads_batched(dpres, h_all, W11, cbsum, c["hmap"], cb, w2, b2, HC, per_sample=c["per_sample"])
+        return g
+    mus, s2s = [], []
+    for t in range(T):
+        with torch.no_grad():
+            Z2 = F.sal_gather(F.conv2d(hs[t], c["Wsal"], None, pad=0), c["hmap"], nsel, c["nsrc"])
+        Dpre = F.drt_direct(hs[t], W11s[t], cbsums[t], c["hmap"], nsel)
+        _, _, mu, s2 = F.head_finish(Z2, cb, w2, b2, nsel, HC, False, per_sample=c["per_sample"], dpre=Dpre)
+        mus.append(mu)
+        s2s.append(s2)
+    g["out"] = (torch.stack(mus, 2), torch.stack(s2s, 2))
+    return g
+
+
+@pytest.mark.parametrize("hw,per_sample", _DRT_CASES)
+def test_batched_duration_sites_equal_the_per_step_ops(hw, per_sample, monkeypatch):
+    """Deferred drt_direct x T + drt_heads_batched against the per-step ops: mu / sigma2 bit for bit (same kernel on the same rows), the
+    gradients w.r.t. every h_t, W11, cbsum, cb, w2, b2 to 2e-6 of their norms (test_batched_duration_branch_equals_the_per_step_form: the
+    per-step form sums drt_layer_2's and the composed bias' partials per step and then over the steps, the batched one over all T x B rows
+    at once); the `live` flags that ride on the site gradients change no bit and belong to ONE backward pass: a second pass through the
+    retained graph with other zeros equals a fresh graph's."""
+    from scanpaths_amd import functional as F
+    c = _drt_case(hw, per_sample)
+    T, shape = c["T"], (c["nsel"], c["B"], c["T"])
+    up = [(_drt_zero_pattern(c, _rand(*shape, seed=7), w), _drt_zero_pattern(c, _rand(*shape, seed=8), w)) for w in (0, 1)]
+    monkeypatch.setattr(F, "ROW_SPARSITY", True)
+    ref = _drt_graph(c, False)
+    gref = torch.autograd.grad(ref["out"], ref["leaves"], grad_outputs=up[0])
+    grads = {}
+    for sparse in (True, False):
+        monkeypatch.setattr(F, "ROW_SPARSITY", sparse)
+        g = _drt_graph(c, True)
+        out = g["heads"](g["dpres"])
+        for a, b in zip(out, ref["out"]):
+            assert a.shape == shape and torch.equal(a, b)
+        F.reset_fusion_counts()
+        grads[sparse] = torch.autograd.grad(out, g["leaves"], grad_outputs=up[0], retain_graph=sparse)
+        assert F.FUSION_COUNTS["drt_live_rows"] == (T if sparse else 0), F.FUSION_COUNTS
+        if sparse:
+            again = torch.autograd.grad(out, g["leaves"], grad_outputs=up[1])
+    for sparse in (True, False):
+        for i, (a, b) in enumerate(zip(grads[sparse], gref)):
+            d, n = float((a.double() - b.double()).norm()), float(b.double().norm())
+            print(f"leaf {i} sparse {sparse}: |diff| {d:.3e} |ref| {n:.3e}")
+            assert d <= 2e-6 * max(n, 1e-12), (i, sparse, d, n)
+    for i, (a, b) in enumerate(zip(grads[True], grads[False])):
+        assert torch.equal(a, b), i
+    monkeypatch.setattr(F, "ROW_SPARSITY", True)
+    g = _drt_graph(c, True)
+    fresh = torch.autograd.grad(g["heads"](g["dpres"]), g["leaves"], grad_outputs=up[1])
+    for i, (a, b) in enumerate(zip(again, fresh)):
+        assert torch.equal(a, b), i
+        assert not torch.equal(a, grads[True][i]), i          # (the second pattern is another gradient)
+
+
+@pytest.mark.parametrize("hw,per_sample", _DRT_CASES)
+def test_duration_site_placeholders_are_nan_until_the_batched_call(hw, per_sample):
+    """a deferred drt_direct output is a graph edge, not data: every element reads NaN, before and after drt_heads_batched (which keeps
+    the site values to itself); drt_heads_batched refuses a placeholder list that does not match its hidden states"""
+    c = _drt_case(hw, per_sample)
+    g = _drt_graph(c, True)
+    is_nan = lambda: all(d.shape == (c["nsel"], c["B"], c["S"]) and bool(torch.isnan(d).all()) for d in g["dpres"])
+    assert is_nan()
+    with pytest.raises(RuntimeError):
+        g["heads"](g["dpres"][:-1])
+    mu, s2 = g["heads"](g["dpres"])
+    assert is_nan() and bool(torch.isfinite(mu).all()) and bool(torch.isfinite(s2).all())
+
+
+@pytest.mark.parametrize("hw,per_sample", _DRT_CASES)
+def test_gradient_hook_on_a_duration_site_is_honoured(hw, per_sample, monkeypatch):
+    """The `live` flags describe the gradient the batched node produced.  A tensor hook on a step's placeholder that returns another
+    gradient must get exactly that gradient's data and weight gradients, also on the rows whose produced gradient was zero: the flags
+    ride on the produced tensor and are lost with it.  (With the flags in a shared mailbox, as before, the rows the batched node called
+    dead were skipped whatever arrived.)"""
+    from scanpaths_amd import functional as F
+    c = _drt_case(hw, per_sample)
+    T, nsel, shape = c["T"], c["nsel"], (c["nsel"], c["B"], c["T"])
+    up = (_drt_zero_pattern(c, _rand(*shape, seed=7), 0), _drt_zero_pattern(c, _rand(*shape, seed=8), 0))
+    E = (_rand(nsel, c["B"], c["S"], seed=9).abs() + 0.5).to(_dev())
+    monkeypatch.setattr(F, "ROW_SPARSITY", True)
+    g = _drt_graph(c, True, per_step_weights=True)
+    seen = []
+    g["dpres"][1].register_hook(lambda d: (seen.append(d), d + E)[1])
+    F.reset_fusion_counts()
+    got = torch.autograd.grad(g["heads"](g["dpres"]), [g["hs"][1], g["W11s"][1], g["cbsums"][1], g["hs"][0], g["hs"][2]], grad_outputs=up)
+    assert len(seen) == 1 and bool((seen[0][:, 0] == 0).all()) and bool((seen[0][0, 1:] != 0).any())
+    assert F.FUSION_COUNTS["drt_live_rows"] == T - 1, F.FUSION_COUNTS          # the hooked step ran dense
+    h1, W11, cbsum = (v.detach().clone().requires_grad_(True) for v in (c["h"][1], c["W11"], c["cbsum"]))
+    want = torch.autograd.grad(F.drt_direct(h1, W11, cbsum, c["hmap"], nsel), [h1, W11, cbsum], grad_outputs=seen[0] + E)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert torch.equal(a, b), i
+    assert bool((got[0][0] != 0).any())          # sample 0 of step 1: dead as produced, alive as it arrived
+
+
 def test_split_gemms_are_as_accurate_as_cpu_fp32():
     """fp32-faithfulness of the split GEMM back-ends on decoder-shaped data (h = o*c in (-1,1) with many near-zero entries,
     heavy-tailed gradients): rms error against fp64 of the forward conv, data gradient and weight gradient must not exceed

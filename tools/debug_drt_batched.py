@@ -15,28 +15,30 @@ m = ScanpathModel(task, convLSTM_length=T, map_width=64, map_height=40, arch="re
 fill_module(m, seed=4, family="tame")
 m = m.to(DEV).train()
 b = {k: v.to(DEV) for k, v in make_batch(task, NB, 320, 512, T, seed=4).items()}
-batches = []
-orig = F.DrtBatch
-class Rec(orig):
-    def __init__(self, T):
-        super().__init__(T); batches.append(self)
-F.DrtBatch = Rec
+calls = []
+orig = F.drt_heads_batched
+def rec(dpres, h_all, W11, cbsum, hmap, *a, **kw):
+    calls.append((h_all, W11.detach(), cbsum.detach(), hmap))
+    return orig(dpres, h_all, W11, cbsum, hmap, *a, **kw)
+F.drt_heads_batched = rec
 F.COST_M_SCALE = 32.0 / 5
 with torch.no_grad():
     args = (b["images"], b["attention_maps"], b["performances"]) if task == "AiR" else (b["images"], b["attention_maps"], b["tasks"])
     F.DRT_BATCHED = True
     pa = m(*args)
-    db = batches[-1]
+    h_all, W11, cbsum, hmap = calls[-1]
     F.DRT_BATCHED = False
     pb = m(*args)
     for k in pa:
         d = (pa[k] - pb[k]).abs().max().item()
         print(k, "max diff", d, "n differing", int((pa[k] != pb[k]).sum()))
-    # sites per step from the recorded operands, one launch each, vs the batch's buffer
-    for t, (h, W11, cbsum, hmap, nsel) in enumerate(db.items):
-        D1 = F.drt_direct(h, W11, cbsum, hmap, nsel)
-        print("step", t, "Dpre diff", (D1 - db.D[t]).abs().max().item(), "n", int((D1 != db.D[t]).sum()), "h contiguous in buf",
-              h.data_ptr() == db.buf[t].data_ptr())
+    # sites per step, one launch each, vs what ONE launch over the T x B rows of h_all writes
+    Tn, B = h_all.shape[:2]
+    nsel = hmap.shape[1]
+    Dall = F.drt_direct(h_all.flatten(0, 1), W11, cbsum, hmap.repeat(Tn, 1).contiguous(), nsel).view(nsel, Tn, B, -1)
+    for t in range(Tn):
+        D1 = F.drt_direct(h_all[t], W11, cbsum, hmap, nsel)
+        print("step", t, "Dpre diff", (D1 - Dall[:, t]).abs().max().item(), "n", int((D1 != Dall[:, t]).sum()))
 
 # ---- timing of the one-launch site kernel at the benchmark size (T x B = 512 hidden states of 40 x 64 x 512) --------------------------------
 if len(sys.argv) > 2 and sys.argv[2] == "time":
