@@ -18,6 +18,7 @@ from torch.autograd import Function
 from . import config as _config
 from . import hip
 from .hip import ConvDesc, WgradDesc, check, ptr
+from .notes import carry, note, notes
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -303,7 +304,7 @@ _HINT_POOL = {}
 
 def _amax_hint(device) -> Optional[torch.Tensor]:
     """{scale, amax bits} buffer for a producer kernel that leaves max|output| behind (block max + one guarded atomic per block);
-    attached to the produced tensor as ``_sp_amax`` so that split_op can skip its read-only amax pass.  None when the 2xfp16
+    noted on the produced tensor (notes.py: ``amax``) so that split_op can skip its read-only amax pass.  None when the 2xfp16
     back-end is not in use."""
     if not USE_BF16X3 or SPLIT_SCHEME != "f16x2" or not FUSED_AMAX:
         return None
@@ -377,7 +378,7 @@ def _hint_ptr(hint: Optional[torch.Tensor]) -> Optional[int]:
 
 def _fp32_required(x: torch.Tensor, what: str) -> None:
     """a tensor whose fp32 form was left unwritten by its producer (bn skip_dx, cell backward skip) must never be read as fp32"""
-    if getattr(x, "_sp_skipped", False):
+    if notes(x).skipped:
         raise RuntimeError(f"scanpaths_amd: {what} needs the fp32 form of a gradient that exists only as a split operand; "
                            "run with SP_LSTM_SKIP_DPRE=0")
 
@@ -391,14 +392,14 @@ def split_op(x: torch.Tensor, scheme: Optional[str] = None, channel: bool = Fals
     channel far below the tensor's maximum (the terminate-logit columns of the saliency tap gradient: 2^-20 .. 2^-29 of the action
     map's) keeps its 22 bits in the weight-gradient GEMM, whose output row / column it alone feeds."""
     scheme = scheme or _scheme_for(x.shape[-1])
-    cache = getattr(x, "_sp_cache", None)        # {scheme: SplitOperand} shared by every alias of a multi-consumer tensor (fanout)
+    cache = notes(x).cache                       # {scheme: SplitOperand} shared by every alias of a multi-consumer tensor (fanout)
     if cache is not None and scheme in cache:
         return cache[scheme]
     _fp32_required(x, "split_op")
     if scheme == "bf16x3":
         op = SplitOperand(split3(x), None, scheme)
     else:
-        hint = getattr(x, "_sp_amax", None)      # left by the kernel that produced x (same tensor object, never modified since)
+        hint = notes(x).amax                     # left by the kernel that produced x (same tensor object, never modified since)
         xc = x.contiguous()
         n = xc.numel()
         out = torch.empty(2 * n + 32, dtype=torch.float16, device=x.device)
@@ -672,7 +673,7 @@ def _conv_wgrad(g: ConvGeom, x, dy, dwp, *, xs=None, dys=None, channel=False):
     """dwp [Co,KH,KW,Ci] = weight gradient of conv(x, wp); xs / dys: split operands that exist already (the forward's x, the data
     gradient's dy), used when their scheme is the weight gradient's"""
     wsch = g.wgrad_scheme
-    dy_cached = getattr(dy, "_sp_cache", None)       # the producer of dy (a BatchNorm / cell backward) already wrote its split form
+    dy_cached = notes(dy).cache                      # the producer of dy (a BatchNorm / cell backward) already wrote its split form
     if dys is None and dy_cached is not None and wsch in dy_cached:
         dys = dy_cached[wsch]
     if dys is not None and dys.scheme != wsch:
@@ -744,7 +745,7 @@ def touch_zero_grad(t, params):
 class _FanOut(Function):
     """x -> n aliases of x for n consumers; backward adds the n gradients in ONE pass (sp_sum_n) instead of the n-1
     read-read-write adds autograd would issue.  Used for the hoisted x-gate pre-activations (one consumer per decode step).
-    token: dict shared with the aliases (alias i carries ``_sp_fan = (token, i)``).  A consumer whose backward leaves the fp32 form of
+    token: dict shared with the aliases (alias i carries the note ``fan = (token, i)``).  A consumer whose backward leaves the fp32 form of
     its gradient UNWRITTEN (the cell backward, _lstm_rank1_backward) records the split operand it wrote instead under its alias index;
     this backward then reads that contribution from the token BY OUTPUT INDEX -- never from an attribute of the incoming tensor, whose
     identity autograd does not guarantee (a hook that returns a new tensor, an accumulation, a cloning wrapper: ADVICE r3) -- and
@@ -772,7 +773,7 @@ class _FanOut(Function):
         if not idx:
             return None, None, None, None, None
         for i in idx:
-            if i not in tok and getattr(grads[i], "_sp_skipped", False):
+            if i not in tok and notes(grads[i]).skipped:
                 raise RuntimeError("scanpaths_amd: a gradient whose fp32 form was left unwritten reached a fan-in without its record")
         gs = [grads[i].contiguous() for i in idx]
         ops = [tok.get(i) for i in idx]            # contributions that exist only as split operands (cell backward)
@@ -792,7 +793,7 @@ class _FanOut(Function):
             check(hip.lib().sp_sum_n_mixed(f, pl, sc, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc.last) if rc else None, steps,
                                            rc.B if rc else 0, hip.stream()), "sp_sum_n_mixed")
             if hint is not None:
-                out._sp_amax = hint
+                note(out).amax = hint
             return out, None, None, None, None
         if len(gs) == 1:
             return gs[0], None, None, None, None
@@ -806,10 +807,10 @@ class _FanOut(Function):
         arr = (C.c_void_p * len(gs))(*[g.data_ptr() for g in gs])
         hint = _amax_hint(out.device)          # max|sum|: the LSTM cell's backward bounds its split operand with it
         # masked-step sparsity: every term of a tensor that lives at decode step ctx.step (h_t: the two heads' and the next step's
-        # h-gate gradients), or the terms a producer marked with their memory update (_sp_rows: semantic pooling -> vf), are exact
+        # h-gate gradients), or the terms a producer marked with their memory update (the `rows` note: semantic pooling -> vf), are exact
         # zeros for the samples behind their last loss step -- not read (a lost hint only makes the pass dense again)
         rc0 = rows_ctx(ctx.step, gs[0].shape[0]) if gs[0].dim() > 1 else None
-        marks = [getattr(grads[i], "_sp_rows", None) for i in idx]
+        marks = [notes(grads[i]).rows for i in idx]
         if rc0 is None and any(m is not None for m in marks):
             cand = next(m[0] for m in marks if m is not None)      # (a mark is made by a backward node of THIS pass from its own token)
             if gs[0].dim() > 1 and cand.B == gs[0].shape[0] and ROW_SPARSITY:
@@ -826,7 +827,7 @@ class _FanOut(Function):
         check(hip.lib().sp_sum_n(arr, len(gs), n, ptr(out), _hint_ptr(hint), ptr(rc0.last) if sparse else None,
                                  (C.c_int * len(gs))(*steps) if sparse else None, rc0.B if sparse else 0, hip.stream()), "sp_sum_n")
         if hint is not None:
-            out._sp_amax = hint
+            note(out).amax = hint
         return out, None, None, None, None
 
 
@@ -840,16 +841,11 @@ def fanout(x: torch.Tensor, n: int, step=None):
     outs = _FanOut.apply(x, n, token, step, events)
     if events is not None:
         for i, o in enumerate(outs):
-            o._sp_fan_ev = (events, i)      # a consumer may compute its gradient on another stream and leave its completion event here
-    for attr in ("_sp_cache", "_sp_amax"):
-        v = getattr(x, attr, None)
-        if v is not None:
-            for o in outs:
-                setattr(o, attr, v)
+            note(o).fan_ev = (events, i)    # a consumer may compute its gradient on another stream and leave its completion event here
+    carry(x, outs)
     if split_ok:
         for i, o in enumerate(outs):
-            o._sp_fan = (token, i)          # a consumer may hand back its gradient as a split operand only (see _FanOut)
-            o._sp_split_grad_ok = True
+            note(o).fan = (token, i)        # a consumer may hand back its gradient as a split operand only (see _FanOut)
     return outs
 
 
@@ -887,11 +883,7 @@ class _Tap(Function):
 
 def tap(x: torch.Tensor, holder: GradMerge):
     outs = _Tap.apply(x, holder)
-    for attr in ("_sp_cache", "_sp_amax"):
-        v = getattr(x, attr, None)
-        if v is not None:
-            for o in outs:
-                setattr(o, attr, v)
+    carry(x, outs)
     return outs
 
 
@@ -947,25 +939,26 @@ class _Conv2d(Function):
         need_dx, need_dw = ctx.needs_input_grad[:2]
         g = ConvGeom.of(x.shape, *wp.shape[:3], stride, pad, dil)
         y = torch.empty((g.N, g.Ho, g.Wo, g.Co), dtype=torch.float32, device=x.device)
-        shared = getattr(x, "_sp_cache", None) is not None
-        if getattr(x, "_sp_uninit", False) and not conv_runs_from_split(x.shape, w, stride, pad, dil, need_dw):
+        shared = notes(x).cache is not None
+        if notes(x).uninit and not conv_runs_from_split(x.shape, w, stride, pad, dil, need_dw):
             raise RuntimeError("scanpaths_amd: a BatchNorm left this input's fp32 form unwritten (skip_z) but this conv does not run "
                                "from the split operand alone; run with SP_BN_SKIP_DX=0")
         xs, stats = _conv_fwd(g, x, wp, bias, y, relu=relu, wcache=wcache, channel=True, free_a=shared, a_elems=x.numel(), bn_stats=bn_stats)
         if xs is not None:
-            y._sp_from_split = xs.scheme == "f16x2"        # a BatchNorm behind this conv may emit the split gradient (bn_act)
+            yn = note(y)
+            yn.from_split = xs.scheme == "f16x2"           # a BatchNorm behind this conv may emit the split gradient (bn_act)
             if stats is not None:
                 FUSION_COUNTS["conv_bn_stats"] += 1
-                y._sp_bnstats = stats
+                yn.bnstats = stats
             # the weight-gradient GEMM consumes the same split operand: keep it (6 B/element) instead of re-splitting x in
             # backward (HBM pass of 10 B/element per conv); sized for 288 GB
             keep = need_dw and g.wgrad_split(free_splits=True) == xs.scheme
             # Both backward GEMMs of this conv would read ONLY the split form of the output gradient: a BatchNorm behind it (the
             # single consumer of y, see bn_act skip_dx) may then leave the fp32 gradient unwritten.  The token lets this conv's
             # backward fail loudly if such a gradient ever arrives without its split form.
-            if (y._sp_from_split and g.wgrad_scheme == "f16x2" and bias is None and not relu and (not need_dw or keep)
+            if (yn.from_split and g.wgrad_scheme == "f16x2" and bias is None and not relu and (not need_dw or keep)
                     and (not need_dx or g.dgrad_split(free_a=True, a_elems=y.numel()))):
-                ctx.dy_token = y._sp_dy_token = {"skipped": False}
+                ctx.dy_token = yn.dy_token = {"skipped": False}
             if not keep:
                 xs = None
         ctx.xs_scheme = (xs.scheme, xs.kind) if xs is not None else None
@@ -980,7 +973,7 @@ class _Conv2d(Function):
         relu, has_bias = ctx.cfg
         x, wp, y, xs_buf, xs_scale = ctx.saved_tensors
         xs = SplitOperand(xs_buf, xs_scale, *ctx.xs_scheme) if xs_buf is not None else None
-        if ctx.dy_token is not None and ctx.dy_token["skipped"] and getattr(dy, "_sp_cache", None) is None:
+        if ctx.dy_token is not None and ctx.dy_token["skipped"] and notes(dy).cache is None:
             raise RuntimeError("scanpaths_amd: a BatchNorm left this gradient's fp32 form unwritten (skip_dx) but its split form "
                                "did not arrive with it; run with SP_BN_SKIP_DX=0")
         dy = dy.contiguous()
@@ -1062,7 +1055,7 @@ def _conv_backward(g: ConvGeom, x, wp, dy, xs, wcache, need_dx, need_dw, accum=N
     accum: GradMerge whose ``first`` (another consumer's gradient of x) the data gradient is added to in place"""
     dx = dw = None
     dys = None
-    dy_cached = getattr(dy, "_sp_cache", None)       # the producer of dy (a BatchNorm / cell backward) already wrote its split form
+    dy_cached = notes(dy).cache                      # the producer of dy (a BatchNorm / cell backward) already wrote its split form
     defer = wcache.get("defer") if (DEFER_WGRAD and isinstance(wcache, dict)) else None
     rc = rows_ctx(step, g.N)          # samples whose gradient rows are exactly zero at this decode step (loss masks)
     deferred = False
@@ -1300,7 +1293,7 @@ class _BnAct(Function):
         check(L.sp_bn_apply(ptr(x), ptr(mean), ptr(invstd), ptr(gamma), ptr(beta), ptr(res), int(relu), M, Cc, ptr(y),
                             _hint_ptr(hint), hip.stream()), "sp_bn_apply")
         if hint is not None:
-            y._sp_amax = hint
+            note(y).amax = hint
         ctx.cfg = (training, relu, residual is not None)
         ctx.save_for_backward(x, y if relu else None, mean, invstd, gamma.detach())
         return y
@@ -1323,7 +1316,7 @@ class _BnAct(Function):
                                ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), ptr(ws), _hint_ptr(hint), hip.stream()),
               "sp_bn_backward")
         if hint is not None:
-            dx._sp_amax = hint
+            note(dx).amax = hint
         return dx, dgamma, dbeta, None, None, dres, None, None, None, None
 
 
@@ -1360,19 +1353,20 @@ class _BnActSplit(Function):
         zhint, bhint = _amax_hint(dev), _amax_hint(dev)
         skip_z = bool(skip_z) and planes is not None          # the only consumer reads the split operand: fp32 output unwritten
         check(L.sp_bn_fwd_split(ptr(x), M, Cc, eps, momentum, ptr(gamma), ptr(beta), ptr(res),
-                                _hint_ptr(residual._sp_amax) if residual is not None else None, int(relu), ptr(mean), ptr(invstd),
+                                _hint_ptr(notes(residual).amax), int(relu), ptr(mean), ptr(invstd),
                                 ptr(rmean), ptr(rvar), ptr(ext), None if skip_z else ptr(y), ptr(planes), ptr(zhint),
                                 _hint_ptr(bhint), ptr(mask),
                                 ptr(ws), ptr(pre[0]) if pre else None, ptr(pre[1]) if pre else None, pre[2] if pre else 0,
                                 hip.stream()), "sp_bn_fwd_split")
-        y._sp_amax = zhint
+        yn = note(y)
+        yn.amax = zhint
         FUSION_COUNTS["bn_fwd_split"] += 1
         if planes is not None:
             FUSION_COUNTS["bn_fwd_split_operand"] += 1
-            y._sp_cache = {"f16x2": SplitOperand(planes, zhint, "f16x2")}
+            yn.cache = {"f16x2": SplitOperand(planes, zhint, "f16x2")}
         if skip_z:
             FUSION_COUNTS["bn_skip_z"] += 1
-            y._sp_uninit = True            # conv2d refuses such an input unless it runs (forward and backward) from the split operand
+            yn.uninit = True               # conv2d refuses such an input unless it runs (forward and backward) from the split operand
         ctx.cfg = (relu, residual is not None, bool(emit_bwd) and Cc % 16 == 0)
         ctx.save_for_backward(x, mask, mean, invstd, gamma.detach(), ext)
         return y
@@ -1408,9 +1402,9 @@ class _BnActSplit(Function):
                                 None if skip else ptr(dx),
                                 ptr(dres), ptr(planes), ptr(dhint), _hint_ptr(bhint), ptr(dgamma), ptr(dbeta), ptr(ws),
                                 hip.stream()), "sp_bn_bwd_split")
-        dx._sp_amax = dhint
+        note(dx).amax = dhint
         if planes is not None:
-            dx._sp_cache = {"f16x2": SplitOperand(planes, dhint, "f16x2")}
+            note(dx).cache = {"f16x2": SplitOperand(planes, dhint, "f16x2")}
         if ctx.res_store is not None and dres is not None:
             ctx.res_store.first = dres
         if gslot is not None:
@@ -1432,11 +1426,12 @@ def bn_act(x, gamma, beta, rmean, rvar, residual=None, training=True, momentum=0
     skip_z: the output's ONLY consumer is a conv that runs forward and backward from the split operand (conv_runs_from_split): the
     fp32 output is allocated but not written.  Neither tensor may be handed to code outside the encoder."""
     if (training and BN_SPLIT and x.shape[-1] % 4 == 0 and _amax_hint_active()
-            and (residual is None or getattr(residual, "_sp_amax", None) is not None)):
-        emit_bwd = getattr(x, "_sp_from_split", False)       # the producing conv's backward GEMMs read the split gradient
-        token = getattr(x, "_sp_dy_token", None) if (skip_dx and BN_SKIP_DX and emit_bwd) else None
+            and (residual is None or notes(residual).amax is not None)):
+        xn = notes(x)
+        emit_bwd = xn.from_split                             # the producing conv's backward GEMMs read the split gradient
+        token = xn.dy_token if (skip_dx and BN_SKIP_DX and emit_bwd) else None
         return _BnActSplit.apply(x, gamma, beta, rmean, rvar, residual, momentum, eps, relu, emit_split, emit_bwd,
-                                 getattr(x, "_sp_bnstats", None), res_store, token, skip_z and emit_split and BN_SKIP_DX and BN_SKIP_Z)
+                                 xn.bnstats, res_store, token, skip_z and emit_split and BN_SKIP_DX and BN_SKIP_Z)
     return _BnAct.apply(x, gamma, beta, rmean, rvar, residual, training, momentum, eps, relu)
 
 
@@ -1576,7 +1571,7 @@ def lstm_cell(xg, hg, c_prev):
 
 def _h_dest(h_out, like):
     """the caller's buffer for a cell's hidden state (decode(): slice t of the [T, B, Hm, Wm, C] buffer that drt_heads_batched reads in one
-    launch), as a fresh alias: autograd hands an INPUT that a Function returns back as a new tensor object, without the _sp_ marks"""
+    launch), as a fresh alias: autograd hands an INPUT that a Function returns back as a new tensor object, without its notes"""
     if h_out.shape != like.shape or h_out.dtype != like.dtype or h_out.device != like.device or not h_out.is_contiguous():
         raise RuntimeError(f"scanpaths_amd: h_out must be a contiguous {tuple(like.shape)} {like.dtype} tensor on {like.device}")
     return h_out.view(like.shape)
@@ -1605,11 +1600,10 @@ class _LstmCellRank1(Function):
         hint = _amax_hint(xg.device)
         check(hip.lib().sp_lstm_rank1_fwd(ptr(xg), ptr(hg), ptr(c_prev), ptr(spcol), ptr(wc), B, P, Cc, KP, ptr(gates), ptr(c),
                                           ptr(h), _hint_ptr(hint), hip.stream()), "sp_lstm_rank1_fwd")
-        if hint is not None:
-            h._sp_amax = hint
-        h._sp_cache = {}                  # h feeds the saliency tap GEMM of this step and the h-gate conv of the next: split once
+        hn = note(h)
+        hn.amax, hn.cache = hint, {}      # h feeds the saliency tap GEMM of this step and the h-gate conv of the next: split once
         ctx.has = (hg is not None, c_prev is not None)
-        ctx.fan = getattr(xg, "_sp_fan", None)
+        ctx.fan = notes(xg).fan
         ctx.skip_ok = hg is None and ctx.fan is not None      # dpre's only consumer (xg's fan-in) takes a split operand
         ctx.set_materialize_grads(False)          # the last step's dc stays None instead of a zero tensor the kernel would read
         ctx.cbounds = _cell_bounds(c_prev, c)
@@ -1627,10 +1621,10 @@ class _LstmCellRank1(Function):
 
 def _cell_bounds(c_prev, c):
     """(bound of max|c|, bound of max|c_prev|) from |c_t| <= |c_{t-1}| + 1 (gates in (0,1), |g| < 1); travels on the state tensor"""
-    cbp = 0.0 if c_prev is None else getattr(c_prev, "_sp_cbound", None)
+    cbp = 0.0 if c_prev is None else notes(c_prev).cbound
     cb = None if cbp is None else cbp + 1.0
     if cb is not None:
-        c._sp_cbound = cb
+        note(c).cbound = cb
     return cb, cbp
 
 
@@ -1651,8 +1645,7 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
                          step=None):
     """gradients of the cell w.r.t. the gate pre-activations (dpre, carrying its max|.| hint or -- when bounds of max|dh|, max|dc| and
     max|c| are known -- its 2xfp16 split operand, written by the same pass), c_prev, spcol and wc"""
-    dh_h = getattr(dh, "_sp_amax", None) if dh is not None else None
-    dc_h = getattr(dc, "_sp_amax", None) if dc is not None else None
+    dh_h, dc_h = notes(dh).amax, notes(dc).amax
     dh = dh.contiguous() if dh is not None else None
     dc = dc.contiguous() if dc is not None else None
     B, P, KP = spcol.shape
@@ -1676,26 +1669,26 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
                 and (not need_dwc or (RANK1_DWC_SPLIT and rank1_split_ok)))
         if skip:
             FUSION_COUNTS["lstm_skip_dpre"] += 1
-            dpre._sp_skipped = True          # guards every fp32 reader this process owns (_fp32_required); the fan-in reads the record
+            note(dpre).skipped = True        # guards every fp32 reader this process owns (_fp32_required); the fan-in reads the record
         check(hip.lib().sp_lstm_pointwise_bwd(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, None if skip else ptr(dpre), ptr(dcp),
                                               None, _hint_ptr(chint), _hint_ptr(dh_h), _hint_ptr(dc_h), float(cbounds[0]),
                                               float(cbounds[1]), ptr(planes), ptr(hint), ptr(rc.last) if rc is not None else None,
                                               int(step) if rc is not None else 0, P, hip.stream()),
               "sp_lstm_pointwise_bwd")
-        dpre._sp_amax = hint
-        dpre._sp_cache = {"f16x2": SplitOperand(planes, hint, "f16x2")}
+        dps = SplitOperand(planes, hint, "f16x2")
+        note(dpre).amax, note(dpre).cache = hint, {"f16x2": dps}
         if rc is not None:
-            dpre._sp_cache["f16x2"].rows = (rc, int(step))
+            dps.rows = (rc, int(step))
         if skip:
-            fan[0][fan[1]] = dpre._sp_cache["f16x2"]      # xg's fan-in takes this contribution from the record, by alias index
+            fan[0][fan[1]] = dps                          # xg's fan-in takes this contribution from the record, by alias index
     else:
         check(hip.lib().sp_lstm_pointwise_bwd(ptr(dh), ptr(dc), ptr(gates), ptr(c_prev), ptr(c), rows, Cc, ptr(dpre), ptr(dcp),
                                               _hint_ptr(hint), _hint_ptr(chint), None, None, 0.0, 0.0, None, None, None, 0, 1,
                                               hip.stream()), "sp_lstm_pointwise_bwd")
         if hint is not None:
-            dpre._sp_amax = hint
+            note(dpre).amax = hint
     if chint is not None:
-        dcp._sp_amax = chint               # max|dc_prev|: the previous step's cell backward bounds its operand with it
+        note(dcp).amax = chint             # max|dc_prev|: the previous step's cell backward bounds its operand with it
     dsp = dwc = None
     L = hip.lib()
     if (need_dsp and need_dwc and emit and RANK1_FUSED and RANK1_DSP_SPLIT and RANK1_DWC_SPLIT and rank1_split_ok
@@ -1704,7 +1697,7 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
         # the matrix pipe against the split form of wc^T, dwc on the vector pipe from the same LDS tiles, spcol as it is -- instead of two
         # launches of the big GEMM kernels that each re-read the 503 MB of planes, and six small launches preparing their operands
         FUSION_COUNTS["rank1_fused"] += 1
-        ys = dpre._sp_cache["f16x2"]
+        ys = dps
         ws = _split_wcT(wc)             # [B][KP][3C]: K contiguous, one scale per row
         dsp, dwc = torch.empty_like(spcol), torch.empty_like(wc)
         wsp = hip.workspace(L.sp_rank1_grads_workspace(B, P, N3, KP), dpre.device, slot=0)
@@ -1719,7 +1712,7 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
             # per sample, on the split dpre the cell backward just wrote (its first 3C of 4C channels per row) -- the fp32-MFMA
             # batched GEMM it replaces read the fp32 dpre (0.5 GB) at ~2 TB/s
             FUSION_COUNTS["rank1_dsp_split"] += 1
-            xs = dpre._sp_cache["f16x2"]
+            xs = dps
             ws = _split_wcT(wc)             # [B][KP][3C]: K contiguous, one scale per row
             d = _gemm_desc(P, KP, N3, ldx=C4, ldw=N3, ldc=KP, nbatch=B, sX=P * C4, sW=KP * N3, sC=P * KP)
             d.w_scale_rows = 1
@@ -1736,7 +1729,7 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
             # pixels) on the split dpre; spcol's KP tap columns are padded to 32 for the 16-channel groups of the split operand, the
             # kernel stores the first KP columns.  The VALU kernel it replaces read the fp32 dpre at ~2 TB/s (250 us per launch)
             FUSION_COUNTS["rank1_dwc_split"] += 1
-            ys = dpre._sp_cache["f16x2"]
+            ys = dps
             xs = split_op(torch.nn.functional.pad(spcol, (0, 32 - KP)), "f16x2")
             d = WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=N3, ldy=C4, KH=1, KW=1, stride=1, pad=0, dil=1,
                           ldo=KP, alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * C4, strideO=N3 * KP)
@@ -1807,9 +1800,8 @@ class _GateConvLstm(Function):
         _timed(lambda: (("h2_fwd", g.M, g.Co, g.K, f"{g.KH}x{g.KW}", 1), 2.0 * g.M * g.Co * g.K), launch)
         FUSION_COUNTS["gateconv_lstm"] += 1
         FUSION_COUNTS["gateconv_lstm_hplanes"] += int(hplanes is not None)
-        if hint is not None:
-            h._sp_amax = hint
-        h._sp_cache = {"f16x2": SplitOperand(hplanes, hint, "f16x2")} if hplanes is not None else {}
+        hn = note(h)
+        hn.amax, hn.cache = hint, ({"f16x2": SplitOperand(hplanes, hint, "f16x2")} if hplanes is not None else {})
         ctx.set_materialize_grads(False)
         ctx.cbounds = cbounds
         defer = wcache.get("defer") if isinstance(wcache, dict) else None
@@ -1819,8 +1811,8 @@ class _GateConvLstm(Function):
         ctx.geom, ctx.wcache = g, wcache
         # the gate gradient dpre of this step has three consumers: xg's fan-in, the h-gate conv's data and weight gradient.  When all
         # of them read its split form, its fp32 form is never written (_lstm_rank1_backward skip_fp32)
-        ctx.fan = getattr(xg, "_sp_fan", None)
-        ctx.h_events = getattr(h_prev, "_sp_fan_ev", None)      # (events dict of h_prev's fan-out, this consumer's index) or None
+        ctx.fan = notes(xg).fan
+        ctx.h_events = notes(h_prev).fan_ev                      # (events dict of h_prev's fan-out, this consumer's index) or None
         ctx.skip_ok = (ctx.fan is not None and _scheme_for(g.Co) == "f16x2"
                        and (not need_dx or g.dgrad_split(free_a=True, a_elems=xg.numel()))
                        and (not need_dw or (keep and g.wgrad_scheme == "f16x2")))
@@ -1861,7 +1853,7 @@ class _GateConvLstm(Function):
             # soon as this node returns, unless another consumer happens to hold it (xg's fan-in, the deferred weight gradient).  The
             # caching allocator must not hand those blocks to a current-stream kernel while the 1.3-3.3 ms GEMM is still reading them.
             rc_ = rows_ctx(ctx.step, h_prev.shape[0])
-            planes = (getattr(dpre, "_sp_cache", None) or {}).get("f16x2")
+            planes = (notes(dpre).cache or {}).get("f16x2")
             for t_ in (dpre, h_prev, wp, planes.buf if planes is not None else None, planes.scale if planes is not None else None,
                        rc_.last if rc_ is not None else None):
                 if t_ is not None and t_.is_cuda:
@@ -2001,7 +1993,7 @@ class _SemPool(Function):
                                        ptr(rc.last) if rc is not None else None, int(ctx.step) if rc is not None else 0, int(ctx.sbc),
                                        hip.stream()), "sp_sempool_bwd")
         if rc is not None:
-            dvf._sp_rows = (rc, int(ctx.step))      # hint for vf's gradient fan-in (dead samples' rows are exact zeros): F._FanOut
+            note(dvf).rows = (rc, int(ctx.step))    # hint for vf's gradient fan-in (dead samples' rows are exact zeros): F._FanOut
         return da, dvf, None, None
 
 
@@ -2269,9 +2261,9 @@ class _DrtDirect(Function):
         B, Hm, Wm, C_, nsel, nheads, wshape, cshape = ctx.cfg
         h, W11, hmap = ctx.saved_tensors
         # (slot, sample) pairs whose duration gradient is exactly zero -- AiR's unselected head, the step at a scanpath's end -- as the
-        # batched duration backward found them for THIS gradient tensor (_sp_live, a hint: a hook that replaces the gradient drops it and
+        # batched duration backward found them for THIS gradient tensor (the `live` note, a hint: a hook that replaces the gradient drops it and
         # the launches are dense again): skipped like the dead samples, bit-identical sums
-        live = getattr(dD, "_sp_live", None) if ROW_SPARSITY else None
+        live = notes(dD).live if ROW_SPARSITY else None
         FUSION_COUNTS["drt_live_rows"] += int(live is not None)
         dD = dD.contiguous()
         L = hip.lib()
@@ -2302,7 +2294,7 @@ class _DrtHeadsBatched(Function):
     slices), W11, cbsum, hmap (values only: their gradients and h's go through the per-step nodes), cb, w2, b2 + the placeholders
     Dpre_t [nsel,B,S] of the T deferred drt_direct nodes (graph edges, never read) -> mu, sigma2 [nsel, B, T]: sp_drt_direct_fwd ONCE over
     the T x B hidden states, the duration part of the head epilogue once over T x nsel virtual heads.  Backward: d(mu), d(sigma2) ->
-    the site gradients of every step (one launch), each carrying its `live` flags (_sp_live); the per-step nodes' data / weight gradient
+    the site gradients of every step (one launch), each carrying its `live` flags (notes.py); the per-step nodes' data / weight gradient
     launches stay where they were."""
     @staticmethod
     def forward(ctx, h_all, W11, cbsum, hmap, cb, w2, b2, HC, per_sample, *dpres):
@@ -2360,7 +2352,7 @@ class _DrtHeadsBatched(Function):
         db2 = _colsum_any(db2p, NH * 2).view(NH, 2).sum(0)
         dd = list(ddpre.view(Tn, nsel, B, S).unbind(0))
         for d, lv in zip(dd, live.view(Tn, nsel * B).unbind(0)):
-            d._sp_live = lv          # the flags [nsel][B] of THIS gradient ride on it to decode step t's drt_direct node
+            note(d).live = lv        # the flags [nsel][B] of THIS gradient ride on it to decode step t's drt_direct node
         return (None, None, None, None, dcb, dw2.reshape(w2shape), db2.reshape(2), None, None) + tuple(dd)
 
 

@@ -14,6 +14,7 @@ import torch
 
 from helpers import load_npz
 from module_cases import MODULE_CASES, case_inputs, cotangents
+from scanpaths_amd.notes import note
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -102,7 +103,7 @@ def test_convlstm_step_matches_the_reference_module(fused, monkeypatch):
     parts = [F.gemm(se[s], Wr[s], None, "nk").view(B, 3 * C, 9) for s in range(2)]
     wc = torch.cat(parts + [torch.zeros(B, 3 * C, KP - 18, device=DEV)], 2)
     spcol = F.im2col3x3(torch.stack(sp, 0), KP)
-    c._sp_cbound = float(c.detach().abs().max())          # (decode() carries the bound |c_t| <= t + 1 on the state; here the measured maximum)
+    note(c).cbound = float(c.detach().abs().max())        # (decode() carries the bound |c_t| <= t + 1 on the state; here the measured maximum)
     F.reset_fusion_counts()
     if fused:
         assert F.gateconv_lstm_fusable(h, Wh, spcol)

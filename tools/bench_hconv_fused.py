@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from scanpaths_amd import functional as F, hip
+from scanpaths_amd.notes import note
 
 B, Hm, Wm, C, KP = 32, 40, 64, 512, 20
 P = Hm * Wm
@@ -24,19 +25,18 @@ w = (torch.randn(4 * C, C, 3, 3, generator=g) * 0.02).to(dev).contiguous(memory_
 spcol = torch.rand(B, P, KP, generator=g).to(dev)
 wc = (torch.randn(B, 3 * C, KP, generator=g) * 0.1).to(dev)
 gh = torch.randn(B, Hm, Wm, C, generator=g).to(dev)
-gh._sp_amax = None
 
 
 def step():
     h = h0.clone().requires_grad_(True)
     c = c0.clone().requires_grad_(True)
-    c._sp_cbound = 4.0
+    note(c).cbound = 4.0
     hn, cn = F.gateconv_lstm(h, w, xg, c, spcol, wc, {})
     # gradients arrive with their max|.| hints in the model (fan-in pass): reproduce that so the cell backward writes the split dpre
     gg = gh.clone()
     hint = torch.zeros(2, device=dev)          # its own tensor: an in-place torch write into a POOL slot would bump the version counter
     hint[1] = float(gg.abs().max())            # every saved pool slot shares (autograd then refuses the saved operand scales)
-    gg._sp_amax = hint
+    note(gg).amax = hint
     torch.autograd.backward([hn], [gg])
 
 

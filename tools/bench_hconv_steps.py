@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from scanpaths_amd import functional as F, hip
+from scanpaths_amd.notes import note
 
 B, Hm, Wm, C, KP = 32, 40, 64, 512, 20
 T = int(os.environ.get("T_STEPS", "16"))
@@ -31,7 +32,7 @@ def step():
     cache = {"defer": F.DeferredWgrad()}
     h = h0.clone().requires_grad_(True)
     c = c0.clone().requires_grad_(True)
-    c._sp_cbound = 1.0
+    note(c).cbound = 1.0
     xgs = F.fanout(xg, T - 1)
     loss = 0.0
     for t in range(T - 1):

@@ -8,6 +8,7 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from scanpaths_amd import functional as F  # noqa: E402
+from scanpaths_amd.notes import note  # noqa: E402
 
 dev = torch.device("cuda:0")
 SHAPES = [(80, 128, 128, 512), (80, 128, 256, 64), (80, 128, 64, 256), (40, 64, 256, 1024), (40, 64, 1024, 256), (40, 64, 512, 2048)]
@@ -30,7 +31,7 @@ out = []
 for H, W, Ci, Co in SHAPES:
     x = torch.randn(32, H, W, Ci, device=dev)
     w = (torch.randn(Co, Ci, 1, 1, device=dev) * 0.05).contiguous(memory_format=torch.channels_last)
-    x._sp_cache = {}
+    note(x).cache = {}
     F.split_op(x)                                           # the operand is there, as after a BatchNorm that emitted it
     with torch.no_grad():
         t_plain = timed(lambda: F.conv2d(x, w, None))
