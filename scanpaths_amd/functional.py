@@ -58,7 +58,7 @@ def _igemm(d: ConvDesc, X, W, bias, out):
     # streams the matrix once over ~512 workgroups (csrc/gemm_skinny.hip; 135-185 us per launch on the 128 x 128-tile kernel below)
     M_, Nout, Kc, mode, taps, nbatch = d.N_img * d.Ho * d.Wo, d.Nout, d.Kc, d.mode, d.KH * d.KW, d.nbatch
     aligned = all(t is None or t.data_ptr() % 16 == 0 for t in (X, W, out, bias))
-    if (SKINNY_GEMM and taps == 1 and nbatch == 1 and M_ <= 64 and not d.beta and d.Hi == d.Ho and d.Wi == d.Wo and d.stride == 1
+    if (taps == 1 and nbatch == 1 and M_ <= 64 and not d.beta and d.Hi == d.Ho and d.Wi == d.Wo and d.stride == 1
             and d.pad == 0 and aligned and d.ldc % 4 == 0 and hip.lib().sp_gemm_skinny_applies(M_, Nout, Kc, d.ldx, d.ldw, d.ldc, mode)):
         L = hip.lib()
         ws = hip.workspace(L.sp_gemm_skinny_workspace(M_, Nout, Kc, mode), X.device, slot=2)
@@ -102,17 +102,11 @@ def _wgrad(d: WgradDesc, X, dY, dW):
 def _apply_config():
     g = globals()
     c = _config.settings
-    g["FUSED_AMAX"] = bool(c["fused_amax"])      # producers leave max|output| behind for the operand split (see _amax_hint)
     g["USE_BF16X3"] = bool(c["use_split"])
     g["THROUGHPUT_MODE"] = c["split_scheme"] == "f16x1"
     g["SPLIT_SCHEME"] = "f16x2" if c["split_scheme"] == "f16x1" else c["split_scheme"]
-    for name, key in (("GRAD_MERGE", "grad_merge"), ("BN_SPLIT", "bn_split"), ("BN_SKIP_DX", "bn_skip_dx"), ("BN_SKIP_Z", "bn_skip_z"),
-                      ("LSTM_BWD_SPLIT", "lstm_bwd_split"), ("RANK1_DSP_SPLIT", "rank1_dsp_split"), ("RANK1_DWC_SPLIT", "rank1_dwc_split"),
-                      ("LSTM_SKIP_DPRE", "lstm_skip_dpre"), ("FUSE_GATE_LSTM", "fuse_gate_lstm"), ("LSTM_H_PLANES", "lstm_h_planes"),
-                      ("DEFER_WGRAD", "defer_wgrad"), ("CHANNEL_SCALES", "channel_scales"), ("HW2_SINGLE", "hw2_single"),
-                      ("ROW_SPARSITY", "row_sparsity"), ("DIRECT_GRAD", "direct_grad"), ("SKINNY_GEMM", "skinny_gemm"), ("ASYNC_DGRAD", "async_dgrad"),
-                      ("DRT_BATCHED", "drt_batched"), ("RANK1_FUSED", "rank1_fused")):
-        g[name] = bool(c[key])
+    for name, _ in _config.FUSIONS:
+        g[name.upper()] = bool(c[name])
 
 
 _apply_config()
@@ -121,7 +115,7 @@ _apply_config()
 # how often each fused pass ran (tests assert that the benchmark's kernel path, not a fallback, is the one under test)
 FUSION_COUNTS = {"lstm_bwd_split": 0, "bn_bwd_split_operand": 0, "gateconv_lstm": 0, "gateconv_lstm_hplanes": 0,
                  "bn_fwd_split": 0, "bn_fwd_split_operand": 0, "bn_skip_z": 0, "bn_bwd_split": 0, "bn_skip_dx": 0,
-                 "conv_bn_stats": 0, "grad_merge": 0, "rank1_dsp_split": 0, "rank1_dwc_split": 0, "lstm_skip_dpre": 0, "wgrad_multi": 0,
+                 "conv_bn_stats": 0, "grad_merge": 0, "lstm_skip_dpre": 0, "wgrad_multi": 0,
                  "row_sparse_bwd": 0, "fan_in_rows": 0, "direct_grad": 0, "output_gate": 0, "skinny_gemm": 0, "async_dgrad": 0,
                  "drt_fwd_batched": 0, "drt_live_rows": 0, "rank1_fused": 0}
 
@@ -306,7 +300,7 @@ def _amax_hint(device) -> Optional[torch.Tensor]:
     """{scale, amax bits} buffer for a producer kernel that leaves max|output| behind (block max + one guarded atomic per block);
     noted on the produced tensor (notes.py: ``amax``) so that split_op can skip its read-only amax pass.  None when the 2xfp16
     back-end is not in use."""
-    if not USE_BF16X3 or SPLIT_SCHEME != "f16x2" or not FUSED_AMAX:
+    if not _amax_hint_active():
         return None
     key = hip.device_index(device)
     pool = _HINT_POOL.get(key)
@@ -361,7 +355,7 @@ def _nan(device) -> torch.Tensor:
 
 
 def _amax_hint_active() -> bool:
-    return bool(USE_BF16X3 and SPLIT_SCHEME == "f16x2" and FUSED_AMAX)
+    return bool(USE_BF16X3 and SPLIT_SCHEME == "f16x2")
 
 
 def _scale_slot(device) -> torch.Tensor:
@@ -404,7 +398,7 @@ def split_op(x: torch.Tensor, scheme: Optional[str] = None, channel: bool = Fals
         n = xc.numel()
         out = torch.empty(2 * n + 32, dtype=torch.float16, device=x.device)
         Cc = xc.shape[-1]
-        if channel and CHANNEL_SCALES and hint is None and xc.dim() >= 2 and Cc % 16 == 0 and not THROUGHPUT_MODE:
+        if channel and hint is None and xc.dim() >= 2 and Cc % 16 == 0 and not THROUGHPUT_MODE:
             cscale = torch.empty(Cc, dtype=torch.float32, device=x.device)
             L = hip.lib()
             ws = hip.workspace(L.sp_split2_f16_cols_workspace(n // Cc, Cc), x.device, slot=1)
@@ -562,7 +556,7 @@ def _wgrad_b3(d: WgradDesc, Xs, dYs, dW):
         d.x_scale_vec, d.y_scale_vec = int(Xs.kind == "cols"), int(dYs.kind == "cols")
     M, Co, K = d.N_img * d.Ho * d.Wo, d.Co, d.KH * d.KW * d.Ci
     # large single weight gradients whose shape fits the 256 x 256-tile kernel (x-gate conv, sal_conv): hw2_kernel with one segment
-    big = L.sp_conv_wgrad_f16x2_multi_workspace(C.byref(d), 1) if (f16 and HW2_SINGLE and not THROUGHPUT_MODE
+    big = L.sp_conv_wgrad_f16x2_multi_workspace(C.byref(d), 1) if (f16 and not THROUGHPUT_MODE
                                                                    and 2.0 * M * COST_M_SCALE * Co * K >= HW2_SINGLE_MIN_FLOPS) else 0
     ws = hip.workspace(big if big > 0 else (L.sp_conv_wgrad_f16x2_workspace if f16 else L.sp_conv_wgrad_bf16x3_workspace)(C.byref(d)),
                        dW.device, slot=0)
@@ -1431,7 +1425,7 @@ def bn_act(x, gamma, beta, rmean, rvar, residual=None, training=True, momentum=0
         emit_bwd = xn.from_split                             # the producing conv's backward GEMMs read the split gradient
         token = xn.dy_token if (skip_dx and BN_SKIP_DX and emit_bwd) else None
         return _BnActSplit.apply(x, gamma, beta, rmean, rvar, residual, momentum, eps, relu, emit_split, emit_bwd,
-                                 xn.bnstats, res_store, token, skip_z and emit_split and BN_SKIP_DX and BN_SKIP_Z)
+                                 xn.bnstats, res_store, token, skip_z and emit_split and BN_SKIP_DX)
     return _BnAct.apply(x, gamma, beta, rmean, rvar, residual, training, momentum, eps, relu)
 
 
@@ -1656,17 +1650,20 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
     dpre = torch.empty_like(gates)
     dcp = torch.empty_like(c)
     hint, chint = _amax_hint(gates.device), _amax_hint(gates.device)
-    rank1_split_ok = P % 256 == 0 and N3 % 32 == 0 and KP <= 32 and KP % 4 == 0 and not THROUGHPUT_MODE
+    L = hip.lib()
     rc = rows_ctx(step, B)          # samples without loss gradient at this decode step: zero outputs, inputs not read
-    emit = (LSTM_BWD_SPLIT and hint is not None and Cc % 256 == 0 and cbounds[0] is not None and (dh is None or dh_h is not None)
+    emit = (hint is not None and Cc % 256 == 0 and cbounds[0] is not None and (dh is None or dh_h is not None)
             and (dc is None or dc_h is not None) and _scheme_for(C4) == "f16x2")
+    # both gradients of the rank-1 gate term from ONE pass over the split dpre (csrc/rank1_grads.hip; KP = 12 or 20: one or two streams
+    # of 3 x 3 taps), else each from the fp32 dpre.  Decided HERE, before the cell backward is launched: it also decides `skip`
+    fused = bool(emit and need_dsp and need_dwc and P % 256 == 0 and not THROUGHPUT_MODE and L.sp_rank1_grads_applies(B, P, N3, KP, C4))
     if emit:
         FUSION_COUNTS["lstm_bwd_split"] += 1
         planes = torch.empty(2 * dpre.numel() + 32, dtype=torch.float16, device=dpre.device)
-        # skip_fp32 (the caller's other consumers of dpre read its split form): when the two rank-1 gradients do too, the fp32
-        # tensor is allocated (autograd wants one) but never written -- 671 MB per step at the benchmark size
-        skip = (skip_fp32 and fan is not None and LSTM_SKIP_DPRE and (not need_dsp or (RANK1_DSP_SPLIT and rank1_split_ok))
-                and (not need_dwc or (RANK1_DWC_SPLIT and rank1_split_ok)))
+        # skip_fp32 (the caller's other consumers of dpre read its split form): when the rank-1 gradients do too, or are not wanted, the
+        # fp32 tensor is allocated (autograd wants one) but never written -- 671 MB per step at the benchmark size.  The fp32 forms
+        # below read dpre directly, so whatever sends a gradient there must keep it written
+        skip = skip_fp32 and fan is not None and LSTM_SKIP_DPRE and (fused or not (need_dsp or need_dwc))
         if skip:
             FUSION_COUNTS["lstm_skip_dpre"] += 1
             note(dpre).skipped = True        # guards every fp32 reader this process owns (_fp32_required); the fan-in reads the record
@@ -1690,54 +1687,22 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
     if chint is not None:
         note(dcp).amax = chint             # max|dc_prev|: the previous step's cell backward bounds its operand with it
     dsp = dwc = None
-    L = hip.lib()
-    if (need_dsp and need_dwc and emit and RANK1_FUSED and RANK1_DSP_SPLIT and RANK1_DWC_SPLIT and rank1_split_ok
-            and L.sp_rank1_grads_applies(B, P, N3, KP, C4)):
-        # both gradients of the rank-1 gate term from ONE pass over the split dpre the cell backward just wrote (csrc/rank1_grads.hip): dsp on
-        # the matrix pipe against the split form of wc^T, dwc on the vector pipe from the same LDS tiles, spcol as it is -- instead of two
-        # launches of the big GEMM kernels that each re-read the 503 MB of planes, and six small launches preparing their operands
+    if fused:
+        # dsp on the matrix pipe against the split form of wc^T, dwc on the vector pipe from the same LDS tiles, spcol as it is
         FUSION_COUNTS["rank1_fused"] += 1
-        ys = dps
         ws = _split_wcT(wc)             # [B][KP][3C]: K contiguous, one scale per row
         dsp, dwc = torch.empty_like(spcol), torch.empty_like(wc)
         wsp = hip.workspace(L.sp_rank1_grads_workspace(B, P, N3, KP), dpre.device, slot=0)
-        check(L.sp_rank1_grads_f16x2(ptr(ys.buf), ptr(ys.scale), C4, ptr(ws.buf), ptr(ws.scale), ptr(spcol), B, P, N3, KP, ptr(dsp), ptr(dwc),
+        check(L.sp_rank1_grads_f16x2(ptr(dps.buf), ptr(dps.scale), C4, ptr(ws.buf), ptr(ws.scale), ptr(spcol), B, P, N3, KP, ptr(dsp), ptr(dwc),
                                      ptr(wsp), ptr(rc.last) if rc is not None else None, int(step) if rc is not None else 0, hip.stream()),
               "sp_rank1_grads_f16x2")
         return dpre, dcp, dsp, dwc
-    if need_dsp:
+    if need_dsp:        # dsp[b] = dpre[b][:, :3C] x wc[b]: a batched pointwise GEMM with one weight set per sample
         dsp = torch.empty_like(spcol)
-        if emit and RANK1_DSP_SPLIT and rank1_split_ok:
-            # gradient of the spatial-memory taps, dsp[b] = dpre[b][:, :3C] x wc[b]: a batched pointwise GEMM with one weight set
-            # per sample, on the split dpre the cell backward just wrote (its first 3C of 4C channels per row) -- the fp32-MFMA
-            # batched GEMM it replaces read the fp32 dpre (0.5 GB) at ~2 TB/s
-            FUSION_COUNTS["rank1_dsp_split"] += 1
-            xs = dps
-            ws = _split_wcT(wc)             # [B][KP][3C]: K contiguous, one scale per row
-            d = _gemm_desc(P, KP, N3, ldx=C4, ldw=N3, ldc=KP, nbatch=B, sX=P * C4, sW=KP * N3, sC=P * KP)
-            d.w_scale_rows = 1
-            if rc is not None:          # one item per sample: items without loss gradient at this step are zero tiles
-                d.row_last, d.row_step = rc.last.data_ptr(), int(step)
-            check(hip.lib().sp_conv_igemm_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(ws.buf), ptr(ws.scale), None, ptr(dsp),
-                                                hip.stream()), "sp_conv_igemm_f16x2 (batched)")
-        else:
-            _igemm(_gemm_desc(P, KP, N3, ldx=C4, ldw=KP, ldc=KP, mode=1, nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP), dpre, wc, None, dsp)
-    if need_dwc:
+        _igemm(_gemm_desc(P, KP, N3, ldx=C4, ldw=KP, ldc=KP, mode=1, nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP), dpre, wc, None, dsp)
+    if need_dwc:        # dwc[b] = dpre[b][:, :3C]^T x spcol[b]: one TN GEMM per sample (K = the sample's pixels)
         dwc = torch.empty_like(wc)
-        if emit and RANK1_DWC_SPLIT and rank1_split_ok:
-            # filter gradient of the rank-1 gate term, dwc[b] = dpre[b][:, :3C]^T x spcol[b]: one TN GEMM per sample (K = the sample's
-            # pixels) on the split dpre; spcol's KP tap columns are padded to 32 for the 16-channel groups of the split operand, the
-            # kernel stores the first KP columns.  The VALU kernel it replaces read the fp32 dpre at ~2 TB/s (250 us per launch)
-            FUSION_COUNTS["rank1_dwc_split"] += 1
-            ys = dps
-            xs = split_op(torch.nn.functional.pad(spcol, (0, 32 - KP)), "f16x2")
-            d = WgradDesc(N_img=1, Hi=P // 64, Wi=64, Ci=32, ldx=32, Ho=P // 64, Wo=64, Co=N3, ldy=C4, KH=1, KW=1, stride=1, pad=0, dil=1,
-                          ldo=KP, alpha=1.0, nbatch=B, strideX=P * 32, strideY=P * C4, strideO=N3 * KP)
-            if rc is not None:
-                d.row_last, d.row_step = rc.last.data_ptr(), int(step)
-            check(L.sp_conv_wgrad_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(ys.buf), ptr(ys.scale), ptr(dwc), None, hip.stream()),
-                  "sp_conv_wgrad_f16x2 (batched)")
-        elif KP <= 24:
+        if KP <= 24:
             ws = hip.workspace(L.sp_rank1_dwc_workspace(B, P, N3, KP), dpre.device, slot=0)
             check(L.sp_rank1_dwc(ptr(dpre), ptr(spcol), B, P, C4, N3, KP, ptr(ws), ptr(dwc), hip.stream()), "sp_rank1_dwc")
         else:
@@ -1788,7 +1753,7 @@ class _GateConvLstm(Function):
         cbounds = _cell_bounds(c_prev, c)
         # |h| = |o * c| <= |c| <= t + 1: with that bound the epilogue writes h's split operand itself (no max|h| pass, no split pass)
         hplanes = torch.empty(2 * h.numel() + 32, dtype=torch.float16, device=h.device) \
-            if (LSTM_H_PLANES and hint is not None and cbounds[0] is not None and g.Ci % 16 == 0) else None
+            if (hint is not None and cbounds[0] is not None and g.Ci % 16 == 0) else None
 
         def launch():
             check(hip.lib().sp_gateconv_lstm_f16x2(C.byref(d), ptr(xs.buf), ptr(xs.scale), ptr(wsplit.buf), ptr(wsplit.scale),

@@ -81,8 +81,7 @@ def _no_hgate_fwd(M, N, K, Kc, nbatch=1, **kw):        # ... and its forward (N 
     return False if ((N == 512 and K == 18432) or (N == 2048 and K == 4608)) else _pays(M, N, K, Kc, nbatch, **kw)
 
 
-for name, sw in (("f16x2 bench path", dict(COST_M_SCALE=16.0)), ("f16x2, CHANNEL_SCALES off", dict(COST_M_SCALE=16.0, CHANNEL_SCALES=False)),
-                 ("f16x2, rank-1 gradients on fp32", dict(COST_M_SCALE=16.0, RANK1_DSP_SPLIT=False, RANK1_DWC_SPLIT=False)),
+for name, sw in (("f16x2 bench path", dict(COST_M_SCALE=16.0)),
                  ("f16x2, h-gate data gradient on fp32 MFMA", dict(COST_M_SCALE=16.0, _b3_pays=_no_hgate_dgrad)),
                  ("f16x2, h-gate forward + data gradient on fp32 MFMA", dict(COST_M_SCALE=16.0, _b3_pays=_no_hgate_fwd, FUSE_GATE_LSTM=False)),
                  ("bf16x3", dict(COST_M_SCALE=16.0, SPLIT_SCHEME="bf16x3"))):

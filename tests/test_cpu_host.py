@@ -169,6 +169,39 @@ def test_config_switchboard_ignores_stray_environment_variables():
         config.set(split_scheme="fp8")
 
 
+def test_fusion_switches_are_declared_once():
+    """config.FUSIONS is the only declaration of a fusion switch: its default, its env variable and the global that functional reads
+    (NAME.upper()) are one-to-one with the table, and every fusion is on by default"""
+    from scanpaths_amd import config, functional as F
+    names, envs = [n for n, _ in config.FUSIONS], [e for _, e in config.FUSIONS]
+    assert len(set(names)) == len(names) == len(set(envs)) == 10
+    other = {"split_scheme", "use_split", "library", "always_reset_amax"}
+    assert set(config.DEFAULTS) == set(names) | other and all(config.DEFAULTS[n] is True for n in names)
+    assert {e: s for e, (s, _) in config._ENV.items() if s not in other} == {e: n for n, e in config.FUSIONS}
+    assert all(e.startswith("SP_") for e in envs) and dict(config.FUSIONS)["fuse_gate_lstm"] == "SP_FUSE_LSTM"
+    for n, e in config.FUSIONS:
+        assert getattr(F, n.upper()) is True, n
+        parse = config._ENV[e][1]
+        assert parse("0") is False and parse("1") is True
+    # no module global of functional that looks like a switch is left without a row (the back-end globals keep their explicit handling)
+    flags = {k for k, v in vars(F).items() if k.isupper() and isinstance(v, bool)}
+    assert flags == {n.upper() for n in names} | {"USE_BF16X3", "THROUGHPUT_MODE"}, flags
+
+
+def test_a_retired_switch_is_simply_unknown():
+    """no compatibility shim: config.set refuses the name, and its env variable is not a tuning variable any more (neither honoured
+    nor reported)"""
+    import subprocess
+    import sys
+    from scanpaths_amd import config
+    with pytest.raises(KeyError, match="known:.*'bn_skip_dx'"):
+        config.set(rank1_fused=False)
+    code = "import scanpaths_amd.functional as F, scanpaths_amd.config as c; print(c.non_default(), hasattr(F, 'RANK1_FUSED'))"
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True,
+                       env={**os.environ, "SP_ALLOW_ENV_TUNING": "1", "SP_RANK1_FUSED": "0", "SP_SPLIT_SCHEME": "", "SP_LIBRARY": ""})
+    assert r.returncode == 0 and r.stdout.split() == ["{}", "False"] and "SP_RANK1_FUSED" not in r.stderr, (r.stdout, r.stderr)
+
+
 def test_sampling_refuses_cpu():
     """the sampler is a device kernel now (tests/test_inference_gpu.py holds the known answers); no CPU path"""
     from scanpaths_amd import hip

@@ -281,6 +281,42 @@ def test_lstm_cell_and_gate_conv(fused):
         _close(wrg[s].grad, wrr[s].grad, 1e-5, f"dwr{s}")
 
 
+def test_lstm_cell_keeps_fp32_gate_gradient_for_fp32_rank1_gradients():
+    """the cell backward emits its 2xfp16 split operand (C % 256 == 0, bounds of max|dh| and max|c| known) and xg's fan-in would take
+    it from the record -- but KP = 16 is no tap count of the one-pass rank-1 kernel (sp_rank1_grads_applies: 12 or 20), so dsp and dwc
+    come from the fp32 kernels, which read the fp32 gate gradient: it must be WRITTEN (lstm_skip_dpre == 0).  2 samples x 256 pixels,
+    C = 256: the smallest shape that takes this decision.  Gradients against an fp64 restatement of the cell, same bars as
+    test_lstm_cell_and_gate_conv."""
+    from scanpaths_amd import functional as F, hip
+    if F.SPLIT_SCHEME != "f16x2" or not F.USE_BF16X3:
+        pytest.skip("2xfp16 back-end not active")
+    dev = _dev()
+    B, Hm, Wm, C, KP = 2, 16, 16, 256, 16
+    P = Hm * Wm
+    assert hip.lib().sp_rank1_grads_applies(B, P, 3 * C, KP, 4 * C) == 0
+    Xg, spcol, wc = _rand(B, Hm, Wm, 4 * C, seed=50), _rand(B, P, KP, seed=51), _rand(B, 3 * C, KP, seed=52, scale=0.2)
+    w1, w2 = _rand(B, Hm, Wm, C, seed=53), _rand(B, Hm, Wm, C, seed=54)
+    dbl = lambda t: t.double().requires_grad_(True)
+    Xr, sr, wr = dbl(Xg), dbl(spcol), dbl(wc)
+    pre = Xr.view(B, P, 4 * C) + torch.cat([torch.bmm(sr, wr.transpose(1, 2)), torch.zeros(B, P, C, dtype=torch.float64)], 2)
+    i, o, g = pre[..., :C].sigmoid(), pre[..., 2 * C:3 * C].sigmoid(), pre[..., 3 * C:].tanh()
+    hr = (o * (i * g)).view(B, Hm, Wm, C)                        # no previous state: c = i * g
+    (Xr.sum() + (hr * w1.double()).sum() + (hr * w2.double()).sum()).backward()
+
+    Xd, sd, wd = (t.to(dev).requires_grad_(True) for t in (Xg, spcol, wc))
+    xg, other = F.fanout(Xd, 2)                                  # xg's only other consumer: its fan-in could take a split operand
+    h, _ = F.lstm_cell_rank1(xg, None, None, sd, wd)
+    h1, h2 = F.fanout(h, 2)                                      # two consumers: dh arrives summed, with its max|.| hint
+    F.reset_fusion_counts()
+    (other.sum() + (h1 * w1.to(dev)).sum() + (h2 * w2.to(dev)).sum()).backward()
+    torch.cuda.synchronize()
+    counts = {k: F.FUSION_COUNTS[k] for k in ("lstm_bwd_split", "rank1_fused", "lstm_skip_dpre")}
+    assert counts == {"lstm_bwd_split": 1, "rank1_fused": 0, "lstm_skip_dpre": 0}, counts
+    _close(Xd.grad, Xr.grad, 1e-5, "dXg")
+    _close(sd.grad, sr.grad, 1e-5, "dspcol")
+    _close(wd.grad, wr.grad, 1e-5, "dwc")
+
+
 def test_list_attention_and_small_ops():
     from scanpaths_amd import functional as F
     T, R, D = 5, 6, 1200

@@ -1,4 +1,4 @@
-"""Diagnose HIP-graph replay vs eager at different input amplitudes (encoder only / full model; SP_NO_AMAX_HINT, back-ends)."""
+"""Diagnose HIP-graph replay vs eager at different input amplitudes (encoder only / full model; back-ends)."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
