@@ -381,7 +381,9 @@ int sp_select_rows_bwd(const float* dout, const unsigned char* sel, int64_t rows
  * of the decode loop reads, AiR/models/baseline_attention.py:160-166,311-336), bit 1 = the duration half (mu, sigma2, :155-159: read by
  * nothing inside the recurrence); 3 = both.  The decode loop runs parts = 1 per step and parts = 2 ONCE behind the loop over T x nheads
  * virtual heads (head (t, i) of B rows; dpre = the sites of all steps from one sp_drt_direct_fwd launch over T x B rows).  Arguments of
- * the half that is not asked for may be NULL. */
+ * the half that is not asked for may be NULL.
+ * dh, dw = sites of the 7x7 stride-5 pad-2 duration conv along Hm, Wm: floor((len - 3) / 5) + 1, and 0 for a side below 3 pixels (the
+ * window does not fit: the reference's conv raises).  SP_EINVAL for a side below 3 and for dh * dw > 256, before any launch. */
 int sp_head_finish_fwd(const float* Z, int B, int Hm, int Wm, int ldz, int nheads, int HC, const float* cb,
                        int cb_per_sample /* 1: cb is [B][nheads][HC] (COCO per-task heads) */, const float* w2, const float* b2, int softmax, float* logits, float* amap, float* mu,
                        float* sigma2, float* drt,

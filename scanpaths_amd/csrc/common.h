@@ -58,6 +58,12 @@ static inline bool sp_reset_needed(hipStream_t s) {
 
 static inline int64_t sp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Sites of the 7x7 stride-5 pad-2 duration conv (drt_layer_1) along a side of `len` pixels: floor((len + 4 - 7) / 5) + 1.  The ONE place
+// that computes it (decoder.hip head epilogue, head_direct.hip make_axis): written as the plain C expression, sides 1 and 2 gave 1 site
+// (C division truncates toward zero) where the Python side's floor division and the reference give 0 -- a 7-wide window does not fit
+// into 2 + 4 padded pixels.  0 = the side is refused (SP_EINVAL / -1) before any launch.
+static inline int sp_drt_sites(int len) { return len < 3 ? 0 : (len - 3) / 5 + 1; }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

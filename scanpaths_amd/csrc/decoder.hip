@@ -941,7 +941,7 @@ extern "C" int sp_head_finish_fwd(const float* Z, int B, int Hm, int Wm, int ldz
     if ((parts & 1) && (!Z || !logits || !amap)) return SP_ENULL;
     if ((parts & 2) && (!w2 || !b2 || !mu || !sigma2 || !drt)) return SP_ENULL;
     if (parts == 2 && !dpre) return SP_ENULL;          // without Z the duration sites come from sp_drt_direct_fwd
-    const int dh = (Hm + 4 - 7) / 5 + 1, dw = (Wm + 4 - 7) / 5 + 1;
+    const int dh = sp_drt_sites(Hm), dw = sp_drt_sites(Wm);
     if (zc <= 0) zc = HC;
     if (HC < 52 || dh * dw > MAXS || dh < 1 || dw < 1 || zc < 2 || ((parts & 2) && !dpre && zc < 2 + NTAP) || ((parts & 1) && nheads * zc > ldz))
         return SP_EINVAL;
@@ -963,7 +963,7 @@ extern "C" int sp_head_finish_bwd(const float* dlogits, int64_t dlogits_ld, cons
     if ((parts & 1) && (!dlogits || !logits || !amap || !dZ)) return SP_ENULL;
     if ((parts & 2) && (!dmu || !dsigma2 || !sigma2 || !drt || !w2 || !dw2_partial || !db2_partial)) return SP_ENULL;
     if (parts == 2 && !ddpre) return SP_ENULL;
-    const int dh = (Hm + 4 - 7) / 5 + 1, dw = (Wm + 4 - 7) / 5 + 1;
+    const int dh = sp_drt_sites(Hm), dw = sp_drt_sites(Wm);
     if (zc <= 0) zc = HC;
     if (HC < 52 || dh * dw > MAXS || dh < 1 || dw < 1 || zc < 2 || ((parts & 2) && !ddpre && zc < 2 + NTAP) || ((parts & 1) && nheads * zc > ldz))
         return SP_EINVAL;

@@ -29,7 +29,7 @@ struct AxisCls {
 };
 
 static bool make_axis(int len, AxisCls& a) {
-    a.n = (len + 4 - 7) / 5 + 1;
+    a.n = sp_drt_sites(len);
     a.ncls = 0;
     a.len = len;
     if (a.n < 1 || a.n > MAXSITE) return false;

@@ -415,6 +415,45 @@ def test_split_counts_of_the_weight_gradient_kernels_follow_the_round_quantisati
     assert splits(fp, desc(32, 80, 128, 64, 64, 1)) == 512         # one tile: 512 workgroups (was 128)
 
 
+def test_decoder_entry_points_refuse_shapes_outside_their_domain_before_any_launch():
+    """Host logic, no GPU: the argument checks of the decoder's small kernels (csrc/decoder.hip, the rowsum pair of csrc/bn_pool.hip) return
+    SP_EINVAL (-1) before they touch a device, so dummy non-null HOST buffers are enough.  The site count of the 7x7 stride-5 pad-2 duration
+    conv (common.h sp_drt_sites) is 0 for a side of 1 or 2 pixels, as the reference's conv (it raises there) and functional.py's floor division
+    say -- the plain C expression (len + 4 - 7) / 5 + 1 truncated toward zero to ONE site, passed the `dh < 1` check and would have launched
+    a kernel that writes a site into a 0-element buffer."""
+    from scanpaths_amd import hip
+    L = hip.lib()
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.addressof(buf)
+    # duration sites: sides 1 and 2 have none
+    assert L.sp_head_num_classes(2, 8) == -1 and L.sp_head_num_classes(8, 1) == -1 and L.sp_head_num_classes(1, 1) == -1
+    assert L.sp_head_num_classes(3, 3) == 1 and L.sp_head_num_classes(7, 8) >= 1
+
+    def head_fwd(Hm, Wm, parts=3, zc=2, ldz=2):
+        return L.sp_head_finish_fwd(p, 1, Hm, Wm, ldz, 1, 64, p, 0, p, p, 0, p, p, p, p, p, p, zc, parts, None)
+
+    def head_bwd(Hm, Wm, parts=3, zc=2, ldz=2):
+        return L.sp_head_finish_bwd(p, 0, p, p, p, p, p, p, p, 1, Hm, Wm, ldz, 1, 64, p, 0, p, p, p, p, p, zc, parts, None, None)
+    for Hm, Wm in ((2, 8), (8, 2), (1, 8), (8, 1), (1, 1), (2, 2)):
+        for parts in (1, 2, 3):
+            assert head_fwd(Hm, Wm, parts) == -1, (Hm, Wm, parts)
+            assert head_bwd(Hm, Wm, parts) == -1, (Hm, Wm, parts)
+    # dh * dw = 16 * 17 = 272 sites > MAXS = 256 (78 x 78 = 256 sites is the largest square map)
+    assert head_fwd(78, 83) == -1 and head_bwd(78, 83) == -1
+    # attention over a memory list: T <= MAXT = 40
+    assert L.sp_listatt_fwd(p, p, 41, 1, 4, p, p, None) == -1 and L.sp_listatt_fwd(p, p, 0, 1, 4, p, p, None) == -1
+    assert L.sp_listatt_bwd(p, p, p, p, 41, 1, 4, p, p, None) == -1
+    # semantic pooling forward: a thread owns a channel quad, 128 quads per block
+    assert L.sp_sempool_fwd(p, p, 1, 1, 4, 516, 1.0, p, p, 0, None) == -1
+    assert L.sp_sempool_fwd(p, p, 1, 1, 4, 6, 1.0, p, p, 0, None) == -1
+    assert L.sp_sempool_bwd(p, p, p, p, 1, 1, 4, 6, 1.0, p, p, None, 0, 0, None) == -1
+    # im2col: 9 columns per stream must fit into the row
+    assert L.sp_im2col3x3_1ch(p, 2, 1, 2, 2, 17, p, None) == -1 and L.sp_col2im3x3_1ch(p, 2, 1, 2, 2, 17, p, None) == -1
+    assert L.sp_im2col3x3_1ch(p, 1, 1, 2, 2, 8, p, None) == -1
+    # channel mean: rows are read as float4
+    assert L.sp_rowsum(p, 1, 6, 1.0, p, None) == -1 and L.sp_rowsum_bwd(p, 1, 6, 1.0, p, None) == -1
+
+
 def test_conv_geometry_fills_the_descriptors_of_its_three_gemms():
     """Host logic, no GPU: functional.ConvGeom is the one place that fills sp_conv_desc / sp_wgrad_desc for a conv's forward, data-gradient
     and weight-gradient GEMM.  Every field is pinned against the values the call sites passed by hand before it existed, written out
