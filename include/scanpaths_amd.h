@@ -618,6 +618,29 @@ int sp_scan_likelihood(const float* probs, const float* mu, const float* sigma2,
                        const int* order, int R, int T, int Hm, int Wm, int S, int ncol, double frame_w, double frame_h,
                        double uniform_mix, double* LL, double* IG, double* NSS, double* AUC, double* DLL, double* CONT, double* TERM,
                        int* dropped, void* stream);
+/* Gaussian kernel sums between fixations with a leave-group-out rule, at K bandwidths at once (csrc/scankde.hip):
+ * the KDE centre-bias baseline of IG and the human gold standard of the likelihood scorers.  fix: N rows of ncol >= 2 doubles (x, y, ..)
+ * SORTED BY IMAGE: image g of G owns rows img_start[g] .. img_start[g + 1] (img_start [G + 1], img_start[G] = N), in an order fixed by
+ * the image's own data; img[i] = the image, path[i] = the scanpath and step[i] = the position in its scanpath of fixation i.
+ * bandwidths: K values > 0 and finite, in pixels of the frame, IN HOST MEMORY (they are checked and travel as kernel arguments), K at
+ * most the max_bandwidths() value below; Hm * Wm at most sp_scan_likelihood_max_cells().  A fixation outside the frame or with a
+ * non-finite coordinate is dropped: it is no source, and as a query it scores NaN and gets valid 0.  The cell of a fixation is that of
+ * sp_scan_likelihood.  Cell kernel of source j at bandwidth b: k_j(c) = wy_j(row) wx_j(col), wx_j(col) = exp(ax(col) - max ax) /
+ * sum_col exp(ax(col) - max ax), ax(col) = -(cx(col) - x_j)^2 / (2 b^2), cx(col) = (col + 0.5) frame_w / Wm, wy likewise on y.
+ *   leave 0 ("image"):  tables [G][K][P] = the sum of k_j over the valid sources of all OTHER images (prefix plus suffix over the
+ *     images: summed directly, an exact zero row for G = 1); nother [G] their number.  With LL: LL [N][K] = log2(P ((1 - u) q + u / P)),
+ *     q = tables[img[i]][k][cell of i] / M, others [N] = M = nother[img[i]].  own [G][K][P] is work space.
+ *   leave 1 ("scanpath") / 2 ("scanpath_step"):  the sources are the valid fixations of the same image with another path (and, for 2,
+ *     the same step), summed serially in row order; blocks [nblocks][2] = (image, b) lists every block b of 256 consecutive (row, k)
+ *     items of every image with rows: b < ceil(rows * K / 256).
+ * LL is NaN for a dropped query and for M = 0; a zero q at u = 0 scores -inf.  prep [N][K][4] is work space.  Every element of every
+ * output is written; no floating-point atomics; repeated calls are bit-identical, and leave 1 / 2 values of an image do not depend on
+ * the other images of the call. */
+int sp_scan_kde_max_bandwidths(void);
+int sp_scan_kde(const double* fix, const int* path, const int* step, const int* img, const int64_t* img_start, const int* blocks,
+                int64_t N, int ncol, int G, int nblocks, const double* bandwidths, int K, int Hm, int Wm, double frame_w,
+                double frame_h, double uniform_mix, int leave, double* prep, double* own, int* nother, double* tables, double* LL,
+                int* others, int* valid, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -156,6 +156,9 @@ SIGNATURES = {
     "sp_scan_likelihood_max_cells": (_I, []),
     "sp_scan_likelihood": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double,
                                 _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sp_scan_kde_max_bandwidths": (_I, []),
+    "sp_scan_kde": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P,
+                         _P, _P, _P, _P]),
     "sp_sample_actions": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, _P, _P]),
     "sp_generate_scanpath": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sp_beam_search": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),

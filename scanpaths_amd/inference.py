@@ -80,8 +80,28 @@ def run_likelihood_loop(model, loader: Iterable[dict], *, uniform_mix, metrics=(
     small device->host copy (the scores; the distributions stay on the device).  loader yields run_test_loop's batches; "performances"
     is read when the model has the two AiR heads ("good_all_actions_prob" in its output), and with a baseline of more than one row
     "baseline_rows" names the row of every sample's image.  The key of a sample is its question id.
-    Returns (means, per_key of every batch): means = the batches' pooled means merged by utils.evaluation.LikelihoodTable."""
-    from .utils.evaluation import LikelihoodTable, likelihood_evaluation
+    Returns (means, per_key of every batch): means = the batches' pooled means merged by utils.evaluation.LikelihoodTable.
+    With the human gold standard next to it: run_likelihood_gold_loop."""
+    return _likelihood_loop(model, loader, None, uniform_mix=uniform_mix, metrics=metrics, min_length=min_length, baseline=baseline,
+                            ablate_attention_info=ablate_attention_info, frame_size=frame_size, map_shape=map_shape)
+
+
+@torch.no_grad()
+def run_likelihood_gold_loop(model, loader: Iterable[dict], *, gold_standard, uniform_mix, metrics=("LL", "NSS", "AUC"), min_length=0,
+                             baseline=None, ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None
+                             ) -> Tuple[dict, List[dict]]:
+    """run_likelihood_loop with the ceiling: gold_standard is None (then this IS run_likelihood_loop) or a dict of the keywords of
+    utils.evaluation.likelihood_gold_standard_evaluation (bandwidth, uniform_mix, max_length[, same_step, map_shape]; frame_size
+    defaults to this call's).  Every batch is then also scored by it; its "GOLD" entries join the same LikelihoodTable and the batch's
+    per_key ("dropped" stays the likelihood scorer's: the same fixations are not counted twice), so that
+    utils.evaluation.information_gain_explained(means, means) reads the explained share off the returned means."""
+    return _likelihood_loop(model, loader, gold_standard, uniform_mix=uniform_mix, metrics=metrics, min_length=min_length,
+                            baseline=baseline, ablate_attention_info=ablate_attention_info, frame_size=frame_size, map_shape=map_shape)
+
+
+def _likelihood_loop(model, loader, gold_standard, *, uniform_mix, metrics, min_length, baseline, ablate_attention_info, frame_size,
+                     map_shape):
+    from .utils.evaluation import LikelihoodTable, likelihood_evaluation, likelihood_gold_standard_evaluation
     model.eval()
     table, per_batch = LikelihoodTable(), []
     for batch in loader:
@@ -94,5 +114,10 @@ def run_likelihood_loop(model, loader: Iterable[dict], *, uniform_mix, metrics=(
                                                batch.get("baseline_rows"), baseline, uniform_mix=uniform_mix, metrics=metrics,
                                                min_length=min_length, frame_size=frame_size, map_shape=map_shape)
         table.add(means)
+        if gold_standard is not None:
+            gold, gold_keys = likelihood_gold_standard_evaluation(batch["fix_vectors"], batch["question_ids"],
+                                                                  **dict({"frame_size": frame_size}, **gold_standard))
+            table.add({k: v for k, v in gold.items() if k != "dropped"})
+            per_key["GOLD"] = gold_keys["GOLD"]
         per_batch.append(per_key)
     return table.result(), per_batch

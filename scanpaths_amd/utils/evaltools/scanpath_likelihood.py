@@ -23,8 +23,10 @@ NaN in the spatial outputs, counted in "dropped".  With Z = the sum of the step'
          log2(p_0 / (Z + p_0)); -inf for n' < min_length and n' < T.
 Per-fixation outputs are NaN for t >= min(n, T); "n" = min(n, T).  No epsilon goes inside any logarithm: uniform_mix is the only
 regulariser, it has no default, and with 0 a zero probability scores -inf, reported as such.  One upload, one launch and one copy back
-per call; probs, mu and sigma2 stay on the device.  There is no CPU path, no map of more than MAX_CELLS cells, no human gold-standard
-row and no conditioning on earlier human fixations (the model has none)."""
+per call; probs, mu and sigma2 stay on the device.  There is no CPU path, no map of more than MAX_CELLS cells and no conditioning on
+earlier human fixations (the model has none).  The two reference points the bits are read against -- the kernel-density centre-bias
+baseline for "IG" (kde_cell_baselines, in place of cell_baselines' raw histogram) and the human gold-standard row -- are
+scanpath_kde.py's."""
 from __future__ import annotations
 
 from typing import Dict, Optional, Tuple

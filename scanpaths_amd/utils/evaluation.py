@@ -838,6 +838,54 @@ def likelihood_evaluation(predict, fix_vectors, keys, performances=None, image_k
     return means, per_key
 
 
+def likelihood_gold_standard_evaluation(fix_vectors, keys, *, bandwidth, uniform_mix, max_length, same_step=False,
+                                        frame_size=(240, 320), map_shape=(30, 40)):
+    """The human gold standard of likelihood_evaluation's "LL" (evaltools/scanpath_kde.py, csrc/scankde.hip): every
+    fixation of a subject is scored under the kernel density estimate of the OTHER subjects' fixations on the same sample, in bits over
+    uniform -- what the people who saw the image tell about where one more of them looks.  fix_vectors[i]: the subjects' fixation
+    vectors of sample i, keys[i]: its key, as likelihood_evaluation takes them; each sample is one image.  bandwidth (pixels of the
+    frame; kde_bandwidth_search finds it) and uniform_mix have no defaults; max_length is required: the model's T, so that the ceiling
+    is pooled over the fixations the model is scored on.  same_step=True keeps only the other subjects' fixation at the same position
+    t (leave="scanpath_step"): step t against fixation t, the footing the model is scored on.  A sample with one subject scores NaN.
+    Returns (means, per_key) in exactly likelihood_evaluation's format with the one metric "GOLD"; LikelihoodTable merges it."""
+    from .evaltools.scanpath_kde import kde_leave_out_likelihood
+    keys = list(keys)
+    if len(fix_vectors) != len(keys):
+        raise ValueError("one key per sample is required")
+    if max_length is None:
+        raise ValueError("max_length is required: the model's number of decode steps")
+    index, _ = _key_index(keys, None)
+    paths = [fv for subjects in fix_vectors for fv in subjects]
+    sample = np.repeat(np.arange(len(keys), dtype=np.int64), [len(subjects) for subjects in fix_vectors])
+    res = kde_leave_out_likelihood(paths, sample, frame_size, map_shape, bandwidth=bandwidth, uniform_mix=uniform_mix,
+                                   leave="scanpath_step" if same_step else "scanpath", max_length=max_length)
+    G, key_of = len(index), np.array([index[keys[i]] for i in sample], dtype=np.int64)
+    met = np.arange(res["LL"].shape[1])[None, :] < res["n"][:, None]             # [S, Tmax]: a fixation that counts
+    v, owner = res["LL"][met], np.broadcast_to(key_of[:, None], met.shape)[met]
+    ok = ~np.isnan(v)
+    ksum, kcnt = np.bincount(owner[ok], weights=v[ok], minlength=G), np.bincount(owner[ok], minlength=G)
+    per_key = {"keys": list(index), "GOLD": np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan),
+               "dropped": np.bincount(key_of, weights=res["dropped"], minlength=G).astype(np.int64)}
+    total, count = float(v[ok].sum()), int(ok.sum())
+    means = {"GOLD": total / count if count else float("nan"), "GOLD_sum": total, "GOLD_count": count, "GOLD_nan": int((~ok).sum()),
+             "GOLD_nan_keys": int(np.isnan(per_key["GOLD"]).sum()), "dropped": int(res["dropped"].sum())}
+    return means, per_key
+
+
+def information_gain_explained(means, gold_means) -> dict:
+    """The share of the explainable information a model explains (Kümmerer, Wallis & Bethge 2015): means holds "LL" and "IG" of
+    likelihood_evaluation / LikelihoodTable, gold_means "GOLD" of likelihood_gold_standard_evaluation (the same dict when one table
+    merged both).  "BASE" = LL - IG, the baseline's bits over uniform; "IG_gold" = GOLD - BASE, the gold standard's information gain
+    over the baseline; "IGE" = IG / IG_gold; and the "LL_count" / "IG_count" / "GOLD_count" the three were pooled from (0 for a missing
+    one).  NaN where an input is missing, and IGE also where IG_gold is not > 0."""
+    nan = float("nan")
+    ll, ig, gold = (float(m.get(k, nan)) for m, k in ((means, "LL"), (means, "IG"), (gold_means, "GOLD")))
+    base = ll - ig
+    ig_gold = gold - base
+    return {"BASE": base, "IG_gold": ig_gold, "IGE": ig / ig_gold if ig_gold > 0 else nan, "LL_count": int(means.get("LL_count", 0)),
+            "IG_count": int(means.get("IG_count", 0)), "GOLD_count": int(gold_means.get("GOLD_count", 0))}
+
+
 class LikelihoodTable:
     """The pooled means of likelihood_evaluation over several batches, merged exactly: add(means) sums every metric's "_sum",
     "_count", "_nan" and "_nan_keys" entry and "dropped"; result() = the means dict of all batches as one call would give it (a key
