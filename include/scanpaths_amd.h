@@ -641,6 +641,32 @@ int sp_scan_kde(const double* fix, const int* path, const int* step, const int* 
                 int64_t N, int ncol, int G, int nblocks, const double* bandwidths, int K, int Hm, int Wm, double frame_w,
                 double frame_h, double uniform_mix, int leave, double* prep, double* own, int* nother, double* tables, double* LL,
                 int* others, int* valid, void* stream);
+/* Target-search efficiency (csrc/scansearch.hip), float64, every operation rounded on its own.  A box is (x_min,
+ * y_min, x_max, y_max), half-open: a point is inside iff x_min <= x < x_max && y_min <= y < y_max, compared in double; no box coordinate is
+ * converted to an integer, so huge, negative, empty, inverted and NaN boxes are harmless and hold nothing.
+ * sp_scan_target_hits (one wavefront per scanpath): nscan scanpaths in the fixation layout of sp_scan_sed_stde, box [nscan][4] one per
+ * scanpath.  Only the first min(n, max_steps) fixations count; a fixation with a non-finite coordinate is never inside.  hit [nscan] =
+ * the index of the first fixation inside, -1 for none;  path [nscan] = the sum of sqrt(dx*dx + dy*dy) over consecutive fixations up to
+ * the hit, added left to right in index order (0 for a hit at 0, NaN without a hit);  spr [nscan] = |fix_0 - centre| / path, centre =
+ * ((x_min + x_max) / 2, (y_min + y_max) / 2), not clipped (1.0 for a hit at 0, NaN without a hit).  A non-finite coordinate before the
+ * hit makes path and spr NaN.  A count outside [0, sp_scan_max_fixations()] gives -1 / NaN / NaN and none of its rows is read.  Each
+ * output may be NULL (not all).  ncol >= 2, nscan >= 1, max_steps >= 1.
+ * sp_scan_target_mass (one block per box, one launch): probs [R][T][1 + Hm * Wm] float32 as sp_scan_likelihood reads it, box [NB][4] in
+ * frame pixels, box_row [NB] = the row of probs of each box (any number of boxes per row).  Cell (r, c) belongs to a box iff the pixel
+ * the sampler emits for it, in the sampler's float32 arithmetic (fmaf((float)c, xg, 0.5f * xg): ONE rounding, as sp_generate_scanpath's
+ * kernel compiles; xg = (float)(frame_w / Wm); rows likewise) widened to double, is inside: a rectangle of cells [r0, r1) x [c0, c1), cells [NB] its size.  Per step t, with p0 = action 0:
+ *   Z = sum of the P cells;  D = Z + p0 for t >= min_length, else Z;  q = p0 / D for t >= min_length, else 0;  m = (sum of the box's
+ *   cells) / D;  A_0 = 1, A_{t+1} = A_t * ((1 - q) - m);  MASS_t = m, HIT_t = A_t * m, TFP_t = HIT_0 + .. + HIT_t left to right, each
+ *   [NB][T].
+ * Sums: every lane adds the cells (of the map; of the box numbered in row-major order of its rectangle) lane, lane + 64, .. in that
+ * order, the 64 partial sums combine by the xor butterfly 32, 16, .., 1.  D == 0 or a NaN in D, m or q gives NaN in all three at that
+ * step and every later step of the box.  A box_row outside [0, R) gives cells -1 and NaN everywhere and reads nothing of probs.  Each
+ * output may be NULL (not all); every element of every output given is written.  Hm and Wm in [1, 1024] (no cell limit), frame_w and
+ * frame_h > 0 and finite, min_length >= 0. */
+int sp_scan_target_hits(const double* fix, int ncol, const int64_t* start, const int* count, const double* box, int nscan, int max_steps,
+                        int* hit, double* path, double* spr, void* stream);
+int sp_scan_target_mass(const float* probs, const double* box, const int* box_row, int R, int T, int Hm, int Wm, int NB, double frame_w,
+                        double frame_h, int min_length, double* MASS, double* HIT, double* TFP, int* cells, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -159,6 +159,8 @@ SIGNATURES = {
     "sp_scan_kde_max_bandwidths": (_I, []),
     "sp_scan_kde": (_I, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P,
                          _P, _P, _P, _P]),
+    "sp_scan_target_hits": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
+    "sp_scan_target_mass": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P]),
     "sp_sample_actions": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_uint64, _P, _P, _P, _P]),
     "sp_generate_scanpath": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "sp_beam_search": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P]),

@@ -121,3 +121,29 @@ def _likelihood_loop(model, loader, gold_standard, *, uniform_mix, metrics, min_
             per_key["GOLD"] = gold_keys["GOLD"]
         per_batch.append(per_key)
     return table.result(), per_batch
+
+
+@torch.no_grad()
+def run_search_efficiency_loop(model, loader: Iterable[dict], *, boxes, min_length, max_steps, human_curve=None,
+                               ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None) -> Tuple[dict, List[dict]]:
+    """The model's own target-fixation probability curve over a loader, exactly and without sampling
+    (utils.evaluation.search_efficiency_model_evaluation): per batch ONE eval-mode forward, ONE sp_scan_target_mass launch and ONE small
+    device->host copy (the curves; the distributions stay on the device).  loader yields run_test_loop's batches; "tasks" is passed to the
+    model when the batch has it (the COCO-Search18 signature), "performances" is read when the model has the two AiR heads
+    ("good_all_actions_prob" in its output).  The key of a sample is its question id; boxes: key -> (x_min, y_min, x_max, y_max) in the
+    pixels of frame_size.  min_length is the sampler's and has no default; human_curve (optional, [max_steps]): for "PM".
+    Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.SearchEfficiencyTable."""
+    from .utils.evaluation import SearchEfficiencyTable, search_efficiency_model_evaluation
+    model.eval()
+    table, per_batch = SearchEfficiencyTable(), []
+    for batch in loader:
+        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
+        if ablate_attention_info:
+            attention_maps = attention_maps * 0
+        predict = model(images, attention_maps, batch["tasks"].cuda()) if "tasks" in batch else model(images, attention_maps)
+        means, per_key = search_efficiency_model_evaluation(
+            predict, batch["question_ids"], boxes, min_length=min_length, max_steps=max_steps,
+            performances=batch["performances"] if "good_all_actions_prob" in predict else None, frame_size=frame_size, map_shape=map_shape)
+        table.add(means)
+        per_batch.append(per_key)
+    return table.result(human_curve), per_batch

@@ -906,3 +906,168 @@ class LikelihoodTable:
                 m = k[:-len("_count")]
                 out[m] = self.parts[m + "_sum"] / self.parts[k] if self.parts[k] else float("nan")
         return out
+
+
+# ---- target-search efficiency (evaltools/search_efficiency.py, csrc/scansearch.hip) --------------------------------------
+def _boxes_of(index, boxes) -> np.ndarray:
+    """float64 [G, 4]: the box of every key, in the index's order; a key without a box is an error, not a silent drop"""
+    from .evaltools.search_efficiency import _check_boxes
+    missing = [k for k in index if k not in boxes]
+    if missing:
+        raise ValueError(f"key {missing[0]!r} ({len(missing)} in all) has no box")
+    return _check_boxes([boxes[k] for k in index])
+
+
+def _hit_tables(prefix, res, key_of, G, max_steps):
+    """target_hits' result of a set of scanpaths with their keys -> (means, per_key) entries under prefix: the hit curve pooled over the
+    scanpaths (numerators "_sum" float64 [max_steps] -- integers, hence exact -- over "_count"), its area, and the mean scanpath ratio
+    over the scanpaths that hit"""
+    from .evaltools.search_efficiency import hit_counts, tfp_auc
+    key_of = np.asarray(key_of, dtype=np.int64)
+    hit, spr = res["hit"], res["SPR"]
+    num = np.stack([hit_counts(hit[key_of == g], max_steps) for g in range(G)]) if G else np.zeros((0, max_steps))
+    cnt = np.bincount(key_of, minlength=G)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        curves = np.where(cnt[:, None] > 0, num / np.maximum(cnt, 1)[:, None], np.nan)
+    ok = ~np.isnan(spr)
+    ssum, scnt = np.bincount(key_of[ok], weights=spr[ok], minlength=G), np.bincount(key_of[ok], minlength=G)
+    per_key = {prefix + "TFP": curves, prefix + "TFP_AUC": curves.sum(1), prefix + "SPR": np.where(scnt > 0, ssum / np.maximum(scnt, 1), np.nan)}
+    total, S = hit_counts(hit, max_steps), int(len(hit))
+    curve = total / S if S else np.full(max_steps, np.nan)
+    nspr = int(ok.sum())
+    means = {prefix + "TFP": curve, prefix + "TFP_sum": total, prefix + "TFP_count": S, prefix + "TFP_AUC": tfp_auc(curve),
+             prefix + "SPR": float(spr[ok].sum()) / nspr if nspr else float("nan"), prefix + "SPR_sum": float(spr[ok].sum()),
+             prefix + "SPR_count": nspr}
+    return means, per_key
+
+
+def search_efficiency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, boxes, *, max_steps, image_keys=None):
+    """Did the scanpaths reach the target, and how fast (Yang et al. 2020; Mondal et al. 2023): the target-fixation probability after
+    1 .. max_steps fixations, its area, the scanpath ratio, and the probability mismatch against the human curve, for predicted
+    scanpaths and for the human ones, grouped by key as scanpath_distance_evaluation groups them.  boxes: key -> (x_min, y_min, x_max,
+    y_max), half-open, in the pixels of the fixations' frame; a key of gt_keys without a box raises ValueError.  image_keys[i]
+    (optional): the image of gt_fix_vectors[i] (one key on two images raises ValueError).  max_steps has no default: only the first
+    max_steps fixations of a scanpath count.  All scanpaths of the call are scored in one launch (evaltools.search_efficiency.target_hits).
+    Returns (means, per_key).  means["TFP"] float64 [max_steps] = the share of ALL predicted scanpaths whose first fixation inside the
+    box is among their first k + 1, ["TFP_AUC"] = its sum, ["SPR"] = the mean of |fixation 0 - box centre| / path up to the hit (not
+    clipped) over the scanpaths that hit; ["human_TFP"] / ["human_TFP_AUC"] / ["human_SPR"] the same over the human scanpaths; ["PM"] =
+    sum_k |TFP_k - human_TFP_k|; and the entries a table needs (SearchEfficiencyTable): [name + "_sum"] / [name + "_count"] = the
+    numerator (for a curve: float64 [max_steps] of integer counts) and the number of scanpaths behind each mean.  per_key: "keys" and
+    the same names per key in first-appearance order of gt_keys -- curves [G, max_steps], the rest [G]; NaN where a key has no scanpath
+    (no hit, for SPR)."""
+    from .evaltools.search_efficiency import _check_steps, probability_mismatch, target_hits
+    max_steps = _check_steps(max_steps)
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
+    box = _boxes_of(index, boxes)
+    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
+    res = target_hits(paths, box[key_of], max_steps=max_steps)
+    H, G = len(gt_keys), len(index)
+    means, per_key = _hit_tables("human_", {k: v[:H] for k, v in res.items()}, key_of[:H], G, max_steps)
+    per_key = dict({"keys": list(index)}, **per_key)
+    if predict_fix_vectors is not None:
+        m, p = _hit_tables("", {k: v[H:] for k, v in res.items()}, key_of[H:], G, max_steps)
+        means.update(m, PM=probability_mismatch(m["TFP"], means["human_TFP"]))
+        per_key.update(p, PM=np.abs(p["TFP"] - per_key["human_TFP"]).sum(1))
+    return means, per_key
+
+
+def search_efficiency_human_evaluation(gt_fix_vectors, gt_keys, boxes, *, max_steps, image_keys=None):
+    """The human row of search_efficiency_evaluation alone: "human_TFP", "human_TFP_AUC", "human_SPR" with their "_sum" / "_count"
+    entries; means["human_TFP"] is the human_curve of search_efficiency_model_evaluation and of SearchEfficiencyTable.result."""
+    return search_efficiency_evaluation(gt_fix_vectors, None, gt_keys, None, boxes, max_steps=max_steps, image_keys=image_keys)
+
+
+def search_efficiency_model_evaluation(predict, keys, boxes, *, min_length, max_steps, performances=None, human_curve=None,
+                                       frame_size=(240, 320), map_shape=None):
+    """The model's own target-fixation probability curve of ONE batch, exactly and without sampling
+    (evaltools.search_efficiency.target_hit_probability): predict is the model's eval-mode output on the device, keys[i] the key of sample
+    i, boxes: key -> (x_min, y_min, x_max, y_max) in the pixels of frame_size = (height, width); a key without a box raises ValueError.
+    With performances (AiR: performances[i][k] = subject k of sample i answered correctly) every subject is one entry, read against
+    predict["good_all_actions_prob"] when it answered correctly and ["poor_all_actions_prob"] otherwise, exactly as likelihood_evaluation
+    assigns the heads; without it every sample is one entry read against predict["all_actions_prob"].  min_length: the sampler's
+    (required; terminate is masked before it).  The curve is the mean over the entries of TFP[:, :max_steps] (a curve of T < max_steps
+    steps keeps its last value: the scanpath has ended); an entry whose curve holds a NaN (a step without mass) is left out and counted.
+    One launch and one copy back for the batch.
+    Returns (means, per_key): means["TFP"] float64 [max_steps], ["TFP_AUC"] its sum, ["PM"] = sum_k |TFP_k - human_curve_k| when
+    human_curve is given, ["TFP_sum"] / ["TFP_count"] the sum of the entries' curves and their number (what SearchEfficiencyTable
+    merges), ["TFP_nan"] the entries left out, ["empty_boxes"] the entries whose box holds no cell; per_key["TFP"] [G, max_steps], ["TFP_AUC"]
+    [G] in first-appearance order of keys (per_key["keys"])."""
+    from .evaltools.search_efficiency import _check_min_length, _check_steps, probability_mismatch, target_hit_probability, tfp_auc
+    max_steps, min_length = _check_steps(max_steps), _check_min_length(min_length)
+    keys = list(keys)
+    N = len(keys)
+    if performances is not None and len(performances) != N:
+        raise ValueError("one list of performances per sample is required")
+    if human_curve is not None:
+        human_curve = np.asarray(human_curve, dtype=np.float64).reshape(-1)
+        if len(human_curve) != max_steps:
+            raise ValueError(f"human_curve of {len(human_curve)} steps, max_steps {max_steps}")
+    import torch
+    names = ["all_actions_prob"] if performances is None else ["good_all_actions_prob", "poor_all_actions_prob"]
+    missing = [k for k in names if k not in predict]
+    if missing:
+        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
+                                                            else ""))
+    if any(predict[k].shape[0] != N for k in names):
+        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
+    index, _ = _key_index(keys, None)
+    box = _boxes_of(index, boxes)
+    rows, key_of = [], []
+    for i in range(N):
+        for good in ([None] if performances is None else performances[i]):
+            rows.append(i if performances is None or good == True else N + i)                      # noqa: E712  (as likelihood_evaluation)
+            key_of.append(index[keys[i]])
+    key_of = np.asarray(key_of, dtype=np.int64)
+    probs = predict[names[0]] if performances is None else torch.cat([predict[names[0]], predict[names[1]]], 0)
+    res = target_hit_probability(probs, box[key_of], rows, frame_size, min_length=min_length, map_shape=map_shape)
+    tfp = res["TFP"][:, :max_steps]
+    if tfp.shape[1] < max_steps:
+        tfp = np.concatenate([tfp, np.repeat(tfp[:, -1:], max_steps - tfp.shape[1], 1)], 1)
+    ok = ~np.isnan(tfp).any(1)
+    G = len(index)
+    ksum = np.stack([tfp[ok & (key_of == g)].sum(0) for g in range(G)]) if G else np.zeros((0, max_steps))
+    kcnt = np.bincount(key_of[ok], minlength=G)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        curves = np.where(kcnt[:, None] > 0, ksum / np.maximum(kcnt, 1)[:, None], np.nan)
+    per_key = {"keys": list(index), "TFP": curves, "TFP_AUC": curves.sum(1)}
+    total, count = tfp[ok].sum(0), int(ok.sum())
+    curve = total / count if count else np.full(max_steps, np.nan)
+    means = {"TFP": curve, "TFP_sum": total, "TFP_count": count, "TFP_nan": int((~ok).sum()), "TFP_AUC": tfp_auc(curve),
+             "empty_boxes": int((res["cells"] == 0).sum())}
+    if human_curve is not None:
+        means["PM"] = probability_mismatch(curve, human_curve)
+    return means, per_key
+
+
+class SearchEfficiencyTable:
+    """The pooled results of the search-efficiency calls over several batches, merged exactly where the numbers are counts: add(means)
+    sums every "_sum" (for a curve: its numerators, float64 [max_steps]), "_count" and "_nan" entry and "empty_boxes"; result() = the
+    means dict of all batches as one call on their union gives it -- every curve = its summed numerators / its summed count, "_AUC" of
+    every curve, "SPR", and "PM" between "TFP" and "human_TFP" (or the human_curve passed to result, for the model's exact curve).  The
+    hit curves of scanpaths merge exactly (integer numerators); sums of ratios and of probabilities merge to rounding."""
+
+    def __init__(self):
+        self.parts = {}
+
+    def add(self, means) -> None:
+        for k, v in means.items():
+            if k == "empty_boxes" or k.endswith(("_sum", "_count", "_nan")):
+                self.parts[k] = self.parts[k] + v if k in self.parts else (np.array(v, dtype=np.float64) if isinstance(v, np.ndarray) else v)
+
+    def result(self, human_curve=None) -> dict:
+        from .evaltools.search_efficiency import probability_mismatch, tfp_auc
+        out = dict(self.parts)
+        for k in self.parts:
+            if k.endswith("_count"):
+                m = k[:-len("_count")]
+                total, count = self.parts[m + "_sum"], self.parts[k]
+                if isinstance(total, np.ndarray):
+                    out[m] = total / count if count else np.full(total.shape, np.nan)
+                    out[m + "_AUC"] = tfp_auc(out[m])
+                else:
+                    out[m] = total / count if count else float("nan")
+        human = out.get("human_TFP") if human_curve is None else np.asarray(human_curve, dtype=np.float64).reshape(-1)
+        if human is not None and "TFP" in out:
+            out["PM"] = probability_mismatch(out["TFP"], human)
+        return out
