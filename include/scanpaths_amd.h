@@ -667,6 +667,39 @@ int sp_scan_target_hits(const double* fix, int ncol, const int64_t* start, const
                         int* hit, double* path, double* spr, void* stream);
 int sp_scan_target_mass(const float* probs, const double* box, const int* box_row, int R, int T, int Hm, int Wm, int NB, double frame_w,
                         double frame_h, int min_length, double* MASS, double* HIT, double* TFP, int* cells, void* stream);
+/* Saccade statistics (csrc/scansaccade.hip), float64, every operation rounded on its own.  A fixation is read as
+ * the action-map cell it falls in, a saccade is the cell displacement (dr, dc) of consecutive fixations, and both entry points fill the
+ * same displacement lattice of D = (2 Hm - 1) * (2 Wm - 1) entries: entry (dr + Hm - 1) * (2 Wm - 1) + (dc + Wm - 1).  Hm * Wm at most
+ * sp_scan_likelihood_max_cells().
+ * sp_scan_saccade_counts (one wavefront per scanpath; a zeroing launch and the counting launch): nscan scanpaths in the fixation layout
+ * of sp_scan_target_hits, group [nscan] in [0, ngroups).  Only the first min(n, max_steps) fixations count.  The cell of a fixation is
+ * that of sp_scan_likelihood: col = floor(x * Wm / frame_w), row = floor(y * Hm / frame_h) in double; a fixation outside the frame or
+ * with a non-finite coordinate is dropped and counted in dropped [nscan].  Saccade t counts iff fixations t and t + 1 are both kept
+ * (nothing bridges a dropped fixation): counts [ngroups][D] int64 gets 1 at its entry by an integer atomic add -- integers, so the
+ * order cannot matter -- and saccades [nscan] the number counted.  A scanpath with a count outside [0, sp_scan_max_fixations()] or a
+ * group outside [0, ngroups) gets saccades -1 and dropped 0; none of its rows is read and nothing is counted.  The launcher zeroes
+ * counts; every element of every output is written; all three outputs are required.  ncol >= 2, nscan, ngroups, max_steps >= 1,
+ * frame_w and frame_h > 0 and finite.
+ * sp_scan_saccade_expectation (one block per (row, 256 displacements), then one thread per (group, displacement): two launches): the
+ * expected number of saccades per displacement of the scanpaths the sampler draws from probs [R][T][1 + Hm * Wm] float32 (as
+ * sp_scan_target_mass reads it), in closed form: the step distributions are not conditioned on sampled fixations.  row_group [R] in
+ * [0, ngroups).  With Tm = min(T, max_steps), per row and step t < Tm, p0 = action 0:
+ *   Z_t = sum of the P cells (every lane adds cells lane, lane + 64, .. in that order from 0.0; the 64 partial sums combine by the xor
+ *   butterfly 32, 16, .., 1);  D_t = Z_t + p0 for t >= min_length, else Z_t;  q_t = p0 / D_t for t >= min_length, else 0;  c_t(i) =
+ *   (double)p_t[1 + i] / D_t;  A_0 = 1, A_{t+1} = A_t * (1 - q_t);
+ *   X_t[d] = sum of c_t(i) * c_{t+1}(i + d) over the cells i whose partner i + d is inside the map, in ascending row-major i from 0.0,
+ *   every product rounded before it is added;  E_r[d] = sum_{t = 0}^{Tm - 2} A_t * X_t[d], ascending t from 0.0;  saccades [R] =
+ *   sum_t A_t * ((1 - q_t) * (1 - q_{t+1})) in the same order;  E [ngroups][D] = the E_r of the group's good rows added in ascending row
+ *   index from 0.0 (no floating-point atomics).
+ * A row is bad iff some D_t, t < Tm, is zero or not finite: bad [R] = 1, saccades NaN, and it adds nothing to its group; steps t >= Tm
+ * are never read.  row_group outside [0, ngroups): bad -1, saccades NaN, nothing of the row is read.  Tm < 2: E and saccades are zero
+ * (a bad row stays bad).  work: scratch of R * D doubles (the rows' E_r), contents undefined afterwards.  All outputs and work are
+ * required; every element of E, saccades and bad is written.  R, T, ngroups, max_steps >= 1, min_length >= 0. */
+int sp_scan_saccade_counts(const double* fix, int ncol, const int64_t* start, const int* count, const int* group, int nscan, int ngroups,
+                           int max_steps, int Hm, int Wm, double frame_w, double frame_h, int64_t* counts, int* saccades, int* dropped,
+                           void* stream);
+int sp_scan_saccade_expectation(const float* probs, const int* row_group, int R, int T, int Hm, int Wm, int ngroups, int min_length,
+                                int max_steps, double* work, double* E, double* saccades, int* bad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -1,5 +1,6 @@
-// What the scanpath scorer kernels share (scanmetrics.hip, scandist.hip, seqscore.hip, scansimplify.hip, scanlik.hip) --
-// the device-side counterpart of utils/evaltools/_batch.py: the fixation limit, the float64 arithmetic rule, the prologue of a kernel
+// What the scanpath scorer kernels share (scanmetrics.hip, scandist.hip, seqscore.hip, scansimplify.hip, scanlik.hip, scansaccade.hip;
+// DESIGN.md §18a) -- the device-side counterpart of utils/evaltools/_batch.py: the fixation limit, the float64 arithmetic rule, the
+// pixel rule that turns a fixation into a map cell, the prologue of a kernel
 // that scores scanpaths or pairs of them in the layout rows [total][ncol] | start int64 [K] | count int32 [K] | pairs int32 [P][2],
 // with the guard against a count the kernel cannot hold, and the two wave reductions.  Include it after common.h.
 //
@@ -19,6 +20,13 @@ __device__ __forceinline__ bool scan_count_bad(int n) { return n < 0 || n > MAXF
 
 // the length of (dx, dy): three roundings and the correctly rounded root
 __device__ __forceinline__ double scan_dist(double dx, double dy) { return __builtin_sqrt(dx * dx + dy * dy); }
+
+// THE PIXEL RULE (sp_fixation_maps, sp_scan_likelihood, sp_scan_saccade_counts): a fixation counts iff both coordinates are finite and
+// inside the half-open frame; its cell along an axis of n cells over `frame` pixels is floor(v * n / frame), in double
+__device__ __forceinline__ bool scan_in_frame(double x, double y, double frame_w, double frame_h) {
+    return isfinite(x) && isfinite(y) && x >= 0.0 && x < frame_w && y >= 0.0 && y < frame_h;
+}
+__device__ __forceinline__ int scan_cell(double v, int n, double frame) { return min((int)floor((v * (double)n) / frame), n - 1); }
 
 // pair p of a launch: the two scanpath indices, their counts and their first rows (rows of ncol values of T; not to be read when bad())
 template <typename T>

@@ -112,9 +112,9 @@ __global__ __launch_bounds__(256) void scan_likelihood_kernel(const LikArgs a) {
                     dll = (-ld - 0.5 * log(2.0 * M_PI * s2) - e * e / (2.0 * s2)) / M_LN2;
                 }
             }
-            if (isfinite(x) && isfinite(y) && x >= 0.0 && x < a.frame_w && y >= 0.0 && y < a.frame_h) {
-                const int col = min((int)floor((x * (double)a.Wm) / a.frame_w), a.Wm - 1);
-                const int row = min((int)floor((y * (double)a.Hm) / a.frame_h), a.Hm - 1);
+            if (scan_in_frame(x, y, a.frame_w, a.frame_h)) {
+                const int col = scan_cell(x, a.Wm, a.frame_w);
+                const int row = scan_cell(y, a.Hm, a.frame_h);
                 const int c = row * a.Wm + col;
                 const float pc = p[1 + c];
                 if (a.AUC) {

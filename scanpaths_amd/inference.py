@@ -147,3 +147,37 @@ def run_search_efficiency_loop(model, loader: Iterable[dict], *, boxes, min_leng
         table.add(means)
         per_batch.append(per_key)
     return table.result(human_curve), per_batch
+
+
+@torch.no_grad()
+def run_saccade_statistics_loop(model, loader: Iterable[dict], *, min_length, max_steps, amplitude_edges, n_directions, human_lattice=None,
+                                ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None) -> Tuple[dict, List[dict]]:
+    """The model's own saccade statistics over a loader, exactly and without sampling
+    (utils.evaluation.saccade_statistics_model_evaluation): per batch ONE eval-mode forward, ONE sp_scan_saccade_expectation call and ONE
+    small device->host copy (the batch's lattice; the distributions stay on the device).  loader yields run_test_loop's batches; "tasks" is
+    passed to the model when the batch has it, "performances" is read when the model has the two AiR heads ("good_all_actions_prob" in
+    its output).  The key of a sample is its question id.  min_length is the sampler's; it, max_steps, amplitude_edges (pixels) and
+    n_directions have no defaults; human_lattice (optional, utils.evaluation.saccade_statistics_human_evaluation's
+    "human_lattice_sum"): for the four comparison numbers.  map_shape defaults to (30, 40) for 1201 actions only.
+    Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.SaccadeStatisticsTable."""
+    from .utils.evaltools.saccade_statistics import _check_directions, _check_edges
+    from .utils.evaluation import SaccadeStatisticsTable, saccade_statistics_model_evaluation
+    amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
+    model.eval()
+    table, per_batch = None, []
+    for batch in loader:
+        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
+        if ablate_attention_info:
+            attention_maps = attention_maps * 0
+        predict = model(images, attention_maps, batch["tasks"].cuda()) if "tasks" in batch else model(images, attention_maps)
+        means, per_key = saccade_statistics_model_evaluation(
+            predict, batch["question_ids"], min_length=min_length, max_steps=max_steps,
+            performances=batch["performances"] if "good_all_actions_prob" in predict else None, frame_size=frame_size, map_shape=map_shape)
+        if table is None:
+            LH, LW = means["lattice_sum"].shape
+            table = SaccadeStatisticsTable(frame_size, ((LH + 1) // 2, (LW + 1) // 2), amplitude_edges, n_directions)
+        table.add(means)
+        per_batch.append(per_key)
+    if table is None:
+        raise ValueError("the loader yielded no batch")
+    return table.result(human_lattice), per_batch

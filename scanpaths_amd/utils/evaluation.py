@@ -1071,3 +1071,225 @@ class SearchEfficiencyTable:
         if human is not None and "TFP" in out:
             out["PM"] = probability_mismatch(out["TFP"], human)
         return out
+
+
+# ---- saccade statistics (evaltools/saccade_statistics.py, csrc/scansaccade.hip) ------------------------------------------
+def _group_labels(index, groups):
+    """groups: key -> label (a task, ...) or None -> (labels in first-appearance order, label index of every key of the index); a key
+    without a label is an error, not a silent drop"""
+    if groups is None:
+        return [], np.zeros(len(index), dtype=np.int64)
+    missing = [k for k in index if k not in groups]
+    if missing:
+        raise ValueError(f"key {missing[0]!r} ({len(missing)} in all) has no group")
+    labels = {}
+    of_key = np.array([labels.setdefault(groups[k], len(labels)) for k in index], dtype=np.int64).reshape(-1)
+    return list(labels), of_key
+
+
+def _saccade_derived(parts, frame_size, amplitude_edges, n_directions, human_lattice=None):
+    """the summed entries of one group (the "_sum" / "_count" / "_bad" / "_dropped" entries) -> the same with "summary" /
+    "human_summary" and, against human_lattice (default: the group's own "human_lattice_sum"), the four comparison numbers"""
+    from .evaltools.saccade_statistics import saccade_comparison, saccade_summary
+    kw = dict(amplitude_edges=amplitude_edges, n_directions=n_directions)
+    out = dict(parts)
+    if "human_lattice_sum" in parts:
+        out["human_summary"] = saccade_summary(parts["human_lattice_sum"], frame_size, **kw)
+    if "lattice_sum" in parts:
+        out["summary"] = saccade_summary(parts["lattice_sum"], frame_size, **kw)
+        human = parts.get("human_lattice_sum") if human_lattice is None else human_lattice
+        if human is not None:
+            out.update(saccade_comparison(parts["lattice_sum"], human, frame_size, **kw))
+    return out
+
+
+def _human_of(human_lattice, label):
+    """the human lattice to compare a group against: human_lattice is None, one lattice (the pooled group's) or a dict label ->
+    lattice with the pooled group's under None"""
+    if isinstance(human_lattice, dict):
+        return human_lattice.get(label)
+    return human_lattice if label is None else None
+
+
+def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, frame_size, map_shape, max_steps,
+                                  amplitude_edges, n_directions, groups=None, image_keys=None):
+    """How the scanpaths move (Le Meur & Liu 2015; Tatler & Vincent 2009): the distribution of saccade amplitudes, of saccade
+    directions, their joint distribution on the displacement lattice of the action map and the share of saccades that stay in the same
+    cell, for predicted scanpaths and for the human ones, keyed as search_efficiency_evaluation keys them.  frame_size = (height, width)
+    of the fixations' frame, map_shape = (Hm, Wm), max_steps (only the first max_steps fixations of a scanpath count), amplitude_edges
+    (pixels) and n_directions have no defaults.  groups (optional): key -> label, e.g. a task; image_keys[i] (optional): the image of
+    gt_fix_vectors[i] (one key on two images raises ValueError).  Humans and predictions of all groups are counted in ONE launch
+    (evaltools.saccade_statistics.saccade_counts).
+    Returns (means, per_key).  means["human_lattice_sum"] / ["lattice_sum"] int64 [2 Hm - 1, 2 Wm - 1] (exact), ["human_saccades_sum"] /
+    ["saccades_sum"], ["human_scanpaths_count"] / ["scanpaths_count"], ["human_fixations_dropped"] / ["fixations_dropped"] -- what
+    SaccadeStatisticsTable merges -- ["human_summary"] / ["summary"] (evaltools.saccade_statistics.saccade_summary) and, against the
+    human side, ["JSD_lattice"], ["JSD_amplitude"], ["JSD_direction"] (bits) and ["W1_amplitude"] (pixels).  With groups,
+    means["by_group"][label] holds the same entries for the keys of that label.  per_key: "keys" and, per key in first-appearance order
+    of gt_keys, the number of saccades counted and of fixations dropped ("human_saccades", "human_dropped", "saccades", "dropped", int64
+    [G]) -- no lattice per key."""
+    from .evaltools.saccade_statistics import (_check_directions, _check_edges, _check_shape, saccade_counts)
+    from .evaltools.scanpath_likelihood import _check_frame
+    from .evaltools.search_efficiency import _check_steps
+    max_steps, (Hm, Wm), _ = _check_steps(max_steps), _check_shape(map_shape), _check_frame(frame_size)
+    amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
+    labels, label_of_key = _group_labels(index, groups)
+    NL = max(len(labels), 1)
+    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
+    H, G = len(gt_keys), len(index)
+    side = np.r_[np.zeros(H, dtype=np.int64), np.ones(len(predict_keys), dtype=np.int64)]
+    launch_group = side * NL + (label_of_key[key_of] if len(key_of) else key_of)
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
+    res = saccade_counts(paths, launch_group, 2 * NL, frame_size, (Hm, Wm), max_steps=max_steps)
+    sacc, drop = res["saccades"].astype(np.int64), res["dropped"].astype(np.int64)
+
+    def entries(label_index):
+        out = {}
+        for prefix, s in (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ()):
+            mine = side == s
+            if label_index is None:
+                lattice = res["counts"][s * NL:(s + 1) * NL].sum(0)
+            else:
+                lattice = res["counts"][s * NL + label_index]
+                mine = mine & (label_of_key[key_of] == label_index)
+            out.update({prefix + "lattice_sum": lattice, prefix + "saccades_sum": int(sacc[mine].sum()),
+                        prefix + "scanpaths_count": int(mine.sum()), prefix + "fixations_dropped": int(drop[mine].sum())})
+        return _saccade_derived(out, frame_size, amplitude_edges, n_directions)
+
+    means = entries(None)
+    if groups is not None:
+        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
+    per_key = {"keys": list(index)}
+    for prefix, s in (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ()):
+        mine = side == s
+        per_key[prefix + "saccades"] = np.bincount(key_of[mine], weights=sacc[mine], minlength=G).astype(np.int64)
+        per_key[prefix + "dropped"] = np.bincount(key_of[mine], weights=drop[mine], minlength=G).astype(np.int64)
+    return means, per_key
+
+
+def saccade_statistics_human_evaluation(gt_fix_vectors, gt_keys, *, frame_size, map_shape, max_steps, amplitude_edges, n_directions,
+                                        groups=None, image_keys=None):
+    """The human row of saccade_statistics_evaluation alone: the "human_" entries; means["human_lattice_sum"] is the human_lattice of
+    saccade_statistics_model_evaluation and of SaccadeStatisticsTable.result."""
+    return saccade_statistics_evaluation(gt_fix_vectors, None, gt_keys, None, frame_size=frame_size, map_shape=map_shape,
+                                         max_steps=max_steps, amplitude_edges=amplitude_edges, n_directions=n_directions, groups=groups,
+                                         image_keys=image_keys)
+
+
+def saccade_statistics_model_evaluation(predict, keys, *, min_length, max_steps, performances=None, frame_size=(240, 320), map_shape=None,
+                                        groups=None, human_lattice=None, amplitude_edges=None, n_directions=None):
+    """The model's own saccade statistics of ONE batch, exactly and without sampling
+    (evaltools.saccade_statistics.saccade_expectation): predict is the model's eval-mode output on the device, keys[i] the key of sample
+    i.  With performances (AiR: performances[i][k] = subject k of sample i answered correctly) every subject is one entry, read against
+    predict["good_all_actions_prob"] when it answered correctly and ["poor_all_actions_prob"] otherwise, exactly as
+    search_efficiency_model_evaluation assigns the heads; without it every sample is one entry read against
+    predict["all_actions_prob"].  min_length (the sampler's) and max_steps are required.  groups (optional): key -> label.  One
+    expectation call and one copy back for the batch; an entry whose row is bad (a step without mass) adds nothing and is counted.
+    Returns (means, per_key): means["lattice_sum"] float64 [2 Hm - 1, 2 Wm - 1] = the expected saccade counts summed over the entries,
+    ["saccades_sum"] its total as the kernel's closed form gives it, ["rows_count"] / ["rows_bad"] the entries that count / were bad --
+    what SaccadeStatisticsTable merges; with amplitude_edges and n_directions (the summary cannot be binned without them)
+    ["summary"] and, when human_lattice is given, ["JSD_lattice"], ["JSD_amplitude"], ["JSD_direction"], ["W1_amplitude"] against it;
+    with groups, means["by_group"][label] the same per label (human_lattice: one lattice for the pooled entries, or a dict label ->
+    lattice with the pooled one under None).  per_key: "keys" and "saccades" float64 [G], the expected number of saccades per entry of
+    the key (NaN for a key without a good entry)."""
+    from .evaltools.saccade_statistics import _check_directions, _check_edges, saccade_expectation
+    from .evaltools.scanpath_likelihood import _check_frame, _check_map
+    from .evaltools.search_efficiency import _check_min_length, _check_steps
+    max_steps, min_length = _check_steps(max_steps), _check_min_length(min_length)
+    _check_frame(frame_size)
+    if (amplitude_edges is None) != (n_directions is None):
+        raise ValueError("amplitude_edges and n_directions go together: the summary needs both")
+    if amplitude_edges is not None:
+        amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
+    elif human_lattice is not None:
+        raise ValueError("human_lattice is compared through the summary: amplitude_edges and n_directions are required with it")
+    keys = list(keys)
+    N = len(keys)
+    if performances is not None and len(performances) != N:
+        raise ValueError("one list of performances per sample is required")
+    import torch
+    names = ["all_actions_prob"] if performances is None else ["good_all_actions_prob", "poor_all_actions_prob"]
+    missing = [k for k in names if k not in predict]
+    if missing:
+        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
+                                                            else ""))
+    if any(predict[k].shape[0] != N for k in names):
+        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
+    _check_map(int(predict[names[0]].shape[-1]), map_shape)
+    index, _ = _key_index(keys, None)
+    labels, label_of_key = _group_labels(index, groups)
+    NL = max(len(labels), 1)
+    rows, key_of = [], []
+    for i in range(N):
+        for good in ([None] if performances is None else performances[i]):
+            rows.append(i if performances is None or good == True else N + i)                      # noqa: E712  (as likelihood_evaluation)
+            key_of.append(index[keys[i]])
+    key_of, G = np.asarray(key_of, dtype=np.int64), len(index)
+    if not len(rows):
+        raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
+    probs = predict[names[0]] if performances is None else torch.cat([predict[names[0]], predict[names[1]]], 0)
+    if performances is not None:                               # one row per entry: a head read by k subjects counts k times
+        probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
+    entry_label = label_of_key[key_of]
+    res = saccade_expectation(probs, entry_label, NL, min_length=min_length, max_steps=max_steps, map_shape=map_shape)
+    good = res["bad"] == 0
+
+    def entries(label_index):
+        mine = good if label_index is None else good & (entry_label == label_index)
+        lost = ~good if label_index is None else ~good & (entry_label == label_index)
+        if label_index is not None:
+            lattice = res["E"][label_index]
+        else:
+            lattice = res["E"][0].copy()
+            for g in range(1, NL):                              # ascending label: a fixed order
+                lattice = lattice + res["E"][g]
+        out = {"lattice_sum": lattice, "saccades_sum": float(res["saccades"][mine].sum()), "rows_count": int(mine.sum()),
+               "rows_bad": int(lost.sum())}
+        if amplitude_edges is None:
+            return out
+        label = None if label_index is None else labels[label_index]
+        return _saccade_derived(out, frame_size, amplitude_edges, n_directions, _human_of(human_lattice, label))
+
+    means = entries(None)
+    if groups is not None:
+        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
+    ksum = np.bincount(key_of[good], weights=res["saccades"][good], minlength=G)
+    kcnt = np.bincount(key_of[good], minlength=G)
+    per_key = {"keys": list(index), "saccades": np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan)}
+    return means, per_key
+
+
+class SaccadeStatisticsTable:
+    """The pooled results of the saccade-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
+    "_dropped" entry (also inside "by_group"); result(human_lattice=None) derives the summaries and the four comparison numbers from
+    the SUMMED lattices, as one call on the union of the batches gives them.  The comparison is against "human_lattice_sum" when the
+    table holds one, else against human_lattice (one lattice for the pooled entries, or a dict label -> lattice with the pooled one
+    under None).  Integer lattices (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums and
+    merge to rounding: the batches' lattices are added in the order of add, one call adds its rows in row order."""
+
+    def __init__(self, frame_size, map_shape, amplitude_edges, n_directions):
+        from .evaltools.saccade_statistics import _check_directions, _check_edges, _check_shape
+        from .evaltools.scanpath_likelihood import _check_frame
+        self.frame_size, self.map_shape = _check_frame(frame_size), _check_shape(map_shape)
+        self.amplitude_edges, self.n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
+        self.parts, self.by_group = {}, {}
+
+    def _merge(self, parts, means) -> None:
+        want = (2 * self.map_shape[0] - 1, 2 * self.map_shape[1] - 1)
+        for k, v in means.items():
+            if k.endswith(("_sum", "_count", "_bad", "_dropped")):
+                if isinstance(v, np.ndarray) and v.shape != want:
+                    raise ValueError(f"{k} of shape {v.shape}: the table's lattice is {want}")
+                parts[k] = parts[k] + v if k in parts else (v.copy() if isinstance(v, np.ndarray) else v)
+
+    def add(self, means) -> None:
+        self._merge(self.parts, means)
+        for label, m in means.get("by_group", {}).items():
+            self._merge(self.by_group.setdefault(label, {}), m)
+
+    def result(self, human_lattice=None) -> dict:
+        args = (self.frame_size, self.amplitude_edges, self.n_directions)
+        out = _saccade_derived(self.parts, *args, _human_of(human_lattice, None))
+        if self.by_group:
+            out["by_group"] = {label: _saccade_derived(p, *args, _human_of(human_lattice, label)) for label, p in self.by_group.items()}
+        return out
