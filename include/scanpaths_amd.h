@@ -700,6 +700,32 @@ int sp_scan_saccade_counts(const double* fix, int ncol, const int64_t* start, co
                            void* stream);
 int sp_scan_saccade_expectation(const float* probs, const int* row_group, int R, int T, int Hm, int Wm, int ngroups, int min_length,
                                 int max_steps, double* work, double* E, double* saccades, int* bad, void* stream);
+/* Cluster bootstrap of ratio-of-sums statistics (csrc/scanboot.hip), float64, every operation rounded on its own,
+ * every sum in a fixed order, no floating-point atomics.
+ * sp_boot_cluster_sums (one thread per (cluster, column)): num, den [G][M] with the keys sorted by cluster, ascending key index inside a
+ * cluster; cluster c owns rows start[c] .. start[c] + count[c] - 1.  N [C][M] and D [C][M] get the sums of its rows of num and den in
+ * that order from 0.0; a run outside [0, G) reads nothing and gives NaN.  G, M >= 1, 1 <= C <= 2^24.
+ * sp_boot_resample (one wavefront per replicate, one more for the point estimate): N, D as above with row stride ld >= M doubles (a
+ * launch may take M consecutive columns of a wider table), 1 <= M <= sp_boot_max_columns().  Draw j of replicate b is word j & 3 of the
+ * Philox4x32-10 block with key (seed lo, seed hi) and counter (b, j >> 2, 0, 1) -- the sampler's counter ends in 0 --, the drawn cluster
+ * (uint64(word) * C) >> 32; C draws per replicate.  Lane l adds the rows of draws l, l + 64, .. in that order from 0.0, the 64 partial
+ * sums of a column combine by the xor butterfly 32, 16, .., 1;  R[m] = sum N / sum D (IEEE: 0 / 0 = NaN);  contrast [S][4] = (i, j, k, l):
+ * stat [S][B] gets (R[i] - R[j]) / (R[k] - R[l]), where j = -1 subtracts nothing, k = -1 means no division and l = -1 subtracts nothing
+ * in the denominator; an index that is not a column of the launch gives NaN.  estimate [S]: the same contrasts with every cluster once,
+ * cluster c at position c of the same order.  Launches with one seed share their draws.  S, B >= 1.
+ * sp_boot_summarise (one block per statistic, then one thread per replicate): per statistic over its B replicates, valid = not NaN:
+ * n_valid, n_le0 (<= 0) and n_ge0 (>= 0) among the valid;  mean = the sum of the valid replicates (thread t of 256 adds t, t + 256, ..
+ * from 0.0, butterfly per wave, the four waves as ((w0 + w1) + w2) + w3) / n_valid, NaN without one;  sd = sqrt(the sum of
+ * (v - mean) * (v - mean) in the same order / (n_valid - 1)), NaN for n_valid < 2;  quant [S][Q]: for q[k] in [0, 1] the valid replicate
+ * of rank min(max(ceil(q[k] * n_valid) - 1, 0), n_valid - 1) in ascending order (ties by index; an order statistic, no interpolation,
+ * so +-inf stay exact), NaN without a valid replicate.  Q >= 0. */
+int sp_boot_max_columns(void);
+int sp_boot_cluster_sums(const double* num, const double* den, const int64_t* start, const int* count, int G, int C, int M, double* N,
+                         double* D, void* stream);
+int sp_boot_resample(const double* N, const double* D, int C, int M, int ld, const int* contrast, int S, int B, uint64_t seed,
+                     double* stat, double* estimate, void* stream);
+int sp_boot_summarise(const double* stat, int S, int B, const double* q, int Q, double* mean, double* sd, double* quant, int* n_valid,
+                      int* n_le0, int* n_ge0, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Post-hoc sampling (models/sampling.py:16-77), SURVEY.md §8 row f1.

@@ -15,25 +15,10 @@
 // pair -- reproducible for a given seed on any device count; the stream necessarily differs from torch's (the reference's CPU
 // and CUDA streams differ from each other too).
 #include "common.h"
+#include "philox.h"
 
 namespace {
 
-__device__ __forceinline__ void philox_round(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-    const uint32_t h0 = (uint32_t)(p0 >> 32), l0 = (uint32_t)p0, h1 = (uint32_t)(p1 >> 32), l1 = (uint32_t)p1;
-    c[0] = h1 ^ c[1] ^ k0;
-    c[1] = l1;
-    c[2] = h0 ^ c[3] ^ k1;
-    c[3] = l0;
-}
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        philox_round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 // (0,1).  From x >> 8 = 2^23 on the "+ 0.5f" is a tie of float32 and rounds to even; for x >> 8 = 2^24 - 1 that is 2^24, i.e. 1.0f:
 // the min keeps that one value (256 of the 2^32 words) at the largest float below 1, every other word keeps its value
 __device__ __forceinline__ float u01(uint32_t x) { return fminf(((float)(x >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f); }

@@ -1293,3 +1293,125 @@ class SaccadeStatisticsTable:
         if self.by_group:
             out["by_group"] = {label: _saccade_derived(p, *args, _human_of(human_lattice, label)) for label, p in self.by_group.items()}
         return out
+
+
+# ---- bootstrap intervals and paired comparisons for every keyed table (evaltools/bootstrap.py, csrc/scanboot.hip) ----------
+def _score_names(per_key) -> list:
+    """every float64 [G] entry of a per_key table (of the first one of a sequence)"""
+    t = per_key if isinstance(per_key, dict) else list(per_key)[0]
+    G = len(t["keys"])
+    return [k for k, v in t.items() if k != "keys" and isinstance(v, np.ndarray) and v.dtype == np.float64 and v.shape == (G,)]
+
+
+def _level_quantiles(level) -> Tuple[float, float]:
+    """the two tail probabilities of a central interval, rounded to 12 decimals so that level = 0.95 gives 0.025 and not the
+    0.025000000000000022 of (1 - 0.95) / 2, which would move the order statistic by one whenever 0.025 * n_valid is an integer"""
+    if isinstance(level, bool) or not isinstance(level, (int, float)) or not 0.0 < level < 1.0:
+        raise ValueError(f"level {level!r}: a number inside (0, 1) is required")
+    lo = float(np.round((1.0 - level) / 2.0, 12))
+    return lo, float(np.round(1.0 - lo, 12))
+
+
+def _match_rows(keys_a, keys_b) -> np.ndarray:
+    """the row of the second table for every row of the first: the t-th row of a key pairs with the t-th row of that key; a key (or an
+    occurrence of it) that one table lacks raises ValueError naming it"""
+    rows, seen, out = {}, {}, []
+    for r, k in enumerate(keys_b):
+        rows.setdefault(k, []).append(r)
+    for k in keys_a:
+        t = seen.get(k, 0)
+        seen[k] = t + 1
+        if t >= len(rows.get(k, ())):
+            raise ValueError(f"key {k!r} of the first table is missing in the second: the two tables must hold the same keys")
+        out.append(rows[k][t])
+    extra = [k for k in rows if len(rows[k]) != seen.get(k, 0)]
+    if extra:
+        raise ValueError(f"key {extra[0]!r} of the second table is missing in the first: the two tables must hold the same keys")
+    return np.array(out, dtype=np.int64)
+
+
+def _interval(res, s) -> dict:
+    return {"estimate": float(res["estimate"][s]), "se": float(res["se"][s]), "lo": float(res["quantiles"][s, 0]),
+            "hi": float(res["quantiles"][s, 1]), "n_valid": int(res["n_valid"][s])}
+
+
+def bootstrap_evaluation(per_key, *, names=None, cluster_keys=None, replicates, seed, level=0.95) -> dict:
+    """Standard error and percentile interval of the mean over keys of a keyed evaluation's per_key table (or a sequence of them from
+    several batches), by a cluster bootstrap on the device (evaltools.bootstrap.bootstrap_ratio).  names: the entries to
+    bootstrap (default: every float64 [G] entry); cluster_keys: the image of every key -- a list aligned with per_key["keys"] or a
+    mapping key -> image; the resampling unit is the image, because several keys of one image (AiR's questions, any dataset's
+    subjects) are not independent draws.  None: every key is its own cluster.  replicates and seed have no defaults; level: the
+    coverage of the central percentile interval.
+    Returns {name: {"estimate", "se", "lo", "hi", "n_valid"}}: "estimate" is the nanmean over keys exactly as the family's own
+    means[name] computes it (on the host, by the same expression, so the two are equal to the bit; the kernel's own point estimate adds
+    in another order and may differ in the last place); "se" the standard deviation of the valid replicates; "lo" / "hi" their order
+    statistics at (1 - level) / 2 and 1 - (1 - level) / 2; "n_valid" how many replicates were not NaN.
+    THE LIKELIHOOD FAMILY'S means[name] is pooled over fixations, not a mean over keys: this function gives the interval of the mean
+    over keys of per_key[name]; for the pooled mean call bootstrap_ratio with num = the key's sum and den = the key's count."""
+    from .evaltools.bootstrap import bootstrap_ratio, key_clusters, table_columns
+    names = _score_names(per_key) if names is None else list(names)
+    if not names:
+        raise ValueError("no entry to bootstrap: names is empty")
+    q = _level_quantiles(level)
+    num, den, keys = table_columns(per_key, names)
+    res = bootstrap_ratio(num, den, key_clusters(keys, cluster_keys), None, replicates=replicates, seed=seed, quantiles=q)
+    out = {}
+    for s, name in enumerate(names):
+        out[name] = _interval(res, s)
+        out[name]["estimate"] = _nanmean(np.where(den[:, s] > 0, num[:, s], np.nan))
+    return out
+
+
+def bootstrap_comparison(per_key_a, per_key_b, *, names=None, cluster_keys=None, replicates, seed, level=0.95) -> dict:
+    """Paired comparison of two models scored on the same keys: the tables (or sequences of tables) are matched by key -- differing key
+    sets raise ValueError naming a missing key -- and every replicate resamples the same images for both, so the between-image
+    variance cancels in the difference.  A key that is NaN in either table is left out of both for that name: the difference is paired
+    on the common keys.  cluster_keys (a list aligned with per_key_a["keys"] or a mapping), replicates, seed, level: bootstrap_evaluation.
+    Returns {name: {"a", "b", "difference" (a - b on the common keys, the kernel's point estimates), "se", "lo", "hi" (of the
+    difference), "p", "n_valid"}}; "p" = min(1, 2 (min(n_le0, n_ge0) + 1) / (n_valid + 1)): the two-sided bootstrap p-value of "no
+    difference", from the integer counts of replicates <= 0 and >= 0."""
+    from .evaltools.bootstrap import bootstrap_ratio, key_clusters, table_columns
+    names = [n for n in _score_names(per_key_a) if n in _score_names(per_key_b)] if names is None else list(names)
+    if not names:
+        raise ValueError("no entry to compare: names is empty")
+    q = _level_quantiles(level)
+    na, da, keys = table_columns(per_key_a, names)
+    nb, db, keys_b = table_columns(per_key_b, names)
+    rows = _match_rows(keys, keys_b)
+    both = (da > 0) & (db[rows] > 0)
+    n = len(names)
+    num, den = np.zeros((len(keys), 2 * n)), np.zeros((len(keys), 2 * n))
+    num[:, 0::2], num[:, 1::2] = np.where(both, na, 0.0), np.where(both, nb[rows], 0.0)
+    den[:, 0::2] = den[:, 1::2] = both
+    con = [c for s in range(n) for c in ((2 * s, -1, -1, -1), (2 * s + 1, -1, -1, -1), (2 * s, 2 * s + 1, -1, -1))]
+    res = bootstrap_ratio(num, den, key_clusters(keys, cluster_keys), con, replicates=replicates, seed=seed, quantiles=q)
+    out = {}
+    for s, name in enumerate(names):
+        d = _interval(res, 3 * s + 2)
+        tail = min(int(res["n_le0"][3 * s + 2]), int(res["n_ge0"][3 * s + 2]))
+        out[name] = {"a": float(res["estimate"][3 * s]), "b": float(res["estimate"][3 * s + 1]), "difference": d["estimate"],
+                     "se": d["se"], "lo": d["lo"], "hi": d["hi"], "p": min(1.0, 2.0 * (tail + 1) / (d["n_valid"] + 1)),
+                     "n_valid": d["n_valid"]}
+    return out
+
+
+def bootstrap_information_gain_explained(per_key, gold_per_key, *, cluster_keys=None, replicates, seed, level=0.95) -> dict:
+    """The interval of information_gain_explained on key means: per_key holds "LL" and "IG" of likelihood_evaluation, gold_per_key
+    "GOLD" of likelihood_gold_standard_evaluation (matched by key; the same table when one holds all three).  BASE = LL - IG is built
+    per key on the host, so that it stays a linear column, and IGE = IG / (GOLD - BASE) is ONE contrast of the three column means: its
+    replicates are ratios of differences on the same resampled images.  A key that is NaN in any of the three (a -inf in both LL and
+    IG makes BASE NaN) is left out of all of them.  Returns {"IGE", "IG_gold", "BASE"}, each {"estimate", "se", "lo", "hi", "n_valid"}
+    (the kernel's point estimates: means over keys, where information_gain_explained on pooled means weighs fixations)."""
+    from .evaltools.bootstrap import bootstrap_ratio, key_clusters, table_columns
+    q = _level_quantiles(level)
+    nm, dm, keys = table_columns(per_key, ["LL", "IG"])
+    ng, dg, keys_g = table_columns(gold_per_key, ["GOLD"])
+    rows = _match_rows(keys, keys_g)
+    with np.errstate(invalid="ignore"):
+        value = np.stack([nm[:, 1], ng[rows, 0], nm[:, 0] - nm[:, 1]], 1)                  # IG, GOLD, BASE
+    ok = (dm[:, 0] > 0) & (dm[:, 1] > 0) & (dg[rows, 0] > 0) & ~np.isnan(value).any(1)
+    num = np.where(ok[:, None], value, 0.0)
+    den = np.repeat(ok[:, None].astype(np.float64), 3, 1)
+    con = [(0, -1, 1, 2), (1, 2, -1, -1), (2, -1, -1, -1)]
+    res = bootstrap_ratio(num, den, key_clusters(keys, cluster_keys), con, replicates=replicates, seed=seed, quantiles=q)
+    return {name: _interval(res, s) for s, name in enumerate(("IGE", "IG_gold", "BASE"))}
