@@ -1699,7 +1699,14 @@ def _lstm_rank1_backward(gates, c_prev, c, spcol, wc, dh, dc, need_dsp, need_dwc
         return dpre, dcp, dsp, dwc
     if need_dsp:        # dsp[b] = dpre[b][:, :3C] x wc[b]: a batched pointwise GEMM with one weight set per sample
         dsp = torch.empty_like(spcol)
-        _igemm(_gemm_desc(P, KP, N3, ldx=C4, ldw=KP, ldc=KP, mode=1, nbatch=B, sX=P * C4, sW=N3 * KP, sC=P * KP), dpre, wc, None, dsp)
+        KQ = (KP + 3) // 4 * 4          # the GEMM takes rows of whole float4 (KP = 9, one stream unpadded): zero taps behind wc's, cut off again
+        wq, dq = wc, dsp
+        if KQ != KP:
+            wq, dq = torch.empty(B, N3, KQ, dtype=wc.dtype, device=wc.device), torch.empty(B, P, KQ, dtype=wc.dtype, device=wc.device)
+            check(L.sp_pad_lastdim(ptr(wc), B * N3, KP, KQ, ptr(wq), hip.stream()), "sp_pad_lastdim")
+        _igemm(_gemm_desc(P, KQ, N3, ldx=C4, ldw=KQ, ldc=KQ, mode=1, nbatch=B, sX=P * C4, sW=N3 * KQ, sC=P * KQ), dpre, wq, None, dq)
+        if KQ != KP:
+            check(L.sp_pad_lastdim(ptr(dq), B * P, KQ, KP, ptr(dsp), hip.stream()), "sp_pad_lastdim")
     if need_dwc:        # dwc[b] = dpre[b][:, :3C]^T x spcol[b]: one TN GEMM per sample (K = the sample's pixels)
         dwc = torch.empty_like(wc)
         if KP <= 24:
