@@ -39,21 +39,33 @@ def to_fix_vectors(fix_h: np.ndarray, n_h: np.ndarray) -> List[np.ndarray]:
     return out
 
 
+def _forward_batches(model, loader, ablate_attention_info: bool, with_tasks: bool):
+    """what every loop below does per batch: images and attention maps to the device, the maps zeroed for the ablation, ONE eval-mode
+    forward -- with batch["tasks"] (the COCO-Search18 signature) when with_tasks and the batch has them -- -> (batch, predict)"""
+    model.eval()
+    for batch in loader:
+        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
+        if ablate_attention_info:
+            attention_maps = attention_maps * 0
+        tasks = (batch["tasks"].cuda(),) if with_tasks and "tasks" in batch else ()
+        yield batch, model(images, attention_maps, *tasks)
+
+
+def _performances(batch, predict):
+    """the batch's performances when the model has the two AiR heads, else None"""
+    return batch["performances"] if "good_all_actions_prob" in predict else None
+
+
 @torch.no_grad()
 def run_test_loop(model, sampling, loader: Iterable[dict], repeat_num: int = 10, ablate_attention_info: bool = False,
                   multimatch=None) -> Tuple[dict, dict, list, list]:
     """loader yields the reference's evaluation batches: images, fix_vectors, performances, attention_maps, question_ids,
     img_names (AiR/test.py:119-123).  Returns (cur_metrics, cur_metrics_std, scores_of_each_images, predict_results)."""
     from .utils.evaluation import evaluation_performance_related
-    model.eval()
     all_gt, all_pred, all_perf, all_alloc, predict_results = [], [], [], [], []
-    for batch in loader:
-        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=False):
         gt_fix_vectors, performances = batch["fix_vectors"], batch["performances"]
-        N = images.shape[0]
-        if ablate_attention_info:
-            attention_maps = attention_maps * 0
-        predict = model(images, attention_maps)
+        N = batch["images"].shape[0]
         fix, nfix = sample_batch(predict, sampling, repeat_num)
         fix_h, n_h = fix.cpu().numpy().astype(np.float64), nfix.cpu().numpy()          # the batch's single device->host copy
         for trial in range(repeat_num):
@@ -102,15 +114,9 @@ def run_likelihood_gold_loop(model, loader: Iterable[dict], *, gold_standard, un
 def _likelihood_loop(model, loader, gold_standard, *, uniform_mix, metrics, min_length, baseline, ablate_attention_info, frame_size,
                      map_shape):
     from .utils.evaluation import LikelihoodTable, likelihood_evaluation, likelihood_gold_standard_evaluation
-    model.eval()
     table, per_batch = LikelihoodTable(), []
-    for batch in loader:
-        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
-        if ablate_attention_info:
-            attention_maps = attention_maps * 0
-        predict = model(images, attention_maps)
-        means, per_key = likelihood_evaluation(predict, batch["fix_vectors"], batch["question_ids"],
-                                               batch["performances"] if "good_all_actions_prob" in predict else None,
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=False):
+        means, per_key = likelihood_evaluation(predict, batch["fix_vectors"], batch["question_ids"], _performances(batch, predict),
                                                batch.get("baseline_rows"), baseline, uniform_mix=uniform_mix, metrics=metrics,
                                                min_length=min_length, frame_size=frame_size, map_shape=map_shape)
         table.add(means)
@@ -134,16 +140,11 @@ def run_search_efficiency_loop(model, loader: Iterable[dict], *, boxes, min_leng
     pixels of frame_size.  min_length is the sampler's and has no default; human_curve (optional, [max_steps]): for "PM".
     Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.SearchEfficiencyTable."""
     from .utils.evaluation import SearchEfficiencyTable, search_efficiency_model_evaluation
-    model.eval()
     table, per_batch = SearchEfficiencyTable(), []
-    for batch in loader:
-        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
-        if ablate_attention_info:
-            attention_maps = attention_maps * 0
-        predict = model(images, attention_maps, batch["tasks"].cuda()) if "tasks" in batch else model(images, attention_maps)
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
         means, per_key = search_efficiency_model_evaluation(
             predict, batch["question_ids"], boxes, min_length=min_length, max_steps=max_steps,
-            performances=batch["performances"] if "good_all_actions_prob" in predict else None, frame_size=frame_size, map_shape=map_shape)
+            performances=_performances(batch, predict), frame_size=frame_size, map_shape=map_shape)
         table.add(means)
         per_batch.append(per_key)
     return table.result(human_curve), per_batch
@@ -163,16 +164,11 @@ def run_saccade_statistics_loop(model, loader: Iterable[dict], *, min_length, ma
     from .utils.evaltools.saccade_statistics import _check_directions, _check_edges
     from .utils.evaluation import SaccadeStatisticsTable, saccade_statistics_model_evaluation
     amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
-    model.eval()
     table, per_batch = None, []
-    for batch in loader:
-        images, attention_maps = batch["images"].cuda(), batch["attention_maps"].cuda()
-        if ablate_attention_info:
-            attention_maps = attention_maps * 0
-        predict = model(images, attention_maps, batch["tasks"].cuda()) if "tasks" in batch else model(images, attention_maps)
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
         means, per_key = saccade_statistics_model_evaluation(
             predict, batch["question_ids"], min_length=min_length, max_steps=max_steps,
-            performances=batch["performances"] if "good_all_actions_prob" in predict else None, frame_size=frame_size, map_shape=map_shape)
+            performances=_performances(batch, predict), frame_size=frame_size, map_shape=map_shape)
         if table is None:
             LH, LW = means["lattice_sum"].shape
             table = SaccadeStatisticsTable(frame_size, ((LH + 1) // 2, (LW + 1) // 2), amplitude_edges, n_directions)

@@ -39,10 +39,9 @@ import torch
 from ... import hip
 from ...hip import check, ptr
 from . import _batch
+from ._args import check_frame, check_map, check_min_length, check_steps, rows
 from ._batch import MAX_FIXATIONS, check_index, pack  # noqa: F401  (MAX_FIXATIONS re-exported)
-from .saliency_maps import _rows
-from .scanpath_likelihood import MAX_CELLS, _check_frame, _check_map
-from .search_efficiency import _check_min_length, _check_steps
+from .scanpath_likelihood import MAX_CELLS
 
 
 def _device() -> torch.device:
@@ -99,10 +98,10 @@ def saccade_counts(scanpaths, groups, n_groups, frame_size, map_shape, *, max_st
     """scanpaths: S arrays [n <= 64, >= 2] of (x, y, ...) or structured fixation vectors; groups [S] in [0, n_groups): the lattice each
     scanpath is counted into (an empty group stays zero); frame_size = (height, width); map_shape = (Hm, Wm), at most 2048 cells.
     Returns {"counts": int64 [n_groups, 2 Hm - 1, 2 Wm - 1], "saccades": int32 [S], "dropped": int32 [S]} (module docstring)."""
-    max_steps = _check_steps(max_steps)
+    max_steps = check_steps(max_steps)
     Hm, Wm = _check_shape(map_shape)
-    fh, fw = _check_frame(frame_size)
-    b = pack([_rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
+    fh, fw = check_frame(frame_size)
+    b = pack([rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
     S = len(b.counts)
     grp, G = _check_groups(groups, S, n_groups, "scanpath")
     LH, LW = 2 * Hm - 1, 2 * Wm - 1
@@ -124,11 +123,11 @@ def saccade_expectation(probs, row_groups, n_groups, *, min_length, max_steps, m
     each row is added into, in ascending row index; min_length: the sampler's (required); max_steps: only the first max_steps steps
     count (required); map_shape = (Hm, Wm) defaults to (30, 40) for 1201 actions only.
     Returns {"E": float64 [n_groups, 2 Hm - 1, 2 Wm - 1], "saccades": float64 [R], "bad": int32 [R]} (module docstring)."""
-    min_length, max_steps = _check_min_length(min_length), _check_steps(max_steps)
+    min_length, max_steps = check_min_length(min_length), check_steps(max_steps)
     if not isinstance(probs, torch.Tensor) or probs.dim() != 3 or min(probs.shape) < 1:
         raise ValueError("probs: a non-empty [R, T, A] tensor is required")
     R, T, A = (int(v) for v in probs.shape)
-    Hm, Wm = _check_map(A, map_shape)
+    Hm, Wm = check_map(A, map_shape, max_cells=MAX_CELLS)
     grp, G = _check_groups(row_groups, R, n_groups, "row")
     LH, LW = 2 * Hm - 1, 2 * Wm - 1
     dev = _device()
@@ -150,7 +149,7 @@ def lattice_vectors(map_shape, frame_size) -> Tuple[np.ndarray, np.ndarray, np.n
     """(dx, dy, amplitude), each float64 [2 Hm - 1, 2 Wm - 1]: the pixel displacement of every lattice entry, dx = dc * frame_w / Wm and
     dy = dr * frame_h / Hm (y pointing down, as stored), and its length sqrt(dx * dx + dy * dy)"""
     Hm, Wm = _check_shape(map_shape)
-    fh, fw = _check_frame(frame_size)
+    fh, fw = check_frame(frame_size)
     dy = np.arange(-(Hm - 1), Hm, dtype=np.float64) * fh / Hm
     dx = np.arange(-(Wm - 1), Wm, dtype=np.float64) * fw / Wm
     dx, dy = np.broadcast_to(dx[None, :], (2 * Hm - 1, 2 * Wm - 1)).copy(), np.broadcast_to(dy[:, None], (2 * Hm - 1, 2 * Wm - 1)).copy()
@@ -180,7 +179,7 @@ def saccade_summary(lattice, frame_size, *, amplitude_edges, n_directions) -> di
     Shares of an empty lattice (and direction shares of a stay-only one) are NaN."""
     edges, n = _check_edges(amplitude_edges), _check_directions(n_directions)
     a, Hm, Wm = _check_lattice(lattice)
-    fh, fw = _check_frame(frame_size)
+    fh, fw = check_frame(frame_size)
     _, _, amp = lattice_vectors((Hm, Wm), (fh, fw))
     total = float(a.sum())
     flat, ampf = a.reshape(-1), amp.reshape(-1)

@@ -19,31 +19,15 @@ import torch
 from ... import hip
 from ...hip import check, ptr
 from . import _batch
+from ._args import rows as _rows
 
 WEIGHTS = {"binary": 0, "count": 1, "duration": 2}
 MODES = {"constant": 0, "reflect": 1, "nearest": 2}
 NORMALISE = {None: 0, "sum": 1, "max": 2}
-_FIELDS = ("start_x", "start_y", "duration")
 
 
 def _device() -> torch.device:
     return _batch.device("fixation / density maps run")
-
-
-def _rows(sp) -> np.ndarray:
-    """one scanpath -> float64 [n, ncol]: a structured fixation vector (start_x, start_y, duration) or an [n, >= 2] array"""
-    a = np.asarray(sp)
-    if a.dtype.names is not None:
-        if any(f not in a.dtype.names for f in _FIELDS[:2]):
-            raise ValueError(f"structured scanpath without start_x / start_y fields: {a.dtype.names}")
-        cols = [f for f in _FIELDS if f in a.dtype.names]
-        return np.stack([np.asarray(a[f], dtype=np.float64).reshape(-1) for f in cols], 1)
-    a = a.astype(np.float64)
-    if a.size == 0:
-        return np.zeros((0, a.shape[-1] if a.ndim == 2 and a.shape[-1] >= 2 else 0))
-    if a.ndim != 2 or a.shape[1] < 2:
-        raise ValueError(f"a scanpath is an [n, >= 2] array of (x, y[, duration]) rows, got shape {a.shape}")
-    return a
 
 
 class _Upload:

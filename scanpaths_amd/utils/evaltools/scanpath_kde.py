@@ -35,9 +35,9 @@ import torch
 from ... import hip
 from ...hip import check
 from . import _batch
+from ._args import check_frame, rows
 from ._batch import starts
-from .saliency_maps import _rows
-from .scanpath_likelihood import MAX_CELLS, _check_frame
+from .scanpath_likelihood import MAX_CELLS
 
 LEAVE = ("image", "scanpath", "scanpath_step")
 MAX_BANDWIDTHS = 16         # = sp_scan_kde_max_bandwidths(), known here so that a refusal needs no library (held equal by the tests)
@@ -80,7 +80,7 @@ class _Points:
     def __init__(self, scanpaths, image_groups, max_length, dense: bool):
         if max_length is not None and (isinstance(max_length, bool) or int(max_length) != max_length or int(max_length) < 1):
             raise ValueError(f"max_length {max_length!r}: None or an integer >= 1")
-        arrs = [_rows(sp)[:max_length] for sp in scanpaths]
+        arrs = [rows(sp)[:max_length] for sp in scanpaths]
         groups = _batch.check_index(list(image_groups), np.iinfo(np.int32).max, "image group").reshape(-1)
         if len(groups) != len(arrs):
             raise ValueError("one image group per scanpath is required")
@@ -154,7 +154,7 @@ def _leave_out(scanpaths, image_groups, frame_size, map_shape, bandwidths, unifo
     u = _check_mix(uniform_mix)
     if leave not in LEAVE:
         raise ValueError(f"leave {leave!r}: one of {LEAVE}")
-    shape, frame = _check_shape(map_shape), _check_frame(frame_size)
+    shape, frame = _check_shape(map_shape), check_frame(frame_size)
     p = _Points(scanpaths, image_groups, max_length, dense=True)
     if p.N == 0:                                                                     # nothing to score: no device
         return p, np.zeros((0, len(bw))), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.int32)
@@ -173,7 +173,7 @@ def kde_cell_baselines(scanpaths, image_groups, frame_size, map_shape, *, bandwi
     bw = _check_bandwidths([bandwidth] if np.ndim(bandwidth) == 0 else bandwidth)
     if len(bw) != 1:
         raise ValueError("kde_cell_baselines takes one bandwidth")
-    shape, frame = _check_shape(map_shape), _check_frame(frame_size)
+    shape, frame = _check_shape(map_shape), check_frame(frame_size)
     p = _Points(scanpaths, image_groups, max_length, dense=False)
     if p.G == 0:                                                                     # no scanpath, no image, no row
         return torch.zeros((0, shape[0] * shape[1]), dtype=torch.float64, device=_device())

@@ -37,8 +37,8 @@ import torch
 from ... import hip
 from ...hip import check, ptr
 from . import _batch
+from ._args import check_frame, check_map, rows as _rows  # (rows is an argument of scanpath_likelihood)
 from ._batch import MAX_FIXATIONS, check_index, pack, starts  # noqa: F401  (MAX_FIXATIONS re-exported)
-from .saliency_maps import _rows
 
 METRICS = ("LL", "IG", "NSS", "AUC", "DLL", "STOP")
 MAX_CELLS = 2048            # = sp_scan_likelihood_max_cells(), known here so that a refusal needs no library (held equal by the tests)
@@ -73,26 +73,6 @@ def _check_args(metrics, uniform_mix, min_length) -> Tuple[Tuple[str, ...], floa
     return metrics, u, int(min_length)
 
 
-def _check_map(A: int, map_shape) -> Tuple[int, int]:
-    if map_shape is None:
-        if A != 1201:
-            raise ValueError(f"map_shape is required for {A} actions (only 1201 = 1 + 30 * 40 has a default)")
-        map_shape = (30, 40)
-    Hm, Wm = (int(v) for v in map_shape)
-    if Hm < 1 or Wm < 1 or Hm * Wm != A - 1:
-        raise ValueError(f"map_shape {tuple(map_shape)} does not hold the {A - 1} cells of {A} actions")
-    if Hm * Wm > MAX_CELLS:
-        raise ValueError(f"map of {Hm * Wm} cells exceeds the kernel limit {MAX_CELLS}")
-    return Hm, Wm
-
-
-def _check_frame(frame_size) -> Tuple[float, float]:
-    fh, fw = (float(v) for v in frame_size)
-    if not (np.isfinite(fh) and np.isfinite(fw) and fh > 0 and fw > 0):
-        raise ValueError(f"frame_size {tuple(frame_size)}: positive finite sizes are required")
-    return fh, fw
-
-
 def _stop(cont: np.ndarray, term: np.ndarray, row: np.ndarray, n: np.ndarray, min_length: int) -> np.ndarray:
     """STOP of every scanpath from CONT / TERM [R, T]; the sums run left to right in index order (np.cumsum accumulates that way)"""
     R, T = cont.shape
@@ -120,9 +100,9 @@ def scanpath_likelihood(probs, scanpaths, rows, frame_size, *, uniform_mix=None,
     if not isinstance(probs, torch.Tensor) or probs.dim() != 3 or min(probs.shape) < 1:
         raise ValueError("probs: a non-empty [R, T, A] tensor is required")
     R, T, A = (int(v) for v in probs.shape)
-    Hm, Wm = _check_map(A, map_shape)
+    Hm, Wm = check_map(A, map_shape, max_cells=MAX_CELLS)
     P = Hm * Wm
-    fh, fw = _check_frame(frame_size)
+    fh, fw = check_frame(frame_size)
     want_ig, want_dll, want_stop = "IG" in metrics, "DLL" in metrics, "STOP" in metrics
     if want_ig and (baseline is None or baseline_rows is None):
         raise TypeError("IG needs the keywords baseline ([NB, P]) and baseline_rows (one row index per scanpath)")

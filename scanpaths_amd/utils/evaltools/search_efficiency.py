@@ -28,7 +28,7 @@ probability_mismatch are pure numpy: TFP-AUC is the plain sum of the cumulative 
 differences, as the papers describe them."""
 from __future__ import annotations
 
-from typing import Dict, Tuple
+from typing import Dict
 
 import numpy as np
 import torch
@@ -36,9 +36,8 @@ import torch
 from ... import hip
 from ...hip import check, ptr
 from . import _batch
+from ._args import check_frame, check_map, check_min_length, check_steps, rows
 from ._batch import MAX_FIXATIONS, check_index, pack  # noqa: F401  (MAX_FIXATIONS re-exported)
-from .saliency_maps import _rows
-from .scanpath_likelihood import _check_frame
 
 MAX_SIDE = 1024             # Hm, Wm at most this (the launcher's refusal, known here so that it needs no library)
 
@@ -48,18 +47,6 @@ def _device() -> torch.device:
 
 
 # ---- argument checks: every refusal comes before the device or the library is touched ---------------------------------------------------
-def _check_steps(max_steps) -> int:
-    if max_steps is None or isinstance(max_steps, bool) or int(max_steps) != max_steps or int(max_steps) < 1:
-        raise ValueError(f"max_steps {max_steps!r}: an integer >= 1")
-    return int(max_steps)
-
-
-def _check_min_length(min_length) -> int:
-    if min_length is None or isinstance(min_length, bool) or int(min_length) != min_length or int(min_length) < 0:
-        raise ValueError(f"min_length {min_length!r}: an integer >= 0 (the sampler's)")
-    return int(min_length)
-
-
 def _check_boxes(boxes, n=None) -> np.ndarray:
     box = np.asarray(boxes, dtype=np.float64)
     if box.size == 0:
@@ -73,26 +60,12 @@ def _check_boxes(boxes, n=None) -> np.ndarray:
     return np.ascontiguousarray(box)
 
 
-def _check_map(A: int, map_shape) -> Tuple[int, int]:
-    """scanpath_likelihood._check_map without the cell limit"""
-    if map_shape is None:
-        if A != 1201:
-            raise ValueError(f"map_shape is required for {A} actions (only 1201 = 1 + 30 * 40 has a default)")
-        map_shape = (30, 40)
-    Hm, Wm = (int(v) for v in map_shape)
-    if Hm < 1 or Wm < 1 or Hm * Wm != A - 1:
-        raise ValueError(f"map_shape {tuple(map_shape)} does not hold the {A - 1} cells of {A} actions")
-    if Hm > MAX_SIDE or Wm > MAX_SIDE:
-        raise ValueError(f"map_shape {tuple(map_shape)}: a side exceeds the kernel limit {MAX_SIDE}")
-    return Hm, Wm
-
-
 # ---- device calls -------------------------------------------------------------------------------------------------------------------------
 def target_hits(scanpaths, boxes, *, max_steps) -> Dict[str, np.ndarray]:
     """scanpaths: S arrays [n <= 64, >= 2] of (x, y, ...) or structured fixation vectors; boxes [S, 4], one per scanpath, finite.
     Returns {"hit": int32 [S], "path", "SPR": float64 [S], "n": int32 [S] = min(n, max_steps)} (module docstring)."""
-    max_steps = _check_steps(max_steps)
-    b = pack([_rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
+    max_steps = check_steps(max_steps)
+    b = pack([rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
     S = len(b.counts)
     box = _check_boxes(boxes, S)
     n = np.minimum(b.counts, max_steps).astype(np.int32)
@@ -113,12 +86,12 @@ def target_hit_probability(probs, boxes, box_rows, frame_size, *, min_length, ma
     """probs: device tensor [R, T, 1 + P] (any float dtype; detached and read as float32); boxes [NB, 4] in the frame frame_size =
     (height, width), finite; box_rows[b]: the row of probs box b is read against; min_length: the sampler's (required); map_shape =
     (Hm, Wm) defaults to (30, 40) for 1201 actions only.  Returns {"MASS", "HIT", "TFP": float64 [NB, T], "cells": int32 [NB]}."""
-    min_length = _check_min_length(min_length)
+    min_length = check_min_length(min_length)
     if not isinstance(probs, torch.Tensor) or probs.dim() != 3 or min(probs.shape) < 1:
         raise ValueError("probs: a non-empty [R, T, A] tensor is required")
     R, T, A = (int(v) for v in probs.shape)
-    Hm, Wm = _check_map(A, map_shape)
-    fh, fw = _check_frame(frame_size)
+    Hm, Wm = check_map(A, map_shape, max_side=MAX_SIDE)
+    fh, fw = check_frame(frame_size)
     box = _check_boxes(boxes)
     NB = len(box)
     row = check_index(box_rows, R, "box row").reshape(-1)
@@ -141,7 +114,7 @@ def target_hit_probability(probs, boxes, box_rows, frame_size, *, min_length, ma
 # ---- pure numpy ---------------------------------------------------------------------------------------------------------------------------
 def search_curve(hit, max_steps) -> np.ndarray:
     """float64 [max_steps]: the share of scanpaths with 0 <= hit <= k, for k = 0 .. max_steps - 1 (NaN without scanpaths)"""
-    max_steps = _check_steps(max_steps)
+    max_steps = check_steps(max_steps)
     hit = np.asarray(hit, dtype=np.int64).reshape(-1)
     if not len(hit):
         return np.full(max_steps, np.nan)

@@ -1,22 +1,32 @@
-"""ScanMatch reward glue of the RL (self-critical) phase with the reference's interface (utils/evaluation.py:361-576),
-SURVEY.md §8 row f3.  The reference scores every (ground-truth scanpath, other scanpath) pair with two pure-python
-Needleman-Wunsch runs inside nested loops; here the pairs of a whole batch are collected first and scored by ONE batched
-device call per ScanMatch object (csrc/scanmatch.hip: one wavefront per pair), then grouped exactly as the reference does
-(mean over the non-NaN rows of a group, NaN for an empty group, accept_flag False when NaN elimination empties a group).
+"""Evaluation on the host: what is scored, for whom, and how the scores of a call are grouped; the scoring itself runs on the device
+(utils/evaltools/, one batched call per measure).  A map of this file:
 
-    same, diff, accept = pairs_eval_scanmatch_performance_related(gt_fix_vectors, predict_fix_vectors, sm_wd, sm_wod,
-                                                                   performance, given_performance)
-    good, poor, good_vs_poor = gtpairs_eval_scanmatch_performance_related(gt_fix_vectors, sm_wd, sm_wod, performance)
+  Reference-interface half (the functions of the reference's utils/evaluation.py, its arguments, result layouts and quirks; SURVEY.md §8
+  rows f1-f3): pairs_eval_scanmatch_performance_related / gtpairs_eval_scanmatch_performance_related -- the ScanMatch reward of the RL
+  (self-critical) phase --, evaluation_performance_related / human_evaluation* / evaluation / pairs_eval -- the validation and test
+  tables --, pairs_eval_scanmatch.  The reference scores every (ground-truth, other) scanpath pair inside nested python loops; here the pairs of a
+  whole call are collected first, scored by one device call per measure (csrc/scanmatch.hip: one wavefront per pair) and grouped exactly
+  as the reference groups them.  Fixation vectors are the reference's structured arrays (start_x, start_y, duration in seconds) or
+  plain [n, 3] arrays; durations become milliseconds as in the reference.  Any object with the reference's ScanMatch methods works; one that also offers
+  sequences / match_pairs (the HIP ScanMatch) is driven in batched form.
 
-Fixation vectors are the reference's structured arrays (start_x, start_y, duration in seconds) or plain [n, 3] arrays;
-durations are converted to milliseconds as in the reference.  Result columns: [0] without duration, [1] with duration.
-Any object with the reference's ScanMatch methods works; objects that also offer ``sequences`` / ``match_pairs`` (the HIP
-ScanMatch) are driven in batched form."""
+  Keyed half (from predict_results_fix_vectors down): measures the reference's tables do not hold.  Every call takes scanpaths with a key
+  each (a question id, an image name) and returns (means, per_key), per_key in first-appearance order of the keys.  _keyed / _key_index
+  check the keys; _model_pairs / _ceiling_pairs / _pair_tables serve the pair measures (saliency_*, scanpath_distance_*,
+  sequence_score_*); the model-side calls that read the model's distributions instead of samples (likelihood_*, search_efficiency_model_*,
+  saccade_statistics_model_*) get their entries from _head_entries; _pool is the mean per key with its pooled sum and count, _key_means
+  the mean over keys.
+
+  Tables: LikelihoodTable, SearchEfficiencyTable, SaccadeStatisticsTable merge the means of several batches (_SumTable holds the merge).
+
+  Bootstrap: bootstrap_evaluation / bootstrap_comparison / bootstrap_information_gain_explained put intervals on any per_key table."""
 from __future__ import annotations
 
 from typing import List, Sequence, Tuple
 
 import numpy as np
+
+from .evaltools._args import check_frame, check_map, check_min_length, check_steps
 
 
 def _as_ms(fv) -> np.ndarray:
@@ -553,14 +563,35 @@ def _ceiling_pairs(index, gt_keys):
     return pairs, owner
 
 
-def _saliency_means(per_key, metrics):
+def _nanmean(v) -> Tuple[float, int]:
+    """(the mean over the values that are not NaN, NaN without one; how many are NaN)"""
+    nan = np.isnan(v)
+    return float(v[~nan].mean()) if (~nan).any() else float("nan"), int(nan.sum())
+
+
+def _key_means(per_key, names):
+    """the means of a keyed call: means[name] = the mean over the keys that did not score NaN, means[name + "_nan"] = how many did"""
     means = {}
-    for m in metrics:
-        v = per_key[m]
-        nan = np.isnan(v)
-        means[m] = float(v[~nan].mean()) if (~nan).any() else float("nan")
-        means[m + "_nan"] = int(nan.sum())
+    for m in names:
+        means[m], means[m + "_nan"] = _nanmean(per_key[m])
     return means
+
+
+def _pool(values, owner, G):
+    """values float64 [n], or curves [n, K], of owner[n] in [0, G) -> (per_key, total, count, n_nan): the mean per owner over its values
+    that are not NaN (a curve: that hold no NaN; NaN for an owner without one), their sum over all owners, their number, and how many
+    were left out"""
+    flat = values.ndim == 1
+    ok = ~np.isnan(values) if flat else ~np.isnan(values).any(1)
+    cnt = np.bincount(owner[ok], minlength=G)
+    if flat:
+        ksum, total = np.bincount(owner[ok], weights=values[ok], minlength=G), float(values[ok].sum())
+    else:
+        ksum = np.stack([values[ok & (owner == g)].sum(0) for g in range(G)]) if G else np.zeros((0, values.shape[1]))
+        cnt, total = cnt[:, None], values[ok].sum(0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_key = np.where(cnt > 0, ksum / np.maximum(cnt, 1), np.nan)
+    return per_key, total, int(ok.sum()), int((~ok).sum())
 
 
 def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, frame_size=(240, 320), *, sigma, extra_metrics=(),
@@ -583,7 +614,7 @@ def saliency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_ke
                             frame_size, sigma, num_groups=len(index), **kw)
     per_key = {"keys": list(index)}
     per_key.update({k: v.cpu().numpy() for k, v in res.items()})
-    return _saliency_means(per_key, ("AUC_Judd", "NSS", "KLdiv") + tuple(extra_metrics)), per_key
+    return _key_means(per_key, ("AUC_Judd", "NSS", "KLdiv") + tuple(extra_metrics)), per_key
 
 
 def saliency_centre_prior_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *, sigma, extra_metrics=(), image_keys=None, **kw):
@@ -630,7 +661,7 @@ def saliency_human_evaluation(gt_fix_vectors, gt_keys, frame_size=(240, 320), *,
             v = folds[m][mem]
             if not np.isnan(v).all():
                 per_key[m][q] = np.nanmean(v)
-    return _saliency_means(per_key, metrics), per_key
+    return _key_means(per_key, metrics), per_key
 
 
 # ---- DTW, Frechet, Hausdorff, Eyenalysis and cross-recurrence of sampled scanpaths (evaltools/visual_attention_metrics.py, -------------
@@ -644,11 +675,6 @@ def _xy(fv) -> np.ndarray:
         return np.asarray(fv[:, :2], dtype=np.float64)
     a = np.array([list(_) for _ in list(fv)], dtype=np.float64)
     return a.reshape(len(a), -1)[:, :2] if len(a) else np.zeros((0, 2))
-
-
-def _nanmean(v) -> float:
-    v = v[~np.isnan(v)]
-    return float(v.mean()) if v.size else float("nan")
 
 
 def _distance_tables(index, paths, pairs, owner, metrics, max_dim, radius, min_line):
@@ -674,14 +700,14 @@ def _pair_tables(index, scores, owner, metrics, lower_is_better, higher_is_bette
     names = []
     for m in metrics:
         v = scores[m]
-        per_key[m] = np.array([_nanmean(v[ps]) for ps in pairs_of_key], dtype=np.float64)
+        per_key[m] = np.array([_nanmean(v[ps])[0] for ps in pairs_of_key], dtype=np.float64)
         names.append(m)
         if m in lower_is_better or m in higher_is_better:
             # the best over each prediction's human scanpaths (fmin / fmax skip NaN; all NaN stays NaN), then the mean over the key's predictions
             best = (np.fmin if m in lower_is_better else np.fmax).reduceat(v, seg) if len(seg) else np.zeros(0)
-            per_key[m + "_best"] = np.array([_nanmean(best[ps]) for ps in preds_of_key], dtype=np.float64)
+            per_key[m + "_best"] = np.array([_nanmean(best[ps])[0] for ps in preds_of_key], dtype=np.float64)
             names.append(m + "_best")
-    return _saliency_means(per_key, names), per_key
+    return _key_means(per_key, names), per_key
 
 
 def scanpath_distance_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, metrics, max_dim=1.0, radius=None,
@@ -762,6 +788,68 @@ def sequence_score_human_evaluation(gt_fix_vectors, gt_keys, *, bandwidth, metri
     return _pair_tables(index, scores, owner, metrics, ("FED",), ("SS",))
 
 
+# ---- what the model-side calls share: the entries of a batch, and the sum tables that merge batches ------------------------------------
+def _head_entries(predict, keys, performances, per_sample=None, outputs=("all_actions_prob",)):
+    """The entries of a model-side call on ONE batch and the rows of the model's output they are read against.  Sample i has
+    per_sample[i] entries (default: one per subject of performances[i], one without performances), all under the key keys[i].  Without performances every entry of sample i reads row i of the unprefixed
+    outputs; with them entry k of sample i reads row i of the "good_" outputs when performances[i][k] is True and row N + i -- the "poor_"
+    outputs stacked behind the good ones -- otherwise, as training assigns the heads.  Refuses a predict that lacks one of the outputs
+    or does not hold N samples.  Returns (index of _key_index, rows, key_of int64 [entries], the shape of the first output, both);
+    both(name) = the output the rows point into: predict[name], or the two heads' stacked."""
+    import torch
+    N = len(keys)
+    names = [h + k for h in (("",) if performances is None else ("good_", "poor_")) for k in outputs]
+    missing = [k for k in names if k not in predict]
+    if missing:
+        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
+                                                            else ""))
+    if any(predict[k].shape[0] != N for k in names):
+        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
+    index, _ = _key_index(keys, None)
+    rows, key_of = [], []
+    for i, n in enumerate(per_sample if per_sample is not None else [1] * N if performances is None else map(len, performances)):
+        for k in range(n):
+            rows.append(i if performances is None or performances[i][k] == True else N + i)           # noqa: E712  (as the reference)
+            key_of.append(index[keys[i]])
+
+    def both(name):
+        return predict[name] if performances is None else torch.cat([predict["good_" + name], predict["poor_" + name]], 0)
+
+    return index, rows, np.asarray(key_of, dtype=np.int64), tuple(predict[names[0]].shape), both
+
+
+class _SumTable:
+    """What the three tables share.  add(means) sums the entries whose name is in _also or ends in one of _suffixes into parts -- and
+    those of means["by_group"][label] into by_group[label]; the first array of a name is copied (as _dtype, where a table sets one), so
+    that the caller's is never written to, and where the table has a shape an array of another one is refused.  _divided() = parts with
+    every name that has a "_count" as its "_sum" / "_count" (NaN for a count of 0)."""
+    _suffixes, _also, _dtype, _shape = (), (), None, None
+
+    def __init__(self):
+        self.parts, self.by_group = {}, {}
+
+    def _merge(self, parts, means) -> None:
+        for k, v in means.items():
+            if k in self._also or k.endswith(self._suffixes):
+                if self._shape is not None and isinstance(v, np.ndarray) and v.shape != self._shape:
+                    raise ValueError(f"{k} of shape {v.shape}: the table's lattice is {self._shape}")
+                parts[k] = parts[k] + v if k in parts else (np.array(v, dtype=self._dtype) if isinstance(v, np.ndarray) else v)
+
+    def add(self, means) -> None:
+        self._merge(self.parts, means)
+        for label, m in means.get("by_group", {}).items():
+            self._merge(self.by_group.setdefault(label, {}), m)
+
+    def _divided(self) -> dict:
+        out = dict(self.parts)
+        for k in self.parts:
+            if k.endswith("_count"):
+                total, count = self.parts[k[:-len("_count")] + "_sum"], self.parts[k]
+                nan = np.full(total.shape, np.nan) if isinstance(total, np.ndarray) else float("nan")
+                out[k[:-len("_count")]] = total / count if count else nan
+        return out
+
+
 # ---- human scanpaths under the model's own step distributions (evaltools/scanpath_likelihood.py, csrc/scanlik.hip; DESIGN.md §19) ------
 def likelihood_evaluation(predict, fix_vectors, keys, performances=None, image_keys=None, baseline=None, *, uniform_mix,
                           metrics=("LL", "NSS", "AUC"), min_length=0, frame_size=(240, 320), map_shape=None):
@@ -794,47 +882,32 @@ def likelihood_evaluation(predict, fix_vectors, keys, performances=None, image_k
         if len(baseline) != 1:
             raise ValueError(f"image_keys is required to choose among the {len(baseline)} baseline rows")
         image_keys = [0] * N
-    import torch
-    heads = ("",) if performances is None else ("good_", "poor_")
-    names = [h + k for h in heads for k in ("all_actions_prob",) + (("log_normal_mu", "log_normal_sigma2") if "DLL" in metrics else ())]
-    missing = [k for k in names if k not in predict]
-    if missing:
-        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
-                                                            else ""))
-    if any(predict[k].shape[0] != N for k in names):
-        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
-    index, _ = _key_index(keys, None)
-    paths, rows, brows, key_of = [], [], [], []
-    for i, subjects in enumerate(fix_vectors):
-        for k, fv in enumerate(subjects):
-            paths.append(fv)
-            rows.append(i if performances is None or performances[i][k] == True else N + i)           # noqa: E712  (as the reference)
-            key_of.append(index[keys[i]])
-            if image_keys is not None:
-                brows.append(image_keys[i])
-
-    def both(name):
-        return predict[name] if performances is None else torch.cat([predict["good_" + name], predict["poor_" + name]], 0)
-
     dll = "DLL" in metrics
+    subjects = [len(s) for s in fix_vectors]
+    index, rows, key_of, (_, T, _), both = _head_entries(predict, keys, performances, subjects, ("all_actions_prob",) + (
+        ("log_normal_mu", "log_normal_sigma2") if dll else ()))
+    paths = [fv for s in fix_vectors for fv in s]
+    brows = [] if image_keys is None else [image_keys[i] for i, n in enumerate(subjects) for _ in range(n)]
     res = scanpath_likelihood(both("all_actions_prob"), paths, rows, frame_size, uniform_mix=uniform_mix, metrics=metrics,
                               map_shape=map_shape, baseline=baseline, baseline_rows=brows if "IG" in metrics else None,
                               log_normal_mu=both("log_normal_mu") if dll else None,
                               log_normal_sigma2=both("log_normal_sigma2") if dll else None, min_length=min_length)
-    G, key_of = len(index), np.asarray(key_of, dtype=np.int64)
-    T = predict[names[0]].shape[1]
     met = np.arange(T)[None, :] < res["n"][:, None]                          # [S, T]: fixation t met a step
+    fixation_key = np.broadcast_to(key_of[:, None], met.shape)[met]
+    return _likelihood_tables(index, key_of, res["dropped"], [(m, res[m], key_of) if m == "STOP" else (m, res[m][met], fixation_key)
+                                                              for m in metrics])
+
+
+def _likelihood_tables(index, key_of, dropped, scored):
+    """scored: (metric, its values, the key of every value); dropped: per scanpath, key_of its key -> (means, per_key) of the
+    likelihood calls: per_key[m] and the pooled means[m] with the entries LikelihoodTable merges"""
     per_key, means = {"keys": list(index)}, {}
-    for m in metrics:
-        v, owner = (res[m], key_of) if m == "STOP" else (res[m][met], np.broadcast_to(key_of[:, None], met.shape)[met])
-        ok = ~np.isnan(v)
-        ksum, kcnt = np.bincount(owner[ok], weights=v[ok], minlength=G), np.bincount(owner[ok], minlength=G)
-        per_key[m] = np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan)
-        total, count = float(v[ok].sum()), int(ok.sum())
-        means.update({m: total / count if count else float("nan"), m + "_sum": total, m + "_count": count,
-                      m + "_nan": int((~ok).sum()), m + "_nan_keys": int(np.isnan(per_key[m]).sum())})
-    per_key["dropped"] = np.bincount(key_of, weights=res["dropped"], minlength=G).astype(np.int64)
-    means["dropped"] = int(res["dropped"].sum())
+    for m, v, owner in scored:
+        per_key[m], total, count, n_nan = _pool(v, owner, len(index))
+        means.update({m: total / count if count else float("nan"), m + "_sum": total, m + "_count": count, m + "_nan": n_nan,
+                      m + "_nan_keys": int(np.isnan(per_key[m]).sum())})
+    per_key["dropped"] = np.bincount(key_of, weights=dropped, minlength=len(index)).astype(np.int64)
+    means["dropped"] = int(dropped.sum())
     return means, per_key
 
 
@@ -859,17 +932,9 @@ def likelihood_gold_standard_evaluation(fix_vectors, keys, *, bandwidth, uniform
     sample = np.repeat(np.arange(len(keys), dtype=np.int64), [len(subjects) for subjects in fix_vectors])
     res = kde_leave_out_likelihood(paths, sample, frame_size, map_shape, bandwidth=bandwidth, uniform_mix=uniform_mix,
                                    leave="scanpath_step" if same_step else "scanpath", max_length=max_length)
-    G, key_of = len(index), np.array([index[keys[i]] for i in sample], dtype=np.int64)
+    key_of = np.array([index[keys[i]] for i in sample], dtype=np.int64)
     met = np.arange(res["LL"].shape[1])[None, :] < res["n"][:, None]             # [S, Tmax]: a fixation that counts
-    v, owner = res["LL"][met], np.broadcast_to(key_of[:, None], met.shape)[met]
-    ok = ~np.isnan(v)
-    ksum, kcnt = np.bincount(owner[ok], weights=v[ok], minlength=G), np.bincount(owner[ok], minlength=G)
-    per_key = {"keys": list(index), "GOLD": np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan),
-               "dropped": np.bincount(key_of, weights=res["dropped"], minlength=G).astype(np.int64)}
-    total, count = float(v[ok].sum()), int(ok.sum())
-    means = {"GOLD": total / count if count else float("nan"), "GOLD_sum": total, "GOLD_count": count, "GOLD_nan": int((~ok).sum()),
-             "GOLD_nan_keys": int(np.isnan(per_key["GOLD"]).sum()), "dropped": int(res["dropped"].sum())}
-    return means, per_key
+    return _likelihood_tables(index, key_of, res["dropped"], [("GOLD", res["LL"][met], np.broadcast_to(key_of[:, None], met.shape)[met])])
 
 
 def information_gain_explained(means, gold_means) -> dict:
@@ -886,26 +951,14 @@ def information_gain_explained(means, gold_means) -> dict:
             "IG_count": int(means.get("IG_count", 0)), "GOLD_count": int(gold_means.get("GOLD_count", 0))}
 
 
-class LikelihoodTable:
+class LikelihoodTable(_SumTable):
     """The pooled means of likelihood_evaluation over several batches, merged exactly: add(means) sums every metric's "_sum",
     "_count", "_nan" and "_nan_keys" entry and "dropped"; result() = the means dict of all batches as one call would give it (a key
     that appears in two batches counts in each for "_nan_keys")."""
-
-    def __init__(self):
-        self.parts = {}
-
-    def add(self, means) -> None:
-        for k, v in means.items():
-            if k == "dropped" or k.endswith(("_sum", "_count", "_nan", "_nan_keys")):
-                self.parts[k] = self.parts.get(k, 0) + v
+    _suffixes, _also = ("_sum", "_count", "_nan", "_nan_keys"), ("dropped",)
 
     def result(self) -> dict:
-        out = dict(self.parts)
-        for k in self.parts:
-            if k.endswith("_count"):
-                m = k[:-len("_count")]
-                out[m] = self.parts[m + "_sum"] / self.parts[k] if self.parts[k] else float("nan")
-        return out
+        return self._divided()
 
 
 # ---- target-search efficiency (evaltools/search_efficiency.py, csrc/scansearch.hip; DESIGN.md §21) --------------------------------------
@@ -922,22 +975,16 @@ def _hit_tables(prefix, res, key_of, G, max_steps):
     """target_hits' result of a set of scanpaths with their keys -> (means, per_key) entries under prefix: the hit curve pooled over the
     scanpaths (numerators "_sum" float64 [max_steps] -- integers, hence exact -- over "_count"), its area, and the mean scanpath ratio
     over the scanpaths that hit"""
-    from .evaltools.search_efficiency import hit_counts, tfp_auc
+    from .evaltools.search_efficiency import tfp_auc
     key_of = np.asarray(key_of, dtype=np.int64)
-    hit, spr = res["hit"], res["SPR"]
-    num = np.stack([hit_counts(hit[key_of == g], max_steps) for g in range(G)]) if G else np.zeros((0, max_steps))
-    cnt = np.bincount(key_of, minlength=G)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        curves = np.where(cnt[:, None] > 0, num / np.maximum(cnt, 1)[:, None], np.nan)
-    ok = ~np.isnan(spr)
-    ssum, scnt = np.bincount(key_of[ok], weights=spr[ok], minlength=G), np.bincount(key_of[ok], minlength=G)
-    per_key = {prefix + "TFP": curves, prefix + "TFP_AUC": curves.sum(1), prefix + "SPR": np.where(scnt > 0, ssum / np.maximum(scnt, 1), np.nan)}
-    total, S = hit_counts(hit, max_steps), int(len(hit))
+    hit = res["hit"].astype(np.int64)[:, None]
+    reached = ((hit >= 0) & (hit <= np.arange(max_steps)[None, :])).astype(np.float64)       # [S, max_steps]: hit within k + 1 fixations
+    curves, total, S, _ = _pool(reached, key_of, G)
+    spr, ssum, nspr, _ = _pool(res["SPR"], key_of, G)
+    per_key = {prefix + "TFP": curves, prefix + "TFP_AUC": curves.sum(1), prefix + "SPR": spr}
     curve = total / S if S else np.full(max_steps, np.nan)
-    nspr = int(ok.sum())
     means = {prefix + "TFP": curve, prefix + "TFP_sum": total, prefix + "TFP_count": S, prefix + "TFP_AUC": tfp_auc(curve),
-             prefix + "SPR": float(spr[ok].sum()) / nspr if nspr else float("nan"), prefix + "SPR_sum": float(spr[ok].sum()),
-             prefix + "SPR_count": nspr}
+             prefix + "SPR": ssum / nspr if nspr else float("nan"), prefix + "SPR_sum": ssum, prefix + "SPR_count": nspr}
     return means, per_key
 
 
@@ -955,8 +1002,8 @@ def search_efficiency_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, p
     numerator (for a curve: float64 [max_steps] of integer counts) and the number of scanpaths behind each mean.  per_key: "keys" and
     the same names per key in first-appearance order of gt_keys -- curves [G, max_steps], the rest [G]; NaN where a key has no scanpath
     (no hit, for SPR)."""
-    from .evaltools.search_efficiency import _check_steps, probability_mismatch, target_hits
-    max_steps = _check_steps(max_steps)
+    from .evaltools.search_efficiency import probability_mismatch, target_hits
+    max_steps = check_steps(max_steps)
     gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
     box = _boxes_of(index, boxes)
     key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
@@ -993,8 +1040,8 @@ def search_efficiency_model_evaluation(predict, keys, boxes, *, min_length, max_
     human_curve is given, ["TFP_sum"] / ["TFP_count"] the sum of the entries' curves and their number (what SearchEfficiencyTable
     merges), ["TFP_nan"] the entries left out, ["empty_boxes"] the entries whose box holds no cell; per_key["TFP"] [G, max_steps], ["TFP_AUC"]
     [G] in first-appearance order of keys (per_key["keys"])."""
-    from .evaltools.search_efficiency import _check_min_length, _check_steps, probability_mismatch, target_hit_probability, tfp_auc
-    max_steps, min_length = _check_steps(max_steps), _check_min_length(min_length)
+    from .evaltools.search_efficiency import probability_mismatch, target_hit_probability, tfp_auc
+    max_steps, min_length = check_steps(max_steps), check_min_length(min_length)
     keys = list(keys)
     N = len(keys)
     if performances is not None and len(performances) != N:
@@ -1003,70 +1050,35 @@ def search_efficiency_model_evaluation(predict, keys, boxes, *, min_length, max_
         human_curve = np.asarray(human_curve, dtype=np.float64).reshape(-1)
         if len(human_curve) != max_steps:
             raise ValueError(f"human_curve of {len(human_curve)} steps, max_steps {max_steps}")
-    import torch
-    names = ["all_actions_prob"] if performances is None else ["good_all_actions_prob", "poor_all_actions_prob"]
-    missing = [k for k in names if k not in predict]
-    if missing:
-        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
-                                                            else ""))
-    if any(predict[k].shape[0] != N for k in names):
-        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
-    index, _ = _key_index(keys, None)
+    index, rows, key_of, _, both = _head_entries(predict, keys, performances)
     box = _boxes_of(index, boxes)
-    rows, key_of = [], []
-    for i in range(N):
-        for good in ([None] if performances is None else performances[i]):
-            rows.append(i if performances is None or good == True else N + i)                      # noqa: E712  (as likelihood_evaluation)
-            key_of.append(index[keys[i]])
-    key_of = np.asarray(key_of, dtype=np.int64)
-    probs = predict[names[0]] if performances is None else torch.cat([predict[names[0]], predict[names[1]]], 0)
-    res = target_hit_probability(probs, box[key_of], rows, frame_size, min_length=min_length, map_shape=map_shape)
+    res = target_hit_probability(both("all_actions_prob"), box[key_of], rows, frame_size, min_length=min_length, map_shape=map_shape)
     tfp = res["TFP"][:, :max_steps]
     if tfp.shape[1] < max_steps:
         tfp = np.concatenate([tfp, np.repeat(tfp[:, -1:], max_steps - tfp.shape[1], 1)], 1)
-    ok = ~np.isnan(tfp).any(1)
-    G = len(index)
-    ksum = np.stack([tfp[ok & (key_of == g)].sum(0) for g in range(G)]) if G else np.zeros((0, max_steps))
-    kcnt = np.bincount(key_of[ok], minlength=G)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        curves = np.where(kcnt[:, None] > 0, ksum / np.maximum(kcnt, 1)[:, None], np.nan)
+    curves, total, count, n_nan = _pool(tfp, key_of, len(index))
     per_key = {"keys": list(index), "TFP": curves, "TFP_AUC": curves.sum(1)}
-    total, count = tfp[ok].sum(0), int(ok.sum())
     curve = total / count if count else np.full(max_steps, np.nan)
-    means = {"TFP": curve, "TFP_sum": total, "TFP_count": count, "TFP_nan": int((~ok).sum()), "TFP_AUC": tfp_auc(curve),
+    means = {"TFP": curve, "TFP_sum": total, "TFP_count": count, "TFP_nan": n_nan, "TFP_AUC": tfp_auc(curve),
              "empty_boxes": int((res["cells"] == 0).sum())}
     if human_curve is not None:
         means["PM"] = probability_mismatch(curve, human_curve)
     return means, per_key
 
 
-class SearchEfficiencyTable:
+class SearchEfficiencyTable(_SumTable):
     """The pooled results of the search-efficiency calls over several batches, merged exactly where the numbers are counts: add(means)
     sums every "_sum" (for a curve: its numerators, float64 [max_steps]), "_count" and "_nan" entry and "empty_boxes"; result() = the
     means dict of all batches as one call on their union gives it -- every curve = its summed numerators / its summed count, "_AUC" of
     every curve, "SPR", and "PM" between "TFP" and "human_TFP" (or the human_curve passed to result, for the model's exact curve).  The
     hit curves of scanpaths merge exactly (integer numerators); sums of ratios and of probabilities merge to rounding."""
-
-    def __init__(self):
-        self.parts = {}
-
-    def add(self, means) -> None:
-        for k, v in means.items():
-            if k == "empty_boxes" or k.endswith(("_sum", "_count", "_nan")):
-                self.parts[k] = self.parts[k] + v if k in self.parts else (np.array(v, dtype=np.float64) if isinstance(v, np.ndarray) else v)
+    _suffixes, _also, _dtype = ("_sum", "_count", "_nan"), ("empty_boxes",), np.float64
 
     def result(self, human_curve=None) -> dict:
         from .evaltools.search_efficiency import probability_mismatch, tfp_auc
-        out = dict(self.parts)
-        for k in self.parts:
-            if k.endswith("_count"):
-                m = k[:-len("_count")]
-                total, count = self.parts[m + "_sum"], self.parts[k]
-                if isinstance(total, np.ndarray):
-                    out[m] = total / count if count else np.full(total.shape, np.nan)
-                    out[m + "_AUC"] = tfp_auc(out[m])
-                else:
-                    out[m] = total / count if count else float("nan")
+        out = self._divided()
+        for m in [m for m, v in out.items() if isinstance(v, np.ndarray) and m + "_count" in self.parts]:      # the curves
+            out[m + "_AUC"] = tfp_auc(out[m])
         human = out.get("human_TFP") if human_curve is None else np.asarray(human_curve, dtype=np.float64).reshape(-1)
         if human is not None and "TFP" in out:
             out["PM"] = probability_mismatch(out["TFP"], human)
@@ -1127,10 +1139,8 @@ def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, 
     means["by_group"][label] holds the same entries for the keys of that label.  per_key: "keys" and, per key in first-appearance order
     of gt_keys, the number of saccades counted and of fixations dropped ("human_saccades", "human_dropped", "saccades", "dropped", int64
     [G]) -- no lattice per key."""
-    from .evaltools.saccade_statistics import (_check_directions, _check_edges, _check_shape, saccade_counts)
-    from .evaltools.scanpath_likelihood import _check_frame
-    from .evaltools.search_efficiency import _check_steps
-    max_steps, (Hm, Wm), _ = _check_steps(max_steps), _check_shape(map_shape), _check_frame(frame_size)
+    from .evaltools.saccade_statistics import _check_directions, _check_edges, _check_shape, saccade_counts
+    max_steps, (Hm, Wm), _ = check_steps(max_steps), _check_shape(map_shape), check_frame(frame_size)
     amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
     gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
     labels, label_of_key = _group_labels(index, groups)
@@ -1142,10 +1152,11 @@ def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, 
     paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
     res = saccade_counts(paths, launch_group, 2 * NL, frame_size, (Hm, Wm), max_steps=max_steps)
     sacc, drop = res["saccades"].astype(np.int64), res["dropped"].astype(np.int64)
+    sides = (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ())
 
     def entries(label_index):
         out = {}
-        for prefix, s in (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ()):
+        for prefix, s in sides:
             mine = side == s
             if label_index is None:
                 lattice = res["counts"][s * NL:(s + 1) * NL].sum(0)
@@ -1160,7 +1171,7 @@ def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, 
     if groups is not None:
         means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
     per_key = {"keys": list(index)}
-    for prefix, s in (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ()):
+    for prefix, s in sides:
         mine = side == s
         per_key[prefix + "saccades"] = np.bincount(key_of[mine], weights=sacc[mine], minlength=G).astype(np.int64)
         per_key[prefix + "dropped"] = np.bincount(key_of[mine], weights=drop[mine], minlength=G).astype(np.int64)
@@ -1192,11 +1203,9 @@ def saccade_statistics_model_evaluation(predict, keys, *, min_length, max_steps,
     with groups, means["by_group"][label] the same per label (human_lattice: one lattice for the pooled entries, or a dict label ->
     lattice with the pooled one under None).  per_key: "keys" and "saccades" float64 [G], the expected number of saccades per entry of
     the key (NaN for a key without a good entry)."""
-    from .evaltools.saccade_statistics import _check_directions, _check_edges, saccade_expectation
-    from .evaltools.scanpath_likelihood import _check_frame, _check_map
-    from .evaltools.search_efficiency import _check_min_length, _check_steps
-    max_steps, min_length = _check_steps(max_steps), _check_min_length(min_length)
-    _check_frame(frame_size)
+    from .evaltools.saccade_statistics import MAX_CELLS, _check_directions, _check_edges, saccade_expectation
+    max_steps, min_length = check_steps(max_steps), check_min_length(min_length)
+    check_frame(frame_size)
     if (amplitude_edges is None) != (n_directions is None):
         raise ValueError("amplitude_edges and n_directions go together: the summary needs both")
     if amplitude_edges is not None:
@@ -1208,26 +1217,13 @@ def saccade_statistics_model_evaluation(predict, keys, *, min_length, max_steps,
     if performances is not None and len(performances) != N:
         raise ValueError("one list of performances per sample is required")
     import torch
-    names = ["all_actions_prob"] if performances is None else ["good_all_actions_prob", "poor_all_actions_prob"]
-    missing = [k for k in names if k not in predict]
-    if missing:
-        raise ValueError(f"predict lacks {missing[0]!r}" + (" (performances given: the two-head outputs are read)" if performances is not None
-                                                            else ""))
-    if any(predict[k].shape[0] != N for k in names):
-        raise ValueError(f"predict holds {predict[names[0]].shape[0]} samples, keys {N}")
-    _check_map(int(predict[names[0]].shape[-1]), map_shape)
-    index, _ = _key_index(keys, None)
+    index, rows, key_of, shape, both = _head_entries(predict, keys, performances)
+    check_map(int(shape[-1]), map_shape, max_cells=MAX_CELLS)
     labels, label_of_key = _group_labels(index, groups)
     NL = max(len(labels), 1)
-    rows, key_of = [], []
-    for i in range(N):
-        for good in ([None] if performances is None else performances[i]):
-            rows.append(i if performances is None or good == True else N + i)                      # noqa: E712  (as likelihood_evaluation)
-            key_of.append(index[keys[i]])
-    key_of, G = np.asarray(key_of, dtype=np.int64), len(index)
     if not len(rows):
         raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
-    probs = predict[names[0]] if performances is None else torch.cat([predict[names[0]], predict[names[1]]], 0)
+    probs = both("all_actions_prob")
     if performances is not None:                               # one row per entry: a head read by k subjects counts k times
         probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
     entry_label = label_of_key[key_of]
@@ -1253,39 +1249,25 @@ def saccade_statistics_model_evaluation(predict, keys, *, min_length, max_steps,
     means = entries(None)
     if groups is not None:
         means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
-    ksum = np.bincount(key_of[good], weights=res["saccades"][good], minlength=G)
-    kcnt = np.bincount(key_of[good], minlength=G)
-    per_key = {"keys": list(index), "saccades": np.where(kcnt > 0, ksum / np.maximum(kcnt, 1), np.nan)}
+    per_key = {"keys": list(index), "saccades": _pool(np.where(good, res["saccades"], np.nan), key_of, len(index))[0]}
     return means, per_key
 
 
-class SaccadeStatisticsTable:
+class SaccadeStatisticsTable(_SumTable):
     """The pooled results of the saccade-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
     "_dropped" entry (also inside "by_group"); result(human_lattice=None) derives the summaries and the four comparison numbers from
     the SUMMED lattices, as one call on the union of the batches gives them.  The comparison is against "human_lattice_sum" when the
     table holds one, else against human_lattice (one lattice for the pooled entries, or a dict label -> lattice with the pooled one
     under None).  Integer lattices (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums and
     merge to rounding: the batches' lattices are added in the order of add, one call adds its rows in row order."""
+    _suffixes = ("_sum", "_count", "_bad", "_dropped")
 
     def __init__(self, frame_size, map_shape, amplitude_edges, n_directions):
         from .evaltools.saccade_statistics import _check_directions, _check_edges, _check_shape
-        from .evaltools.scanpath_likelihood import _check_frame
-        self.frame_size, self.map_shape = _check_frame(frame_size), _check_shape(map_shape)
+        super().__init__()
+        self.frame_size, self.map_shape = check_frame(frame_size), _check_shape(map_shape)
         self.amplitude_edges, self.n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
-        self.parts, self.by_group = {}, {}
-
-    def _merge(self, parts, means) -> None:
-        want = (2 * self.map_shape[0] - 1, 2 * self.map_shape[1] - 1)
-        for k, v in means.items():
-            if k.endswith(("_sum", "_count", "_bad", "_dropped")):
-                if isinstance(v, np.ndarray) and v.shape != want:
-                    raise ValueError(f"{k} of shape {v.shape}: the table's lattice is {want}")
-                parts[k] = parts[k] + v if k in parts else (v.copy() if isinstance(v, np.ndarray) else v)
-
-    def add(self, means) -> None:
-        self._merge(self.parts, means)
-        for label, m in means.get("by_group", {}).items():
-            self._merge(self.by_group.setdefault(label, {}), m)
+        self._shape = (2 * self.map_shape[0] - 1, 2 * self.map_shape[1] - 1)
 
     def result(self, human_lattice=None) -> dict:
         args = (self.frame_size, self.amplitude_edges, self.n_directions)
@@ -1358,7 +1340,7 @@ def bootstrap_evaluation(per_key, *, names=None, cluster_keys=None, replicates, 
     out = {}
     for s, name in enumerate(names):
         out[name] = _interval(res, s)
-        out[name]["estimate"] = _nanmean(np.where(den[:, s] > 0, num[:, s], np.nan))
+        out[name]["estimate"] = _nanmean(np.where(den[:, s] > 0, num[:, s], np.nan))[0]
     return out
 
 
