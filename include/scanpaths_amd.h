@@ -700,6 +700,35 @@ int sp_scan_saccade_counts(const double* fix, int ncol, const int64_t* start, co
                            void* stream);
 int sp_scan_saccade_expectation(const float* probs, const int* row_group, int R, int T, int Hm, int Wm, int ngroups, int min_length,
                                 int max_steps, double* work, double* E, double* saccades, int* bad, void* stream);
+/* Turning angles (csrc/scanturn.hip), float64, every operation rounded on its own: the direction-transition table
+ * M [n + 1][n + 1], n = n_directions in [1, sp_scan_turn_max_directions()]: M[k][k'] = the number of consecutive saccade pairs
+ * (fixation t -> t + 1, then t + 1 -> t + 2) whose first saccade is in sector k and whose second is in sector k'.  Cells, displacements
+ * and the lattice index are those of the saccade statistics above; sector [D] int32 gives every displacement its sector, 0 .. n - 1
+ * for a direction and n for the zero displacement ("stayed"); it is only read (the device computes no atan2), and a value outside
+ * [0, n] is read as n.  Hm * Wm at most sp_scan_likelihood_max_cells().
+ * sp_scan_turn_counts (one wavefront per scanpath; a zeroing launch and the counting launch): the fixation layout, the first
+ * min(n, max_steps) fixations, the pixel rule and dropped [nscan] of sp_scan_saccade_counts.  Pair t counts iff fixations t, t + 1 and
+ * t + 2 are all kept (nothing bridges a dropped fixation): counts [ngroups][n + 1][n + 1] int64 gets 1 by an integer atomic add, pairs
+ * [nscan] the number counted.  A count outside [0, sp_scan_max_fixations()] or a group outside [0, ngroups): pairs -1, dropped 0, none
+ * of its rows is read.  The launcher zeroes counts; every element of every output is written.
+ * sp_scan_turn_expectation (one block per (row, step triple), then one thread per (row, entry) and per (group, entry): three
+ * launches): the expected table of the scanpaths the sampler draws from probs [R][T][1 + Hm * Wm] float32, in closed form.  Z_t, D_t,
+ * q_t, c_t(i), A_t and bad are exactly those of sp_scan_saccade_expectation (the same summation order).  With Tm = min(T, max_steps):
+ *   in_t[b][k] = sum of c_t(a) over the cells a with sector(b - a) = k, out_t[b][k'] = sum of c_{t+2}(a) over the cells a with
+ *   sector(a - b) = k', both in ascending row-major a from 0.0;  X_t[k][k'] = sum over the cells b, ascending from 0.0, of
+ *   (c_{t+1}(b) * in_t[b][k]) * out_t[b][k'];  M_r = sum_{t = 0}^{Tm - 3} (A_t * X_t), ascending t from 0.0;  pairs [R] =
+ *   sum_t A_t * (((1 - q_t) * (1 - q_{t+1})) * (1 - q_{t+2})) in the same order;  M [ngroups][n + 1][n + 1] = the M_r of the group's
+ *   good rows added in ascending row index from 0.0 (no floating-point atomics).
+ * Bad rows (bad 1, pairs NaN, nothing added), row_group outside [0, ngroups) (bad -1) and steps t >= Tm as in
+ * sp_scan_saccade_expectation; Tm < 3: M and pairs are zero (a bad row stays bad).  work: scratch of R * max(Tm - 2, 1) * (n + 1)^2
+ * doubles, contents undefined afterwards.  All outputs and work are required; every element of M, pairs and bad is written. */
+int sp_scan_turn_max_directions(void);
+int sp_scan_turn_counts(const double* fix, int ncol, const int64_t* start, const int* count, const int* group, int nscan, int ngroups,
+                        int max_steps, int Hm, int Wm, double frame_w, double frame_h, const int* sector, int n_directions,
+                        int64_t* counts, int* pairs, int* dropped, void* stream);
+int sp_scan_turn_expectation(const float* probs, const int* row_group, int R, int T, int Hm, int Wm, int ngroups, int min_length,
+                             int max_steps, const int* sector, int n_directions, double* work, double* M, double* pairs, int* bad,
+                             void* stream);
 /* Cluster bootstrap of ratio-of-sums statistics (csrc/scanboot.hip), float64, every operation rounded on its own,
  * every sum in a fixed order, no floating-point atomics.
  * sp_boot_cluster_sums (one thread per (cluster, column)): num, den [G][M] with the keys sorted by cluster, ascending key index inside a

@@ -163,6 +163,9 @@ SIGNATURES = {
     "sp_scan_target_mass": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P]),
     "sp_scan_saccade_counts": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P]),
     "sp_scan_saccade_expectation": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "sp_scan_turn_max_directions": (_I, []),
+    "sp_scan_turn_counts": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, C.c_double, C.c_double, _P, _I, _P, _P, _P, _P]),
+    "sp_scan_turn_expectation": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "sp_boot_max_columns": (_I, []),
     "sp_boot_cluster_sums": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "sp_boot_resample": (_I, [_P, _P, _I, _I, _I, _P, _I, _I, C.c_uint64, _P, _P, _P]),

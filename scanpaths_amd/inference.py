@@ -177,3 +177,26 @@ def run_saccade_statistics_loop(model, loader: Iterable[dict], *, min_length, ma
     if table is None:
         raise ValueError("the loader yielded no batch")
     return table.result(human_lattice), per_batch
+
+
+@torch.no_grad()
+def run_turn_statistics_loop(model, loader: Iterable[dict], *, min_length, max_steps, n_directions, human_table=None,
+                             ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None) -> Tuple[dict, List[dict]]:
+    """The model's own direction-transition table over a loader, exactly and without sampling
+    (utils.evaluation.turn_statistics_model_evaluation): per batch ONE eval-mode forward, ONE sp_scan_turn_expectation call and ONE small
+    device->host copy (the batch's table; the distributions stay on the device).  loader, "tasks", "performances" and the keys as in
+    run_saccade_statistics_loop.  min_length is the sampler's; it, max_steps and n_directions (at most 16) have no defaults;
+    human_table (optional, utils.evaluation.turn_statistics_human_evaluation's "human_table_sum"): for "JSD_turn" and "JSD_transition".
+    map_shape defaults to (30, 40) for 1201 actions only.
+    Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.TurnStatisticsTable."""
+    from .utils.evaluation import TurnStatisticsTable, turn_statistics_model_evaluation
+    table, per_batch = TurnStatisticsTable(n_directions), []
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
+        means, per_key = turn_statistics_model_evaluation(
+            predict, batch["question_ids"], min_length=min_length, max_steps=max_steps, n_directions=n_directions,
+            performances=_performances(batch, predict), frame_size=frame_size, map_shape=map_shape)
+        table.add(means)
+        per_batch.append(per_key)
+    if not per_batch:
+        raise ValueError("the loader yielded no batch")
+    return table.result(human_table), per_batch

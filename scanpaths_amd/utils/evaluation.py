@@ -14,10 +14,10 @@
   each (a question id, an image name) and returns (means, per_key), per_key in first-appearance order of the keys.  _keyed / _key_index
   check the keys; _model_pairs / _ceiling_pairs / _pair_tables serve the pair measures (saliency_*, scanpath_distance_*,
   sequence_score_*); the model-side calls that read the model's distributions instead of samples (likelihood_*, search_efficiency_model_*,
-  saccade_statistics_model_*) get their entries from _head_entries; _pool is the mean per key with its pooled sum and count, _key_means
+  saccade_statistics_model_*, turn_statistics_model_*) get their entries from _head_entries; _pool is the mean per key with its pooled sum and count, _key_means
   the mean over keys.
 
-  Tables: LikelihoodTable, SearchEfficiencyTable, SaccadeStatisticsTable merge the means of several batches (_SumTable holds the merge).
+  Tables: LikelihoodTable, SearchEfficiencyTable, SaccadeStatisticsTable, TurnStatisticsTable merge the means of several batches (_SumTable holds the merge).
 
   Bootstrap: bootstrap_evaluation / bootstrap_comparison / bootstrap_information_gain_explained put intervals on any per_key table."""
 from __future__ import annotations
@@ -819,7 +819,7 @@ def _head_entries(predict, keys, performances, per_sample=None, outputs=("all_ac
 
 
 class _SumTable:
-    """What the three tables share.  add(means) sums the entries whose name is in _also or ends in one of _suffixes into parts -- and
+    """What the tables share.  add(means) sums the entries whose name is in _also or ends in one of _suffixes into parts -- and
     those of means["by_group"][label] into by_group[label]; the first array of a name is copied (as _dtype, where a table sets one), so
     that the caller's is never written to, and where the table has a shape an array of another one is refused.  _divided() = parts with
     every name that has a "_count" as its "_sum" / "_count" (NaN for a count of 0)."""
@@ -1274,6 +1274,163 @@ class SaccadeStatisticsTable(_SumTable):
         out = _saccade_derived(self.parts, *args, _human_of(human_lattice, None))
         if self.by_group:
             out["by_group"] = {label: _saccade_derived(p, *args, _human_of(human_lattice, label)) for label, p in self.by_group.items()}
+        return out
+
+
+# ---- turning angles (evaltools/turn_statistics.py, csrc/scanturn.hip) ------------------------------------------------------
+def _turn_derived(parts, human_table=None):
+    """the summed entries of one group -> the same with "summary" / "human_summary" (evaltools.turn_statistics.turn_summary) and,
+    against human_table (default: the group's own "human_table_sum"), the two comparison numbers "JSD_turn" and "JSD_transition" in bits"""
+    from .evaltools.turn_statistics import turn_comparison, turn_summary
+    out = dict(parts)
+    if "human_table_sum" in parts:
+        out["human_summary"] = turn_summary(parts["human_table_sum"])
+    if "table_sum" in parts:
+        out["summary"] = turn_summary(parts["table_sum"])
+        human = parts.get("human_table_sum") if human_table is None else human_table
+        if human is not None:
+            out.update(turn_comparison(parts["table_sum"], human))
+    return out
+
+
+def turn_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, frame_size, map_shape, max_steps, n_directions,
+                               groups=None, image_keys=None):
+    """How the direction of a saccade depends on the direction of the saccade before it (Tatler & Vincent 2009; Le Meur & Liu 2015): the
+    direction-transition table and the turning-angle histogram with its forward and its return peak, for predicted scanpaths and for the
+    human ones, keyed and grouped as saccade_statistics_evaluation keys and groups them.  frame_size = (height, width), map_shape =
+    (Hm, Wm), max_steps and n_directions (at most 16) have no defaults.  Humans and predictions of all groups are counted in ONE launch
+    (evaltools.turn_statistics.turn_counts).
+    Returns (means, per_key).  means["human_table_sum"] / ["table_sum"] int64 [n + 1, n + 1] (exact; row and column n hold the stays),
+    ["human_pairs_sum"] / ["pairs_sum"], ["human_scanpaths_count"] / ["scanpaths_count"], ["human_fixations_dropped"] /
+    ["fixations_dropped"] -- what TurnStatisticsTable merges -- ["human_summary"] / ["summary"] (evaltools.turn_statistics.turn_summary)
+    and, against the human side, ["JSD_turn"] and ["JSD_transition"] (bits).  With groups, means["by_group"][label] holds the same
+    entries for the keys of that label.  per_key: "keys" and, per key in first-appearance order of gt_keys, the number of saccade pairs
+    counted and of fixations dropped ("human_pairs", "human_dropped", "pairs", "dropped", int64 [G]) -- no table per key."""
+    from .evaltools.saccade_statistics import _check_shape
+    from .evaltools.turn_statistics import _check_n, turn_counts
+    max_steps, (Hm, Wm), _ = check_steps(max_steps), _check_shape(map_shape), check_frame(frame_size)
+    n_directions = _check_n(n_directions)
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
+    labels, label_of_key = _group_labels(index, groups)
+    NL = max(len(labels), 1)
+    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
+    H, G = len(gt_keys), len(index)
+    side = np.r_[np.zeros(H, dtype=np.int64), np.ones(len(predict_keys), dtype=np.int64)]
+    launch_group = side * NL + (label_of_key[key_of] if len(key_of) else key_of)
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
+    res = turn_counts(paths, launch_group, 2 * NL, frame_size, (Hm, Wm), max_steps=max_steps, n_directions=n_directions)
+    pairs, drop = res["pairs"].astype(np.int64), res["dropped"].astype(np.int64)
+    sides = (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ())
+
+    def entries(label_index):
+        out = {}
+        for prefix, s in sides:
+            mine = side == s
+            if label_index is None:
+                table = res["counts"][s * NL:(s + 1) * NL].sum(0)
+            else:
+                table = res["counts"][s * NL + label_index]
+                mine = mine & (label_of_key[key_of] == label_index)
+            out.update({prefix + "table_sum": table, prefix + "pairs_sum": int(pairs[mine].sum()),
+                        prefix + "scanpaths_count": int(mine.sum()), prefix + "fixations_dropped": int(drop[mine].sum())})
+        return _turn_derived(out)
+
+    means = entries(None)
+    if groups is not None:
+        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
+    per_key = {"keys": list(index)}
+    for prefix, s in sides:
+        mine = side == s
+        per_key[prefix + "pairs"] = np.bincount(key_of[mine], weights=pairs[mine], minlength=G).astype(np.int64)
+        per_key[prefix + "dropped"] = np.bincount(key_of[mine], weights=drop[mine], minlength=G).astype(np.int64)
+    return means, per_key
+
+
+def turn_statistics_human_evaluation(gt_fix_vectors, gt_keys, *, frame_size, map_shape, max_steps, n_directions, groups=None,
+                                     image_keys=None):
+    """The human row of turn_statistics_evaluation alone: the "human_" entries; means["human_table_sum"] is the human_table of
+    turn_statistics_model_evaluation and of TurnStatisticsTable.result."""
+    return turn_statistics_evaluation(gt_fix_vectors, None, gt_keys, None, frame_size=frame_size, map_shape=map_shape, max_steps=max_steps,
+                                      n_directions=n_directions, groups=groups, image_keys=image_keys)
+
+
+def turn_statistics_model_evaluation(predict, keys, *, min_length, max_steps, n_directions, performances=None, frame_size=(240, 320),
+                                     map_shape=None, groups=None, human_table=None):
+    """The model's own direction-transition table of ONE batch, exactly and without sampling
+    (evaltools.turn_statistics.turn_expectation): predict, keys, performances and groups as in saccade_statistics_model_evaluation (the
+    heads are assigned per subject in the same way).  min_length (the sampler's), max_steps and n_directions (at most 16) are required;
+    frame_size gives the sectors their directions in pixels.  One expectation call and one copy back for the batch; an entry whose row
+    is bad (a step without mass) adds nothing and is counted.
+    Returns (means, per_key): means["table_sum"] float64 [n + 1, n + 1] = the expected pair counts summed over the entries,
+    ["pairs_sum"] its total as the kernel's closed form gives it, ["rows_count"] / ["rows_bad"] the entries that count / were bad --
+    what TurnStatisticsTable merges -- ["summary"] and, when human_table is given, ["JSD_turn"] and ["JSD_transition"] against it; with
+    groups, means["by_group"][label] the same per label (human_table: one table for the pooled entries, or a dict label -> table with
+    the pooled one under None).  per_key: "keys" and "pairs" float64 [G], the expected number of pairs per entry of the key (NaN for a
+    key without a good entry)."""
+    from .evaltools.scanpath_likelihood import MAX_CELLS
+    from .evaltools.turn_statistics import _check_n, _check_table, turn_expectation
+    max_steps, min_length, n_directions = check_steps(max_steps), check_min_length(min_length), _check_n(n_directions)
+    check_frame(frame_size)
+    for h in (human_table.values() if isinstance(human_table, dict) else () if human_table is None else (human_table,)):
+        if _check_table(h).shape != (n_directions + 1, n_directions + 1):
+            raise ValueError(f"human_table of shape {np.shape(h)}: [{n_directions + 1}, {n_directions + 1}] is required")
+    keys = list(keys)
+    N = len(keys)
+    if performances is not None and len(performances) != N:
+        raise ValueError("one list of performances per sample is required")
+    import torch
+    index, rows, key_of, shape, both = _head_entries(predict, keys, performances)
+    check_map(int(shape[-1]), map_shape, max_cells=MAX_CELLS)
+    labels, label_of_key = _group_labels(index, groups)
+    NL = max(len(labels), 1)
+    if not len(rows):
+        raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
+    probs = both("all_actions_prob")
+    if performances is not None:                               # one row per entry: a head read by k subjects counts k times
+        probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
+    entry_label = label_of_key[key_of]
+    res = turn_expectation(probs, entry_label, NL, min_length=min_length, max_steps=max_steps, frame_size=frame_size,
+                           n_directions=n_directions, map_shape=map_shape)
+    good = res["bad"] == 0
+
+    def entries(label_index):
+        mine = good if label_index is None else good & (entry_label == label_index)
+        lost = ~good if label_index is None else ~good & (entry_label == label_index)
+        if label_index is not None:
+            table = res["M"][label_index]
+        else:
+            table = res["M"][0].copy()
+            for g in range(1, NL):                              # ascending label: a fixed order
+                table = table + res["M"][g]
+        out = {"table_sum": table, "pairs_sum": float(res["pairs"][mine].sum()), "rows_count": int(mine.sum()), "rows_bad": int(lost.sum())}
+        return _turn_derived(out, _human_of(human_table, None if label_index is None else labels[label_index]))
+
+    means = entries(None)
+    if groups is not None:
+        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
+    per_key = {"keys": list(index), "pairs": _pool(np.where(good, res["pairs"], np.nan), key_of, len(index))[0]}
+    return means, per_key
+
+
+class TurnStatisticsTable(_SumTable):
+    """The pooled results of the turn-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
+    "_dropped" entry (also inside "by_group"); result(human_table=None) derives the summaries and the two comparison numbers from the
+    SUMMED tables, as one call on the union of the batches gives them.  The comparison is against "human_table_sum" when the table
+    holds one, else against human_table (one table for the pooled entries, or a dict label -> table with the pooled one under None).
+    Integer tables (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums of non-negative terms
+    and merge to rounding: the batches' tables are added in the order of add, one call adds its rows in row order."""
+    _suffixes = ("_sum", "_count", "_bad", "_dropped")
+
+    def __init__(self, n_directions):
+        from .evaltools.turn_statistics import _check_n
+        super().__init__()
+        self.n_directions = _check_n(n_directions)
+        self._shape = (self.n_directions + 1, self.n_directions + 1)
+
+    def result(self, human_table=None) -> dict:
+        out = _turn_derived(self.parts, _human_of(human_table, None))
+        if self.by_group:
+            out["by_group"] = {label: _turn_derived(p, _human_of(human_table, label)) for label, p in self.by_group.items()}
         return out
 
 
