@@ -25,7 +25,6 @@
 namespace {
 
 constexpr int MAXBW = 16;          // = sp_scan_kde_max_bandwidths(): a source's 4 * K prologue values of a 32-source tile fit 16 KB of LDS
-constexpr int MAXCELLS = 2048;     // = sp_scan_likelihood_max_cells()
 constexpr int SLOTS = MAXCELLS / 256;
 constexpr int WBUF = 4096;         // doubles of staged axis weights per tile: at least one source (Hm + Wm <= MAXCELLS + 1)
 constexpr int TILE = 32;           // sources per tile of the pair kernel

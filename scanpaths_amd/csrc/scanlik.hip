@@ -21,7 +21,7 @@
 namespace {
 
 constexpr int SLOTS = 32;         // registers per lane that hold a step's map
-constexpr int MAXCELLS = SLOTS * 64;
+static_assert(SLOTS * 64 == MAXCELLS, "a step map fills the registers of one wave");
 
 struct LikArgs {
     const float *probs, *mu, *sigma2;

@@ -1,16 +1,15 @@
 // Saccade statistics: how a scanpath moves.  A fixation is read as the action-map cell it falls in (the pixel rule of
 // scan_common.h: scan_in_frame / scan_cell, the one scanlik.hip uses), a saccade is the cell displacement (dr, dc) = (row(f_{t+1}) -
-// row(f_t), col(f_{t+1}) - col(f_t)), and everything is counted on ONE displacement lattice of D = (2 Hm - 1) (2 Wm - 1) entries: entry
-// (dr + Hm - 1) * (2 Wm - 1) + (dc + Wm - 1).  float64, every operation rounded on its own (the arithmetic rule of scan_common.h:
-// contraction OFF, plain operators).
+// row(f_t), col(f_{t+1}) - col(f_t)), and everything is counted on ONE displacement lattice of D = (2 Hm - 1) (2 Wm - 1) entries
+// (scan_lattice_index).  float64, every operation rounded on its own (the arithmetic rule of scan_common.h: contraction OFF, plain
+// operators).
 //
 //   scan_saccade_counts_kernel: scanpaths that exist (humans, samples).  ONE WAVEFRONT PER SCANPATH, four per block, one lane per
-//     fixation.  Only the first m = min(n, max_steps) fixations count; a fixation outside the frame or with a non-finite coordinate is
-//     dropped (counted in dropped); saccade t counts iff fixations t and t + 1 are both kept -- nothing bridges a dropped fixation.  Lane
-//     t takes the cell of lane t + 1 by a shuffle and adds 1 to counts[group][entry] with an INTEGER atomic add on the int64 lattice: the
-//     counts are integers, so the order in which the atomics land cannot change them.  A launch of scan_saccade_zero_kernel zeroes the
-//     lattice first (a kernel, not a memset: common.h).  A count outside [0, MAXFIX] or a group outside [0, ngroups): saccades -1,
-//     dropped 0, none of its rows is read, nothing is counted.
+//     fixation, read as a cell by scan_lane_cell (scan_common.h: which fixations count and which are dropped); saccade t counts iff
+//     fixations t and t + 1 are both kept.  Lane t takes the cell of lane t + 1 by a shuffle and adds 1 to counts[group][entry] with an
+//     INTEGER atomic add on the int64 lattice: the counts are integers, so the order in which the atomics land cannot change them.
+//     scan_zero_kernel (scan_common.h) zeroes the lattice first.  A count outside [0, MAXFIX] or a group outside [0, ngroups): saccades
+//     -1, dropped 0, none of its rows is read, nothing is counted.
 //
 //   scan_saccade_expect_kernel: the model, in closed form.  The step distributions are not conditioned on sampled fixations, so the
 //     expected number of saccades of row r with displacement d is E_r[d] = sum_t A_t X_t[d], X_t[d] = sum_i c_t(i) c_{t+1}(i + d) -- a
@@ -18,10 +17,9 @@
 //     ONE BLOCK PER (row, tile of 256 displacements), four waves; thread k of tile j owns displacement d = 256 j + k for every step, so
 //     the 64 lanes of a wave own consecutive dc of (mostly) one dr.  The block walks t serially with c_t and c_{t+1} in LDS (2 P doubles,
 //     at most 32 KB, dynamic; c_{t+1} becomes the next c_t by parity).  THE ORDER OF EVERY SUM:
-//       Z_t    = the P cell values: lane l adds cells l, l + 64, l + 128, .. in that order from 0.0; the 64 partial sums combine by the xor
-//                butterfly 32, 16, 8, 4, 2, 1 (wave_sum_d) -- the order of scansearch.hip and scanlik.hip, a function of P alone.  Every
-//                wave of the block computes it for itself (the same bits), so nothing is passed between waves;
-//       D_t = Z_t + p0_t for t >= min_length, else Z_t;  q_t = p0_t / D_t for t >= min_length, else 0;  c_t(i) = (double)p_t[1 + i] / D_t;
+//       Z_t, D_t, q_t = the step normalisation of scan_common.h (scan_step_mass, scan_step_norm), shared with scanturn.hip and
+//                scansearch.hip.  Every wave of the block computes it for itself (the same bits), so nothing is passed between waves;
+//       c_t(i) = (double)p_t[1 + i] / D_t;
 //       A_0 = 1, A_{t+1} = A_t * (1.0 - q_t);
 //       X_t[d] = over the cells i = (r, c) whose partner (r + dr, c + dc) lies inside the map, in ASCENDING ROW-MAJOR i from 0.0, every
 //                product rounded before it is added (rows max(0, -dr) .. min(Hm, Hm - dr) - 1, columns max(0, -dc) .. min(Wm, Wm - dc) - 1);
@@ -29,7 +27,7 @@
 //       saccades[r] = sum_t A_t * ((1.0 - q_t) * (1.0 - q_{t+1})) in the same order.
 //     LDS reads: for dc >= 0 the c_t(i) address is the same in all lanes of a dr (a broadcast) and the c_{t+1}(i + d) addresses are
 //     consecutive doubles (ds_read_b64: 32 consecutive doubles cover the 64 banks once, no conflict); for dc < 0 the roles swap.
-//     A row is BAD iff some D_t with t < Tm is zero or not finite (the walk stops there; every wave sees the same D_t, so the exit is
+//     A row is BAD iff some step t < Tm is bad (scan_step_norm; the walk stops there; every wave sees the same D_t, so the exit is
 //     block-uniform): bad 1, saccades NaN, the row adds nothing to its group.  row_group outside [0, ngroups): bad -1, saccades NaN,
 //     nothing of the row is read.  Tm < 2: no pair, E_r = 0 and saccades 0 (a bad D_0 still makes the row bad).
 //     E_r goes to work [R][D] (scratch of the call: R * D doubles; 22 MB for 600 rows on 30 x 40); scan_saccade_group_kernel, one thread
@@ -39,13 +37,6 @@
 #include "scan_common.h"
 
 namespace {
-
-constexpr int MAXCELLS = 2048;    // = sp_scan_likelihood_max_cells(): two step maps in double fit in 32 KB of LDS
-
-__global__ __launch_bounds__(256) void scan_saccade_zero_kernel(unsigned long long* __restrict__ p, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = 0ull;
-}
 
 struct CountArgs {
     const double* fix;
@@ -64,26 +55,14 @@ __global__ __launch_bounds__(256) void scan_saccade_counts_kernel(const CountArg
     const int n = a.count[s], g = a.group[s];
     int ns = -1, nd = 0;
     if (!scan_count_bad(n) && g >= 0 && g < a.ngroups) {              // wave-uniform
-        const int m = min(n, a.max_steps);
-        bool kept = false;
-        int row = 0, col = 0;
-        if (lane < m) {
-            const double* __restrict__ f = a.fix + (a.start[s] + lane) * a.ncol;
-            const double x = f[0], y = f[1];
-            kept = scan_in_frame(x, y, a.frame_w, a.frame_h);
-            if (kept) {
-                col = scan_cell(x, a.Wm, a.frame_w);
-                row = scan_cell(y, a.Hm, a.frame_h);
-            }
-        }
-        nd = __popcll(__ballot(lane < m && !kept));
-        const int rn = __shfl_down(row, 1, 64), cn = __shfl_down(col, 1, 64), kn = __shfl_down((int)kept, 1, 64);
-        const bool sac = lane + 1 < m && kept && kn != 0;              // m <= 64: lane 63 never has a successor
+        const ScanLaneCell f = scan_lane_cell(a.fix, a.ncol, a.start, s, n, a.max_steps, lane, a.Hm, a.Wm, a.frame_w, a.frame_h);
+        nd = f.dropped;
+        const int rn = __shfl_down(f.row, 1, 64), cn = __shfl_down(f.col, 1, 64), kn = __shfl_down((int)f.kept, 1, 64);
+        const bool sac = lane + 1 < f.m && f.kept && kn != 0;          // m <= 64: lane 63 never has a successor
         ns = __popcll(__ballot(sac));
         if (sac) {
-            const int LW = 2 * a.Wm - 1;
-            const int64_t D = (int64_t)(2 * a.Hm - 1) * LW;
-            atomicAdd(a.counts + (int64_t)g * D + (int64_t)(rn - row + a.Hm - 1) * LW + (cn - col + a.Wm - 1), 1ull);
+            const int64_t D = (int64_t)(2 * a.Hm - 1) * (2 * a.Wm - 1);
+            atomicAdd(a.counts + (int64_t)g * D + scan_lattice_index(rn - f.row, cn - f.col, a.Hm, a.Wm), 1ull);
         }
     }
     if (lane == 0) {
@@ -129,17 +108,12 @@ __global__ __launch_bounds__(256) void scan_saccade_expect_kernel(const ExpArgs 
     bool isbad = false;
     for (int t = 0; t < a.Tm; ++t) {
         const float* __restrict__ p = a.probs + ((int64_t)r * a.T + t) * (int64_t)(P + 1);
-        double z = 0.0;
-        for (int c = lane; c < P; c += 64) z = z + (double)p[1 + c];
-        const double Z = wave_sum_d(z);
-        const bool stop = t >= a.min_length;
-        const double p0 = stop ? (double)p[0] : 0.0;
-        const double Dt = stop ? Z + p0 : Z;
-        if (Dt == 0.0 || !isfinite(Dt)) {                           // the same bits in every wave: a block-uniform exit
+        const ScanStep st = scan_step_norm(scan_step_mass(p, P, lane), p, t >= a.min_length);
+        if (st.bad) {                                               // the same bits in every wave: a block-uniform exit
             isbad = true;
             break;
         }
-        const double q = stop ? p0 / Dt : 0.0;
+        const double Dt = st.D, q = st.q;
         double* __restrict__ nxt = sh + (t & 1) * P;
         for (int i = tid; i < P; i += 256) nxt[i] = (double)p[1 + i] / Dt;
         __syncthreads();                                            // c_t is in LDS
@@ -184,14 +158,12 @@ extern "C" int sp_scan_saccade_counts(const double* fix, int ncol, const int64_t
                                       int* saccades, int* dropped, void* stream) {
     if (!fix || !start || !count || !group) return SP_ENULL;
     if (!counts || !saccades || !dropped) return SP_ENULL;
-    if (ncol < 2 || nscan < 1 || ngroups < 1 || max_steps < 1 || Hm < 1 || Wm < 1) return SP_EINVAL;
-    if ((int64_t)Hm * Wm > MAXCELLS) return SP_EINVAL;
-    if (!(frame_w > 0) || !(frame_w < INFINITY) || !(frame_h > 0) || !(frame_h < INFINITY)) return SP_EINVAL;
+    if (ncol < 2 || nscan < 1 || ngroups < 1 || max_steps < 1 || !scan_map_ok(Hm, Wm) || !scan_frame_ok(frame_w, frame_h)) return SP_EINVAL;
     const int64_t total = (int64_t)ngroups * (2 * Hm - 1) * (2 * Wm - 1);
     if (sp_cdiv(total, 256) > (int64_t)INT32_MAX) return SP_EINVAL;
     const CountArgs a{fix, start, count, group, ncol, nscan, ngroups, max_steps, Hm, Wm, frame_w, frame_h, (unsigned long long*)counts,
                       saccades, dropped};
-    hipLaunchKernelGGL(scan_saccade_zero_kernel, dim3((unsigned)sp_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a.counts, total);
+    hipLaunchKernelGGL(scan_zero_kernel<unsigned long long>, dim3((unsigned)sp_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a.counts, total);
     SP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_saccade_counts_kernel, dim3((unsigned)sp_cdiv(nscan, 4)), dim3(256), 0, (hipStream_t)stream, a);
     SP_LAUNCH_CHECK();
@@ -203,8 +175,7 @@ extern "C" int sp_scan_saccade_expectation(const float* probs, const int* row_gr
                                            void* stream) {
     if (!probs || !row_group) return SP_ENULL;
     if (!work || !E || !saccades || !bad) return SP_ENULL;
-    if (R < 1 || T < 1 || Hm < 1 || Wm < 1 || ngroups < 1 || min_length < 0 || max_steps < 1) return SP_EINVAL;
-    if ((int64_t)Hm * Wm > MAXCELLS) return SP_EINVAL;
+    if (R < 1 || T < 1 || !scan_map_ok(Hm, Wm) || ngroups < 1 || min_length < 0 || max_steps < 1) return SP_EINVAL;
     const int D = (2 * Hm - 1) * (2 * Wm - 1);                       // < 4 * MAXCELLS
     const int ntiles = (int)sp_cdiv(D, 256);
     if ((int64_t)R * ntiles > (int64_t)INT32_MAX || (int64_t)ngroups * ntiles > (int64_t)INT32_MAX) return SP_EINVAL;

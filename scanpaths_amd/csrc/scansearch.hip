@@ -21,11 +21,10 @@
 //     column and row by ballots over the Wm and Hm centre values (NaN compares false: no member).  cells = (r1 - r0) * (c1 - c0).  Every
 //     index into probs is built from these clamped ranges and from a box_row checked against R.
 //     Steps are taken in rounds of four, wave w of round k owns step t = 4 k + w.  THE ORDER OF EVERY SUM:
-//       Z_t   = the P cell values: lane l adds cells l, l + 64, l + 128, .. in that order from 0.0; the 64 partial sums combine by the xor
-//               butterfly 32, 16, 8, 4, 2, 1 (wave_sum_d) -- the order of scanlik.hip, a function of P alone;
+//       Z_t   = scan_step_mass of scan_common.h (the order of scansaccade.hip, scanturn.hip and scanlik.hip, a function of P alone);
 //       box_t = the box's cells numbered j = 0 .. cells - 1 in row-major order of the rectangle (cell (r0 + j / w, c0 + j % w), w = c1 -
 //               c0): lane l adds j = l, l + 64, .. in that order from 0.0; the same butterfly.  No sum crosses waves.
-//     D_t = Z_t + p0_t for t >= min_length, else Z_t;  q_t = p0_t / D_t for t >= min_length, else 0;  m_t = box_t / D_t.  Lane 0 of the
+//     (D_t, q_t) = scan_step_norm(Z_t, ..) of scan_common.h, on lane 0 only;  m_t = box_t / D_t.  Lane 0 of the
 //     wave leaves (m_t, q_t, D_t) in LDS (double-buffered by round: one barrier per round); thread 0 of the block then runs the recursion
 //     in step order: A_0 = 1, HIT_t = A_t * m_t, TFP_t = TFP_{t-1} + HIT_t (from 0.0, left to right), A_{t+1} = A_t * ((1 - q_t) - m_t);
 //     MASS_t = m_t.  D_t == 0, or a NaN in D_t, m_t or q_t, poisons the box: NaN in MASS, HIT and TFP at that step and every later one.
@@ -129,17 +128,14 @@ __global__ __launch_bounds__(256) void scan_target_mass_kernel(const MassArgs a)
         const int t = 4 * k + wave;
         if (t < a.T && row_ok) {                                    // wave-uniform
             const float* __restrict__ p = a.probs + ((int64_t)row * a.T + t) * (int64_t)(P + 1);
-            double z = 0.0, in = 0.0;
-            for (int c = lane; c < P; c += 64) z = z + (double)p[1 + c];
+            double in = 0.0;
             for (int j = lane; j < ncell; j += 64) in = in + (double)p[1 + (r0 + j / bw) * a.Wm + c0 + j % bw];
-            const double Z = wave_sum_d(z), B = wave_sum_d(in);
-            if (lane == 0) {
-                const bool stop = t >= a.min_length;
-                const double p0 = stop ? (double)p[0] : 0.0;
-                const double D = stop ? Z + p0 : Z;
-                sh[k & 1][wave][0] = B / D;
-                sh[k & 1][wave][1] = stop ? p0 / D : 0.0;
-                sh[k & 1][wave][2] = D;
+            const double Z = scan_step_mass(p, P, lane), B = wave_sum_d(in);
+            if (lane == 0) {                                        // a bad step poisons the box below: thread 0 reads it off D
+                const ScanStep st = scan_step_norm(Z, p, t >= a.min_length);
+                sh[k & 1][wave][0] = B / st.D;
+                sh[k & 1][wave][1] = st.q;
+                sh[k & 1][wave][2] = st.D;
             }
         }
         __syncthreads();                                            // round k is in LDS; round k - 1's slots (the other parity) are free
@@ -186,7 +182,7 @@ extern "C" int sp_scan_target_mass(const float* probs, const double* box, const 
     if (!MASS && !HIT && !TFP && !cells) return SP_ENULL;
     if (R < 1 || T < 1 || Hm < 1 || Wm < 1 || NB < 1 || min_length < 0) return SP_EINVAL;
     if (Hm > MAXSIDE || Wm > MAXSIDE) return SP_EINVAL;
-    if (!(frame_w > 0) || !(frame_w < INFINITY) || !(frame_h > 0) || !(frame_h < INFINITY)) return SP_EINVAL;
+    if (!scan_frame_ok(frame_w, frame_h)) return SP_EINVAL;
     const MassArgs a{probs, box, box_row, R, T, Hm, Wm, min_length, (float)(frame_w / Wm), (float)(frame_h / Hm), MASS, HIT, TFP, cells};
     hipLaunchKernelGGL(scan_target_mass_kernel, dim3((unsigned)NB), dim3(256), 0, (hipStream_t)stream, a);
     SP_LAUNCH_CHECK();

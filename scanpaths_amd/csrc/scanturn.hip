@@ -1,6 +1,6 @@
 // Turning angles: how the direction of a saccade depends on the direction of the saccade before it.  Fixations are read
 // as action-map cells (the pixel rule of scan_common.h), a saccade is a cell displacement, and every displacement has ONE direction
-// sector: the caller's table sector [D], D = (2 Hm - 1) (2 Wm - 1), entry (dr + Hm - 1) * (2 Wm - 1) + (dc + Wm - 1), values 0 .. n - 1 for
+// sector: the caller's table sector [D], D = (2 Hm - 1) (2 Wm - 1), entry scan_lattice_index(dr, dc) of scan_common.h, values 0 .. n - 1 for
 // the n direction sectors of §22 and n for the zero displacement ("stayed in the cell").  The table is built on the host by the float64
 // rule of §22 and only READ here: the device computes no atan2, so a vector on a sector boundary cannot land differently on the two sides
 // of a comparison.  A table value outside [0, n] is read as n (the index is clamped; what such a table counts is unspecified).  The
@@ -8,23 +8,21 @@
 // first saccade is in sector k and whose second is in sector k'.  float64, every operation rounded on its own (scan_common.h: contraction
 // OFF, plain operators).  E = (n + 1)^2, n <= MAXDIR = 16.
 //
-//   scan_turn_counts_kernel: scanpaths that exist (humans, samples).  ONE WAVEFRONT PER SCANPATH, four per block, one lane per fixation.
-//     Only the first m = min(n_fix, max_steps) fixations count; a fixation outside the frame or with a non-finite coordinate is dropped
-//     (counted in dropped); pair t counts iff fixations t, t + 1 and t + 2 are all kept -- nothing bridges a dropped fixation.  Lane t
-//     takes the cells and kept-flags of lanes t + 1 and t + 2 by shuffles, reads the two sectors and adds 1 to counts[group][k][k'] with
-//     an INTEGER atomic add on int64: integers, so the order in which the atomics land cannot change them.  scan_turn_zero_kernel zeroes
-//     counts first (a kernel, not a memset: common.h).  A count outside [0, MAXFIX] or a group outside [0, ngroups): pairs -1, dropped 0,
-//     none of its rows is read, nothing is counted.
+//   scan_turn_counts_kernel: scanpaths that exist (humans, samples).  ONE WAVEFRONT PER SCANPATH, four per block, one lane per fixation,
+//     read as a cell by scan_lane_cell (scan_common.h: which fixations count and which are dropped -- the code sp_scan_saccade_counts
+//     runs, so dropped agrees); pair t counts iff fixations t, t + 1 and t + 2 are all kept.  Lane t takes the cells and kept-flags of
+//     lanes t + 1 and t + 2 by shuffles, reads the two sectors and adds 1 to counts[group][k][k'] with an INTEGER atomic add on int64:
+//     integers, so the order in which the atomics land cannot change them.  scan_zero_kernel (scan_common.h) zeroes counts first.  A
+//     count outside [0, MAXFIX] or a group outside [0, ngroups): pairs -1, dropped 0, none of its rows is read, nothing is counted.
 //
 //   scan_turn_expect_kernel: the model, in closed form.  The step distributions are not conditioned on sampled fixations, so given the
 //     middle fixation b the incoming and the outgoing saccade are independent, and the expected count of (k, k') factorises per middle
 //     cell into two fans and an outer product.  ONE 256-THREAD BLOCK PER (row, t), t = 0 .. Tm - 3, Tm = min(T, max_steps) (one block per
 //     row when Tm < 3: it only decides bad).  THE ORDER OF EVERY SUM:
-//       Z_s    = the P cell values of step s: lane l adds cells l, l + 64, .. in that order from 0.0, the 64 partial sums combine by the
-//                xor butterfly 32 .. 1 (wave_sum_d): the order of scansaccade.hip, so bad rows agree with sp_scan_saccade_expectation.
-//                Every wave of the block recomputes Z_0 .. Z_{t+2} for itself (the same bits), so nothing is passed between waves and
-//                every exit is block-uniform;
-//       D_s = Z_s + p0_s for s >= min_length, else Z_s;  q_s = p0_s / D_s for s >= min_length, else 0;  c_s(i) = (double)p_s[1 + i] / D_s;
+//       Z_s, D_s, q_s = the step normalisation of scan_common.h (scan_step_mass, scan_step_norm): the code sp_scan_saccade_expectation
+//                runs, so bad rows agree.  Every wave of the block recomputes steps 0 .. t + 2 for itself (the same bits), so nothing
+//                is passed between waves and every exit is block-uniform;
+//       c_s(i) = (double)p_s[1 + i] / D_s;
 //       A_0 = 1, A_{s+1} = A_s * (1.0 - q_s);
 //       in_t[b][k]   = sum over the cells a with sector(b - a) = k  of c_t(a),     a in ASCENDING ROW-MAJOR order from 0.0;
 //       out_t[b][k'] = sum over the cells a with sector(a - b) = k' of c_{t+2}(a), likewise;
@@ -36,7 +34,7 @@
 //     table as bytes.  For a batch of 256 middle cells, thread j owns cell b0 + j and walks all source cells a, adding into its own bins;
 //     after a barrier thread p (p, p + 256 < E) owns one (k, k') and adds the batch's b in ascending order into an accumulator it keeps
 //     across batches, so the b order is ascending overall.
-//     A row is BAD iff some D_s with s < Tm is zero or not finite: the block of t = Tm - 3 walks every step, so it writes bad 1 and pairs
+//     A row is BAD iff some step s < Tm is bad (scan_step_norm): the block of t = Tm - 3 walks every step, so it writes bad 1 and pairs
 //     NaN; a block that meets the bad step leaves (its slice of work stays unwritten and is never read).  row_group outside [0, ngroups):
 //     bad -1, pairs NaN, nothing of the row is read.  Tm < 3: no pair, M and pairs 0 (a bad D_s, s < Tm, still makes the row bad).
 //   scan_turn_rows_kernel: one thread per (row, entry): M_r = sum_t work[r][t] in ASCENDING t from 0.0, left in work[r][0].
@@ -47,13 +45,7 @@
 
 namespace {
 
-constexpr int MAXCELLS = 2048;    // = sp_scan_likelihood_max_cells()
 constexpr int MAXDIR = 16;        // = sp_scan_turn_max_directions(): 2 * 17 * 256 doubles of bins + three maps + the table stay under 160 KB
-
-__global__ __launch_bounds__(256) void scan_turn_zero_kernel(unsigned long long* __restrict__ p, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) p[i] = 0ull;
-}
 
 // a table value outside [0, n] is read as n
 __device__ __forceinline__ int turn_sector(int v, int n) { return (unsigned)v > (unsigned)n ? n : v; }
@@ -75,27 +67,16 @@ __global__ __launch_bounds__(256) void scan_turn_counts_kernel(const CountArgs a
     const int n = a.count[s], g = a.group[s];
     int np = -1, nd = 0;
     if (!scan_count_bad(n) && g >= 0 && g < a.ngroups) {              // wave-uniform
-        const int m = min(n, a.max_steps);
-        bool kept = false;
-        int row = 0, col = 0;
-        if (lane < m) {
-            const double* __restrict__ f = a.fix + (a.start[s] + lane) * a.ncol;
-            const double x = f[0], y = f[1];
-            kept = scan_in_frame(x, y, a.frame_w, a.frame_h);
-            if (kept) {
-                col = scan_cell(x, a.Wm, a.frame_w);
-                row = scan_cell(y, a.Hm, a.frame_h);
-            }
-        }
-        nd = __popcll(__ballot(lane < m && !kept));
-        const int r1 = __shfl_down(row, 1, 64), c1 = __shfl_down(col, 1, 64), k1 = __shfl_down((int)kept, 1, 64);
-        const int r2 = __shfl_down(row, 2, 64), c2 = __shfl_down(col, 2, 64), k2 = __shfl_down((int)kept, 2, 64);
-        const bool pair = lane + 2 < m && kept && k1 != 0 && k2 != 0;  // m <= 64: lanes 62 and 63 never have two successors
+        const ScanLaneCell f = scan_lane_cell(a.fix, a.ncol, a.start, s, n, a.max_steps, lane, a.Hm, a.Wm, a.frame_w, a.frame_h);
+        nd = f.dropped;
+        const int r1 = __shfl_down(f.row, 1, 64), c1 = __shfl_down(f.col, 1, 64), k1 = __shfl_down((int)f.kept, 1, 64);
+        const int r2 = __shfl_down(f.row, 2, 64), c2 = __shfl_down(f.col, 2, 64), k2 = __shfl_down((int)f.kept, 2, 64);
+        const bool pair = lane + 2 < f.m && f.kept && k1 != 0 && k2 != 0;   // m <= 64: lanes 62 and 63 never have two successors
         np = __popcll(__ballot(pair));
         if (pair) {
-            const int LW = 2 * a.Wm - 1, E1 = a.ndir + 1;
-            const int k = turn_sector(a.sector[(r1 - row + a.Hm - 1) * LW + (c1 - col + a.Wm - 1)], a.ndir);
-            const int kk = turn_sector(a.sector[(r2 - r1 + a.Hm - 1) * LW + (c2 - c1 + a.Wm - 1)], a.ndir);
+            const int E1 = a.ndir + 1;
+            const int k = turn_sector(a.sector[scan_lattice_index(r1 - f.row, c1 - f.col, a.Hm, a.Wm)], a.ndir);
+            const int kk = turn_sector(a.sector[scan_lattice_index(r2 - r1, c2 - c1, a.Hm, a.Wm)], a.ndir);
             atomicAdd(a.counts + (int64_t)g * (E1 * E1) + k * E1 + kk, 1ull);
         }
     }
@@ -133,20 +114,15 @@ __global__ __launch_bounds__(256) void scan_turn_expect_kernel(const ExpArgs a) 
     double A = 1.0, At = 1.0, Am1 = 1.0, Am2 = 1.0, qm1 = 0.0, qm2 = 0.0, pr = 0.0, Dm[3] = {1.0, 1.0, 1.0};
     for (int s = 0; s <= last; ++s) {                               // A = A_s on entry
         const float* __restrict__ p = prow + (int64_t)s * (P + 1);
-        double z = 0.0;
-        for (int c = lane; c < P; c += 64) z = z + (double)p[1 + c];
-        const double Z = wave_sum_d(z);
-        const bool stop = s >= a.min_length;
-        const double p0 = stop ? (double)p[0] : 0.0;
-        const double Ds = stop ? Z + p0 : Z;
-        if (Ds == 0.0 || !isfinite(Ds)) {                           // the same bits in every wave: a block-uniform exit
+        const ScanStep st = scan_step_norm(scan_step_mass(p, P, lane), p, s >= a.min_length);
+        if (st.bad) {                                               // the same bits in every wave: a block-uniform exit
             if (writer) {
                 a.bad[r] = 1;
                 a.pairs[r] = nan;
             }
             return;
         }
-        const double q = stop ? p0 / Ds : 0.0;
+        const double Ds = st.D, q = st.q;
         if (s >= 2) pr = pr + Am2 * (((1.0 - qm2) * (1.0 - qm1)) * (1.0 - q));
         if (s == t) At = A;
         if (s == t) Dm[0] = Ds;
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(256) void scan_turn_expect_kernel(const ExpArgs a) 
         }
         if (b < P) {
             // sector(b - a) sits at base - (ra * LW + ca), sector(a - b) at its mirror image D - 1 - that
-            int idx = (b / a.Wm + a.Hm - 1) * LW + (b % a.Wm + a.Wm - 1);
+            int idx = scan_lattice_index(b / a.Wm, b % a.Wm, a.Hm, a.Wm);
             const double* __restrict__ ct = cm;
             const double* __restrict__ ct2 = cm + 2 * P;
             for (int ra = 0; ra < a.Hm; ++ra, idx -= LW) {
@@ -252,15 +228,13 @@ extern "C" int sp_scan_turn_counts(const double* fix, int ncol, const int64_t* s
                                    int n_directions, int64_t* counts, int* pairs, int* dropped, void* stream) {
     if (!fix || !start || !count || !group || !sector) return SP_ENULL;
     if (!counts || !pairs || !dropped) return SP_ENULL;
-    if (ncol < 2 || nscan < 1 || ngroups < 1 || max_steps < 1 || Hm < 1 || Wm < 1) return SP_EINVAL;
-    if ((int64_t)Hm * Wm > MAXCELLS) return SP_EINVAL;
-    if (!(frame_w > 0) || !(frame_w < INFINITY) || !(frame_h > 0) || !(frame_h < INFINITY)) return SP_EINVAL;
+    if (ncol < 2 || nscan < 1 || ngroups < 1 || max_steps < 1 || !scan_map_ok(Hm, Wm) || !scan_frame_ok(frame_w, frame_h)) return SP_EINVAL;
     if (n_directions < 1 || n_directions > MAXDIR) return SP_EINVAL;
     const int64_t total = (int64_t)ngroups * (n_directions + 1) * (n_directions + 1);
     if (sp_cdiv(total, 256) > (int64_t)INT32_MAX) return SP_EINVAL;
     const CountArgs a{fix, start, count, group, sector, ncol, nscan, ngroups, max_steps, Hm, Wm, n_directions, frame_w, frame_h,
                       (unsigned long long*)counts, pairs, dropped};
-    hipLaunchKernelGGL(scan_turn_zero_kernel, dim3((unsigned)sp_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a.counts, total);
+    hipLaunchKernelGGL(scan_zero_kernel<unsigned long long>, dim3((unsigned)sp_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, a.counts, total);
     SP_LAUNCH_CHECK();
     hipLaunchKernelGGL(scan_turn_counts_kernel, dim3((unsigned)sp_cdiv(nscan, 4)), dim3(256), 0, (hipStream_t)stream, a);
     SP_LAUNCH_CHECK();
@@ -272,8 +246,7 @@ extern "C" int sp_scan_turn_expectation(const float* probs, const int* row_group
                                         double* pairs, int* bad, void* stream) {
     if (!probs || !row_group || !sector) return SP_ENULL;
     if (!work || !M || !pairs || !bad) return SP_ENULL;
-    if (R < 1 || T < 1 || Hm < 1 || Wm < 1 || ngroups < 1 || min_length < 0 || max_steps < 1) return SP_EINVAL;
-    if ((int64_t)Hm * Wm > MAXCELLS) return SP_EINVAL;
+    if (R < 1 || T < 1 || !scan_map_ok(Hm, Wm) || ngroups < 1 || min_length < 0 || max_steps < 1) return SP_EINVAL;
     if (n_directions < 1 || n_directions > MAXDIR) return SP_EINVAL;
     const int Tm = T < max_steps ? T : max_steps, nT = Tm < 3 ? 1 : Tm - 2;
     const int P = Hm * Wm, D = (2 * Hm - 1) * (2 * Wm - 1), E1 = n_directions + 1, E = E1 * E1;

@@ -161,22 +161,16 @@ def run_saccade_statistics_loop(model, loader: Iterable[dict], *, min_length, ma
     n_directions have no defaults; human_lattice (optional, utils.evaluation.saccade_statistics_human_evaluation's
     "human_lattice_sum"): for the four comparison numbers.  map_shape defaults to (30, 40) for 1201 actions only.
     Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.SaccadeStatisticsTable."""
-    from .utils.evaltools.saccade_statistics import _check_directions, _check_edges
+    from .utils.evaltools._args import check_directions, check_edges
     from .utils.evaluation import SaccadeStatisticsTable, saccade_statistics_model_evaluation
-    amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
-    table, per_batch = None, []
-    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
-        means, per_key = saccade_statistics_model_evaluation(
-            predict, batch["question_ids"], min_length=min_length, max_steps=max_steps,
-            performances=_performances(batch, predict), frame_size=frame_size, map_shape=map_shape)
-        if table is None:
-            LH, LW = means["lattice_sum"].shape
-            table = SaccadeStatisticsTable(frame_size, ((LH + 1) // 2, (LW + 1) // 2), amplitude_edges, n_directions)
-        table.add(means)
-        per_batch.append(per_key)
-    if table is None:
-        raise ValueError("the loader yielded no batch")
-    return table.result(human_lattice), per_batch
+    amplitude_edges, n_directions = check_edges(amplitude_edges), check_directions(n_directions)
+
+    def table(means):                                           # sized from the first batch's lattice
+        LH, LW = means["lattice_sum"].shape
+        return SaccadeStatisticsTable(frame_size, ((LH + 1) // 2, (LW + 1) // 2), amplitude_edges, n_directions)
+
+    return _statistics_loop(model, loader, ablate_attention_info, table, human_lattice, saccade_statistics_model_evaluation,
+                            min_length=min_length, max_steps=max_steps, frame_size=frame_size, map_shape=map_shape)
 
 
 @torch.no_grad()
@@ -190,13 +184,21 @@ def run_turn_statistics_loop(model, loader: Iterable[dict], *, min_length, max_s
     map_shape defaults to (30, 40) for 1201 actions only.
     Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.TurnStatisticsTable."""
     from .utils.evaluation import TurnStatisticsTable, turn_statistics_model_evaluation
-    table, per_batch = TurnStatisticsTable(n_directions), []
+    table = TurnStatisticsTable(n_directions)
+    return _statistics_loop(model, loader, ablate_attention_info, lambda means: table, human_table, turn_statistics_model_evaluation,
+                            min_length=min_length, max_steps=max_steps, n_directions=n_directions, frame_size=frame_size,
+                            map_shape=map_shape)
+
+
+def _statistics_loop(model, loader, ablate_attention_info, make_table, human, evaluate, **kw):
+    """the two loops above: evaluate(predict, keys, performances=..., **kw) per batch, merged by make_table(the first batch's means)
+    and read against human; a loader without a batch is an error"""
+    table, per_batch = None, []
     for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
-        means, per_key = turn_statistics_model_evaluation(
-            predict, batch["question_ids"], min_length=min_length, max_steps=max_steps, n_directions=n_directions,
-            performances=_performances(batch, predict), frame_size=frame_size, map_shape=map_shape)
+        means, per_key = evaluate(predict, batch["question_ids"], performances=_performances(batch, predict), **kw)
+        table = make_table(means) if table is None else table
         table.add(means)
         per_batch.append(per_key)
-    if not per_batch:
+    if table is None:
         raise ValueError("the loader yielded no batch")
-    return table.result(human_table), per_batch
+    return table.result(human), per_batch

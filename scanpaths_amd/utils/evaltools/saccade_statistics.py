@@ -36,12 +36,10 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from ... import hip
-from ...hip import check, ptr
 from . import _batch
-from ._args import check_frame, check_map, check_min_length, check_steps, rows
-from ._batch import MAX_FIXATIONS, check_index, pack  # noqa: F401  (MAX_FIXATIONS re-exported)
-from .scanpath_likelihood import MAX_CELLS
+from ._args import MAX_CELLS, check_directions, check_edges, check_frame, check_map, check_map_shape, check_min_length, check_probs, check_steps
+from ._batch import MAX_FIXATIONS  # noqa: F401  (re-exported)
+from ._grouped import grouped_counts, grouped_expectation
 
 
 def _device() -> torch.device:
@@ -49,43 +47,6 @@ def _device() -> torch.device:
 
 
 # ---- argument checks: every refusal comes before the device or the library is touched ---------------------------------------------------
-def _check_shape(map_shape) -> Tuple[int, int]:
-    try:
-        Hm, Wm = (int(v) for v in map_shape)
-        exact = all(int(v) == v for v in map_shape)
-    except (TypeError, ValueError):
-        raise ValueError(f"map_shape {map_shape!r}: (Hm, Wm), two integers >= 1, is required") from None
-    if not exact or Hm < 1 or Wm < 1:
-        raise ValueError(f"map_shape {tuple(map_shape)}: (Hm, Wm), two integers >= 1, is required")
-    if Hm * Wm > MAX_CELLS:
-        raise ValueError(f"map_shape {tuple(map_shape)}: a map of {Hm * Wm} cells exceeds the kernel limit {MAX_CELLS}")
-    return Hm, Wm
-
-
-def _check_groups(groups, n, n_groups, what) -> Tuple[np.ndarray, int]:
-    if n_groups is None or isinstance(n_groups, bool) or int(n_groups) != n_groups or int(n_groups) < 1:
-        raise ValueError(f"n_groups {n_groups!r}: an integer >= 1")
-    g = check_index(groups, int(n_groups), "group").reshape(-1)
-    if len(g) != n:
-        raise ValueError(f"one group per {what} is required: {len(g)} groups, {n} {what}s")
-    return g.astype(np.int32), int(n_groups)
-
-
-def _check_edges(amplitude_edges) -> np.ndarray:
-    if amplitude_edges is None:
-        raise ValueError("amplitude_edges is required: at least two increasing finite values, in pixels")
-    e = np.asarray(amplitude_edges, dtype=np.float64).reshape(-1)
-    if len(e) < 2 or not np.isfinite(e).all() or not (np.diff(e) > 0).all():
-        raise ValueError(f"amplitude_edges {e.tolist()}: at least two strictly increasing finite values are required")
-    return e
-
-
-def _check_directions(n_directions) -> int:
-    if n_directions is None or isinstance(n_directions, bool) or int(n_directions) != n_directions or int(n_directions) < 1:
-        raise ValueError(f"n_directions {n_directions!r}: an integer >= 1")
-    return int(n_directions)
-
-
 def _check_lattice(lattice) -> Tuple[np.ndarray, int, int]:
     a = np.asarray(lattice)
     if a.ndim != 2 or a.shape[0] % 2 != 1 or a.shape[1] % 2 != 1:
@@ -99,23 +60,9 @@ def saccade_counts(scanpaths, groups, n_groups, frame_size, map_shape, *, max_st
     scanpath is counted into (an empty group stays zero); frame_size = (height, width); map_shape = (Hm, Wm), at most 2048 cells.
     Returns {"counts": int64 [n_groups, 2 Hm - 1, 2 Wm - 1], "saccades": int32 [S], "dropped": int32 [S]} (module docstring)."""
     max_steps = check_steps(max_steps)
-    Hm, Wm = _check_shape(map_shape)
-    fh, fw = check_frame(frame_size)
-    b = pack([rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
-    S = len(b.counts)
-    grp, G = _check_groups(groups, S, n_groups, "scanpath")
-    LH, LW = 2 * Hm - 1, 2 * Wm - 1
-    if S == 0:
-        return {"counts": np.zeros((G, LH, LW), np.int64), "saccades": np.zeros(0, np.int32), "dropped": np.zeros(0, np.int32)}
-    dev = _device()
-    L = hip.lib()
-    _batch.check_limits(L)
-    buf, at = _batch.upload(b.sections(group=grp), dev)
-    out = _batch.Out({"counts": (np.int64, G * LH * LW), "saccades": (np.int32, S), "dropped": (np.int32, S)}, dev)
-    check(L.sp_scan_saccade_counts(at["rows"], b.ncol, at["starts"], at["counts"], at["group"], S, G, max_steps, Hm, Wm, fw, fh,
-                                   out.ptr("counts"), out.ptr("saccades"), out.ptr("dropped"), hip.stream()), "sp_scan_saccade_counts")
-    host = out.host()
-    return {"counts": host["counts"].reshape(G, LH, LW), "saccades": host["saccades"], "dropped": host["dropped"]}
+    Hm, Wm = check_map_shape(map_shape)
+    return grouped_counts("sp_scan_saccade_counts", _device, scanpaths, groups, n_groups, check_frame(frame_size), (Hm, Wm), max_steps,
+                          shape=(2 * Hm - 1, 2 * Wm - 1), unit="saccades")
 
 
 def saccade_expectation(probs, row_groups, n_groups, *, min_length, max_steps, map_shape=None) -> Dict[str, np.ndarray]:
@@ -124,31 +71,18 @@ def saccade_expectation(probs, row_groups, n_groups, *, min_length, max_steps, m
     count (required); map_shape = (Hm, Wm) defaults to (30, 40) for 1201 actions only.
     Returns {"E": float64 [n_groups, 2 Hm - 1, 2 Wm - 1], "saccades": float64 [R], "bad": int32 [R]} (module docstring)."""
     min_length, max_steps = check_min_length(min_length), check_steps(max_steps)
-    if not isinstance(probs, torch.Tensor) or probs.dim() != 3 or min(probs.shape) < 1:
-        raise ValueError("probs: a non-empty [R, T, A] tensor is required")
-    R, T, A = (int(v) for v in probs.shape)
+    R, _, A = check_probs(probs)
     Hm, Wm = check_map(A, map_shape, max_cells=MAX_CELLS)
-    grp, G = _check_groups(row_groups, R, n_groups, "row")
-    LH, LW = 2 * Hm - 1, 2 * Wm - 1
-    dev = _device()
-    L = hip.lib()
-    if L.sp_scan_likelihood_max_cells() != MAX_CELLS:
-        raise hip.HipError(f"sp_scan_likelihood_max_cells() = {L.sp_scan_likelihood_max_cells()}, this module expects {MAX_CELLS}")
-    buf, at = _batch.upload({"row_group": grp}, dev)
-    p = probs.detach().to(torch.float32).contiguous()
-    work = torch.empty(R * LH * LW, dtype=torch.float64, device=dev)
-    out = _batch.Out({"E": (np.float64, G * LH * LW), "saccades": (np.float64, R), "bad": (np.int32, R)}, dev)
-    check(L.sp_scan_saccade_expectation(ptr(p), at["row_group"], R, T, Hm, Wm, G, min_length, max_steps, ptr(work), out.ptr("E"),
-                                        out.ptr("saccades"), out.ptr("bad"), hip.stream()), "sp_scan_saccade_expectation")
-    host = out.host()
-    return {"E": host["E"].reshape(G, LH, LW), "saccades": host["saccades"], "bad": host["bad"]}
+    shape = (2 * Hm - 1, 2 * Wm - 1)
+    return grouped_expectation("sp_scan_saccade_expectation", _device, probs, (Hm, Wm), row_groups, n_groups, min_length, max_steps,
+                               shape=shape, work=R * shape[0] * shape[1], name="E", unit="saccades")
 
 
 # ---- pure numpy, on one lattice -----------------------------------------------------------------------------------------------------------
 def lattice_vectors(map_shape, frame_size) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """(dx, dy, amplitude), each float64 [2 Hm - 1, 2 Wm - 1]: the pixel displacement of every lattice entry, dx = dc * frame_w / Wm and
     dy = dr * frame_h / Hm (y pointing down, as stored), and its length sqrt(dx * dx + dy * dy)"""
-    Hm, Wm = _check_shape(map_shape)
+    Hm, Wm = check_map_shape(map_shape)
     fh, fw = check_frame(frame_size)
     dy = np.arange(-(Hm - 1), Hm, dtype=np.float64) * fh / Hm
     dx = np.arange(-(Wm - 1), Wm, dtype=np.float64) * fw / Wm
@@ -161,7 +95,7 @@ def direction_sectors(map_shape, frame_size, n_directions) -> np.ndarray:
     the angle 2 pi k / n of atan2(dy, dx): k = int(floor(atan2(dy, dx) * n / (2 pi) + 0.5)) mod n, evaluated in that order in float64 --
     so a vector exactly on the boundary between sectors k and k + 1 (the expression is k + 1 exactly) belongs to sector k + 1, the one
     at the larger angle (with y pointing down: clockwise on the screen)."""
-    n = _check_directions(n_directions)
+    n = check_directions(n_directions)
     dx, dy, _ = lattice_vectors(map_shape, frame_size)
     k = np.floor(np.arctan2(dy, dx) * n / (2 * np.pi) + 0.5).astype(np.int64) % n
     k[(dx == 0) & (dy == 0)] = -1
@@ -177,7 +111,7 @@ def saccade_summary(lattice, frame_size, *, amplitude_edges, n_directions) -> di
       "direction_hist" float64 [n_directions]: the share, among the NON-ZERO displacements, of every sector of direction_sectors -- a
       vector exactly on a sector boundary goes to floor(atan2(dy, dx) * n / (2 pi) + 0.5) mod n, the sector at the larger angle.
     Shares of an empty lattice (and direction shares of a stay-only one) are NaN."""
-    edges, n = _check_edges(amplitude_edges), _check_directions(n_directions)
+    edges, n = check_edges(amplitude_edges), check_directions(n_directions)
     a, Hm, Wm = _check_lattice(lattice)
     fh, fw = check_frame(frame_size)
     _, _, amp = lattice_vectors((Hm, Wm), (fh, fw))

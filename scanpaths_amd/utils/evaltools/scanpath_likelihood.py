@@ -37,11 +37,10 @@ import torch
 from ... import hip
 from ...hip import check, ptr
 from . import _batch
-from ._args import check_frame, check_map, rows as _rows  # (rows is an argument of scanpath_likelihood)
+from ._args import MAX_CELLS, check_frame, check_map, rows as _rows  # (rows is an argument of scanpath_likelihood)
 from ._batch import MAX_FIXATIONS, check_index, pack, starts  # noqa: F401  (MAX_FIXATIONS re-exported)
 
 METRICS = ("LL", "IG", "NSS", "AUC", "DLL", "STOP")
-MAX_CELLS = 2048            # = sp_scan_likelihood_max_cells(), known here so that a refusal needs no library (held equal by the tests)
 _PER_FIXATION = METRICS[:5]
 
 

@@ -36,45 +36,28 @@ from typing import Dict
 import numpy as np
 import torch
 
-from ... import hip
-from ...hip import check, ptr
 from . import _batch
-from ._args import check_frame, check_map, check_min_length, check_steps, rows
-from ._batch import MAX_FIXATIONS, pack  # noqa: F401  (MAX_FIXATIONS re-exported)
-from .saccade_statistics import _check_directions, _check_groups, _check_shape, direction_sectors, jensen_shannon
-from .scanpath_likelihood import MAX_CELLS
-
-MAX_DIRECTIONS = 16         # = sp_scan_turn_max_directions(): two bin arrays [n + 1][256] in double next to three maps in 160 KB of LDS
+from ._args import MAX_CELLS, MAX_DIRECTIONS, check_directions, check_frame, check_map, check_map_shape, check_min_length, check_probs, check_steps
+from ._batch import MAX_FIXATIONS  # noqa: F401  (re-exported)
+from ._grouped import grouped_counts, grouped_expectation
+from .saccade_statistics import direction_sectors, jensen_shannon
 
 
 def _device() -> torch.device:
     return _batch.device("turn statistics run")
 
 
-def _check_n(n_directions) -> int:
-    n = _check_directions(n_directions)
-    if n > MAX_DIRECTIONS:
-        raise ValueError(f"n_directions {n}: exceeds the kernel limit {MAX_DIRECTIONS}")
-    return n
-
-
-def _check_table(table) -> np.ndarray:
+def check_table(table) -> np.ndarray:
     a = np.asarray(table)
     if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 2:
         raise ValueError(f"a transition table is an [n + 1, n + 1] array with n >= 1, got shape {a.shape}")
     return a.astype(np.float64)
 
 
-def _library(L):
-    if L.sp_scan_likelihood_max_cells() != MAX_CELLS or L.sp_scan_turn_max_directions() != MAX_DIRECTIONS:
-        raise hip.HipError(f"kernel limits {L.sp_scan_likelihood_max_cells()} / {L.sp_scan_turn_max_directions()}, this module expects "
-                           f"{MAX_CELLS} / {MAX_DIRECTIONS}")
-
-
 def turn_sectors(map_shape, frame_size, n_directions) -> np.ndarray:
     """int32 [2 Hm - 1, 2 Wm - 1]: direction_sectors(map_shape, frame_size, n_directions) with the zero displacement as sector
     n_directions ("stayed in the cell") instead of -1 -- the table both kernels read"""
-    n = _check_n(n_directions)
+    n = check_directions(n_directions, MAX_DIRECTIONS)
     k = direction_sectors(map_shape, frame_size, n)
     k[k < 0] = n
     return np.ascontiguousarray(k, dtype=np.int32)
@@ -85,25 +68,10 @@ def turn_counts(scanpaths, groups, n_groups, frame_size, map_shape, *, max_steps
     """scanpaths: S arrays [n <= 64, >= 2] of (x, y, ...) or structured fixation vectors; groups [S] in [0, n_groups): the table each
     scanpath is counted into (an empty group stays zero); frame_size = (height, width); map_shape = (Hm, Wm), at most 2048 cells.
     Returns {"counts": int64 [n_groups, n + 1, n + 1], "pairs": int32 [S], "dropped": int32 [S]} (module docstring)."""
-    max_steps, n = check_steps(max_steps), _check_n(n_directions)
-    Hm, Wm = _check_shape(map_shape)
-    fh, fw = check_frame(frame_size)
-    b = pack([rows(sp)[:, :2] for sp in scanpaths], min_cols=2)
-    S = len(b.counts)
-    grp, G = _check_groups(groups, S, n_groups, "scanpath")
-    if S == 0:
-        return {"counts": np.zeros((G, n + 1, n + 1), np.int64), "pairs": np.zeros(0, np.int32), "dropped": np.zeros(0, np.int32)}
-    sector = turn_sectors((Hm, Wm), (fh, fw), n)
-    dev = _device()
-    L = hip.lib()
-    _batch.check_limits(L)
-    _library(L)
-    buf, at = _batch.upload(b.sections(group=grp, sector=sector), dev)
-    out = _batch.Out({"counts": (np.int64, G * (n + 1) * (n + 1)), "pairs": (np.int32, S), "dropped": (np.int32, S)}, dev)
-    check(L.sp_scan_turn_counts(at["rows"], b.ncol, at["starts"], at["counts"], at["group"], S, G, max_steps, Hm, Wm, fw, fh, at["sector"],
-                                n, out.ptr("counts"), out.ptr("pairs"), out.ptr("dropped"), hip.stream()), "sp_scan_turn_counts")
-    host = out.host()
-    return {"counts": host["counts"].reshape(G, n + 1, n + 1), "pairs": host["pairs"], "dropped": host["dropped"]}
+    max_steps, n = check_steps(max_steps), check_directions(n_directions, MAX_DIRECTIONS)
+    shape, frame = check_map_shape(map_shape), check_frame(frame_size)
+    return grouped_counts("sp_scan_turn_counts", _device, scanpaths, groups, n_groups, frame, shape, max_steps, shape=(n + 1, n + 1),
+                          unit="pairs", tables=lambda: {"sector": turn_sectors(shape, frame, n)}, scalars=(n,))
 
 
 def turn_expectation(probs, row_groups, n_groups, *, min_length, max_steps, frame_size, n_directions, map_shape=None) -> Dict[str, np.ndarray]:
@@ -112,26 +80,13 @@ def turn_expectation(probs, row_groups, n_groups, *, min_length, max_steps, fram
     frame_size = (height, width): the sectors are directions in pixels; n_directions <= 16 (all four required); map_shape = (Hm, Wm)
     defaults to (30, 40) for 1201 actions only.
     Returns {"M": float64 [n_groups, n + 1, n + 1], "pairs": float64 [R], "bad": int32 [R]} (module docstring)."""
-    min_length, max_steps, n = check_min_length(min_length), check_steps(max_steps), _check_n(n_directions)
-    fh, fw = check_frame(frame_size)
-    if not isinstance(probs, torch.Tensor) or probs.dim() != 3 or min(probs.shape) < 1:
-        raise ValueError("probs: a non-empty [R, T, A] tensor is required")
-    R, T, A = (int(v) for v in probs.shape)
-    Hm, Wm = check_map(A, map_shape, max_cells=MAX_CELLS)
-    grp, G = _check_groups(row_groups, R, n_groups, "row")
-    sector = turn_sectors((Hm, Wm), (fh, fw), n)
-    E = (n + 1) * (n + 1)
-    dev = _device()
-    L = hip.lib()
-    _library(L)
-    buf, at = _batch.upload({"row_group": grp, "sector": sector}, dev)
-    p = probs.detach().to(torch.float32).contiguous()
-    work = torch.empty(R * max(min(T, max_steps) - 2, 1) * E, dtype=torch.float64, device=dev)
-    out = _batch.Out({"M": (np.float64, G * E), "pairs": (np.float64, R), "bad": (np.int32, R)}, dev)
-    check(L.sp_scan_turn_expectation(ptr(p), at["row_group"], R, T, Hm, Wm, G, min_length, max_steps, at["sector"], n, ptr(work),
-                                     out.ptr("M"), out.ptr("pairs"), out.ptr("bad"), hip.stream()), "sp_scan_turn_expectation")
-    host = out.host()
-    return {"M": host["M"].reshape(G, n + 1, n + 1), "pairs": host["pairs"], "bad": host["bad"]}
+    min_length, max_steps, n = check_min_length(min_length), check_steps(max_steps), check_directions(n_directions, MAX_DIRECTIONS)
+    frame = check_frame(frame_size)
+    R, T, A = check_probs(probs)
+    shape = check_map(A, map_shape, max_cells=MAX_CELLS)
+    return grouped_expectation("sp_scan_turn_expectation", _device, probs, shape, row_groups, n_groups, min_length, max_steps,
+                               shape=(n + 1, n + 1), work=R * max(min(T, max_steps) - 2, 1) * (n + 1) * (n + 1), name="M", unit="pairs",
+                               tables=lambda: {"sector": turn_sectors(shape, frame, n)}, scalars=(n,))
 
 
 # ---- pure numpy, on one transition table ---------------------------------------------------------------------------------------------------
@@ -144,7 +99,7 @@ def turn_summary(table) -> dict:
       "stay_then_stay": the shares of total of table[n, :n], table[:n, n] and table[n, n];  "transition" float64 [n, n] =
       table[:n, :n] / moving.
     Shares of an empty table, or of an empty moving part, are NaN."""
-    a = _check_table(table)
+    a = check_table(table)
     n = a.shape[0] - 1
     total, core = float(a.sum()), a[:n, :n]
     moving = float(core.sum())
@@ -165,7 +120,7 @@ def turn_summary(table) -> dict:
 def turn_comparison(table, human_table) -> dict:
     """The two comparison numbers of a transition table against the human one, in bits (jensen_shannon): "JSD_turn" between the
     turning-angle histograms and "JSD_transition" between the moving parts table[:n, :n], entry by entry"""
-    a, h = _check_table(table), _check_table(human_table)
+    a, h = check_table(table), check_table(human_table)
     if a.shape != h.shape:
         raise ValueError(f"tables of shapes {a.shape} and {h.shape}: one shape is required")
     n = a.shape[0] - 1

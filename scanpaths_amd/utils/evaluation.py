@@ -22,11 +22,13 @@
   Bootstrap: bootstrap_evaluation / bootstrap_comparison / bootstrap_information_gain_explained put intervals on any per_key table."""
 from __future__ import annotations
 
+from collections import namedtuple
 from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from .evaltools._args import check_frame, check_map, check_min_length, check_steps
+from .evaltools._args import (MAX_CELLS, MAX_DIRECTIONS, check_directions, check_edges, check_frame, check_map, check_map_shape, check_min_length,
+                              check_steps)
 
 
 def _as_ms(fv) -> np.ndarray:
@@ -1085,7 +1087,7 @@ class SearchEfficiencyTable(_SumTable):
         return out
 
 
-# ---- saccade statistics (evaltools/saccade_statistics.py, csrc/scansaccade.hip) ------------------------------------------
+# ---- saccade statistics and turning angles: one array per group, counted or expected --------------------------------
 def _group_labels(index, groups):
     """groups: key -> label (a task, ...) or None -> (labels in first-appearance order, label index of every key of the index); a key
     without a label is an error, not a silent drop"""
@@ -1099,30 +1101,112 @@ def _group_labels(index, groups):
     return list(labels), of_key
 
 
-def _saccade_derived(parts, frame_size, amplitude_edges, n_directions, human_lattice=None):
-    """the summed entries of one group (the "_sum" / "_count" / "_bad" / "_dropped" entries) -> the same with "summary" /
-    "human_summary" and, against human_lattice (default: the group's own "human_lattice_sum"), the four comparison numbers"""
-    from .evaltools.saccade_statistics import saccade_comparison, saccade_summary
-    kw = dict(amplitude_edges=amplitude_edges, n_directions=n_directions)
+# a statistic: evaltools.<name>_statistics, the entry names of its array and of what a scanpath or row adds, the expectation's result key
+_Statistic = namedtuple("_Statistic", "name array unit expected")
+_SACCADES, _TURNS = _Statistic("saccade", "lattice", "saccades", "E"), _Statistic("turn", "table", "pairs", "M")
+
+
+def _tool(stat, what):
+    """evaltools.<name>_statistics.<name>_<what> (counts, expectation, summary, comparison), looked up at the call: a test may replace it"""
+    from importlib import import_module
+    return getattr(import_module(f"{__package__}.evaltools.{stat.name}_statistics"), f"{stat.name}_{what}")
+
+
+def _derived(stat, parts, binning, human=None, label=None):
+    """the summed entries of the group of label (None: the pooled one) -> the same with "summary" / "human_summary" and the comparison
+    numbers against human -- one array (the pooled group's) or a dict label -> array -- else against its own "human_<array>_sum";
+    binning: the further arguments of the statistic's summary and comparison"""
+    mine, theirs = stat.array + "_sum", "human_" + stat.array + "_sum"
+    given = human.get(label) if isinstance(human, dict) else human if label is None else None
     out = dict(parts)
-    if "human_lattice_sum" in parts:
-        out["human_summary"] = saccade_summary(parts["human_lattice_sum"], frame_size, **kw)
-    if "lattice_sum" in parts:
-        out["summary"] = saccade_summary(parts["lattice_sum"], frame_size, **kw)
-        human = parts.get("human_lattice_sum") if human_lattice is None else human_lattice
-        if human is not None:
-            out.update(saccade_comparison(parts["lattice_sum"], human, frame_size, **kw))
+    if theirs in parts:
+        out["human_summary"] = _tool(stat, "summary")(parts[theirs], **binning)
+    if mine in parts:
+        out["summary"] = _tool(stat, "summary")(parts[mine], **binning)
+        against = parts.get(theirs) if given is None else given
+        if against is not None:
+            out.update(_tool(stat, "comparison")(parts[mine], against, **binning))
     return out
 
 
-def _human_of(human_lattice, label):
-    """the human lattice to compare a group against: human_lattice is None, one lattice (the pooled group's) or a dict label ->
-    lattice with the pooled group's under None"""
-    if isinstance(human_lattice, dict):
-        return human_lattice.get(label)
-    return human_lattice if label is None else None
+def _by_group(entries, labels, groups, label_of) -> dict:
+    """entries(i, member mask) -> the means of label i (None, everybody: pooled), under means["by_group"][label] when the call has groups"""
+    means = entries(None, np.ones(len(label_of), dtype=bool))
+    if groups is not None:
+        means["by_group"] = {label: entries(i, label_of == i) for i, label in enumerate(labels)}
+    return means
 
 
+def _scanpath_statistics(stat, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, binning, *args, **kw):
+    """(means, per_key) of scanpaths that exist: humans (side 0) and predictions of all groups in ONE counts(paths, side * NL + label,
+    2 NL, *args, **kw) launch; args and kw are checked"""
+    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
+    labels, label_of_key = _group_labels(index, groups)
+    NL = max(len(labels), 1)
+    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
+    side = np.r_[np.zeros(len(gt_keys), dtype=np.int64), np.ones(len(predict_keys), dtype=np.int64)]
+    path_label = label_of_key[key_of] if len(key_of) else key_of
+    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
+    res = _tool(stat, "counts")(paths, side * NL + path_label, 2 * NL, *args, **kw)
+    units, drop = res[stat.unit].astype(np.int64), res["dropped"].astype(np.int64)
+    sides = (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ())
+
+    def entries(i, member):
+        out = {}
+        for prefix, s in sides:
+            mine = member & (side == s)
+            array = res["counts"][s * NL:(s + 1) * NL].sum(0) if i is None else res["counts"][s * NL + i]
+            out.update({f"{prefix}{stat.array}_sum": array, f"{prefix}{stat.unit}_sum": int(units[mine].sum()),
+                        prefix + "scanpaths_count": int(mine.sum()), prefix + "fixations_dropped": int(drop[mine].sum())})
+        return _derived(stat, out, binning)
+
+    per_key = {"keys": list(index)}
+    for prefix, s in sides:
+        for name, v in ((stat.unit, units), ("dropped", drop)):
+            per_key[prefix + name] = np.bincount(key_of[side == s], weights=v[side == s], minlength=len(index)).astype(np.int64)
+    return _by_group(entries, labels, groups, path_label), per_key
+
+
+def _model_statistics(stat, predict, keys, performances, groups, map_shape, human, binning, **kw):
+    """(means, per_key) of the model's step distributions of ONE batch: one row per entry of _head_entries, ONE expectation(probs, the
+    entries' labels, NL, map_shape=map_shape, **kw) call; kw is checked.  binning None: the bare call, no summary and no comparison."""
+    keys = list(keys)
+    if performances is not None and len(performances) != len(keys):
+        raise ValueError("one list of performances per sample is required")
+    import torch
+    index, rows, key_of, shape, both = _head_entries(predict, keys, performances)
+    check_map(int(shape[-1]), map_shape, max_cells=MAX_CELLS)
+    labels, label_of_key = _group_labels(index, groups)
+    if not len(rows):
+        raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
+    probs = both("all_actions_prob")
+    if performances is not None:                               # one row per entry: a head read by k subjects counts k times
+        probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
+    res = _tool(stat, "expectation")(probs, label_of_key[key_of], max(len(labels), 1), map_shape=map_shape, **kw)
+    good, arrays = res["bad"] == 0, res[stat.expected]
+
+    def entries(i, member):
+        out = {stat.array + "_sum": sum(arrays[1:], arrays[0].copy()) if i is None else arrays[i],   # ascending label: a fixed order
+               stat.unit + "_sum": float(res[stat.unit][member & good].sum()), "rows_count": int((member & good).sum()),
+               "rows_bad": int((member & ~good).sum())}
+        return out if binning is None else _derived(stat, out, binning, human, None if i is None else labels[i])
+
+    per_key = {"keys": list(index), stat.unit: _pool(np.where(good, res[stat.unit], np.nan), key_of, len(index))[0]}
+    return _by_group(entries, labels, groups, label_of_key[key_of]), per_key
+
+
+class _StatisticsTable(_SumTable):
+    """what the two tables share: a table sets _stat, _shape and, where its summary needs arguments, _binning"""
+    _suffixes, _binning = ("_sum", "_count", "_bad", "_dropped"), {}
+
+    def _result(self, human) -> dict:
+        out = _derived(self._stat, self.parts, self._binning, human)
+        if self.by_group:
+            out["by_group"] = {label: _derived(self._stat, p, self._binning, human, label) for label, p in self.by_group.items()}
+        return out
+
+
+# ---- saccade statistics (evaltools/saccade_statistics.py, csrc/scansaccade.hip; DESIGN.md §22) ------------------------------------------
 def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, frame_size, map_shape, max_steps,
                                   amplitude_edges, n_directions, groups=None, image_keys=None):
     """How the scanpaths move (Le Meur & Liu 2015; Tatler & Vincent 2009): the distribution of saccade amplitudes, of saccade
@@ -1139,43 +1223,10 @@ def saccade_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, 
     means["by_group"][label] holds the same entries for the keys of that label.  per_key: "keys" and, per key in first-appearance order
     of gt_keys, the number of saccades counted and of fixations dropped ("human_saccades", "human_dropped", "saccades", "dropped", int64
     [G]) -- no lattice per key."""
-    from .evaltools.saccade_statistics import _check_directions, _check_edges, _check_shape, saccade_counts
-    max_steps, (Hm, Wm), _ = check_steps(max_steps), _check_shape(map_shape), check_frame(frame_size)
-    amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
-    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
-    labels, label_of_key = _group_labels(index, groups)
-    NL = max(len(labels), 1)
-    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
-    H, G = len(gt_keys), len(index)
-    side = np.r_[np.zeros(H, dtype=np.int64), np.ones(len(predict_keys), dtype=np.int64)]
-    launch_group = side * NL + (label_of_key[key_of] if len(key_of) else key_of)
-    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
-    res = saccade_counts(paths, launch_group, 2 * NL, frame_size, (Hm, Wm), max_steps=max_steps)
-    sacc, drop = res["saccades"].astype(np.int64), res["dropped"].astype(np.int64)
-    sides = (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ())
-
-    def entries(label_index):
-        out = {}
-        for prefix, s in sides:
-            mine = side == s
-            if label_index is None:
-                lattice = res["counts"][s * NL:(s + 1) * NL].sum(0)
-            else:
-                lattice = res["counts"][s * NL + label_index]
-                mine = mine & (label_of_key[key_of] == label_index)
-            out.update({prefix + "lattice_sum": lattice, prefix + "saccades_sum": int(sacc[mine].sum()),
-                        prefix + "scanpaths_count": int(mine.sum()), prefix + "fixations_dropped": int(drop[mine].sum())})
-        return _saccade_derived(out, frame_size, amplitude_edges, n_directions)
-
-    means = entries(None)
-    if groups is not None:
-        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
-    per_key = {"keys": list(index)}
-    for prefix, s in sides:
-        mine = side == s
-        per_key[prefix + "saccades"] = np.bincount(key_of[mine], weights=sacc[mine], minlength=G).astype(np.int64)
-        per_key[prefix + "dropped"] = np.bincount(key_of[mine], weights=drop[mine], minlength=G).astype(np.int64)
-    return means, per_key
+    max_steps, map_shape, _ = check_steps(max_steps), check_map_shape(map_shape), check_frame(frame_size)
+    binning = dict(frame_size=frame_size, amplitude_edges=check_edges(amplitude_edges), n_directions=check_directions(n_directions))
+    return _scanpath_statistics(_SACCADES, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, binning,
+                                frame_size, map_shape, max_steps=max_steps)
 
 
 def saccade_statistics_human_evaluation(gt_fix_vectors, gt_keys, *, frame_size, map_shape, max_steps, amplitude_edges, n_directions,
@@ -1203,96 +1254,38 @@ def saccade_statistics_model_evaluation(predict, keys, *, min_length, max_steps,
     with groups, means["by_group"][label] the same per label (human_lattice: one lattice for the pooled entries, or a dict label ->
     lattice with the pooled one under None).  per_key: "keys" and "saccades" float64 [G], the expected number of saccades per entry of
     the key (NaN for a key without a good entry)."""
-    from .evaltools.saccade_statistics import MAX_CELLS, _check_directions, _check_edges, saccade_expectation
-    max_steps, min_length = check_steps(max_steps), check_min_length(min_length)
-    check_frame(frame_size)
+    max_steps, min_length, _ = check_steps(max_steps), check_min_length(min_length), check_frame(frame_size)
     if (amplitude_edges is None) != (n_directions is None):
         raise ValueError("amplitude_edges and n_directions go together: the summary needs both")
-    if amplitude_edges is not None:
-        amplitude_edges, n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
-    elif human_lattice is not None:
+    if amplitude_edges is None and human_lattice is not None:
         raise ValueError("human_lattice is compared through the summary: amplitude_edges and n_directions are required with it")
-    keys = list(keys)
-    N = len(keys)
-    if performances is not None and len(performances) != N:
-        raise ValueError("one list of performances per sample is required")
-    import torch
-    index, rows, key_of, shape, both = _head_entries(predict, keys, performances)
-    check_map(int(shape[-1]), map_shape, max_cells=MAX_CELLS)
-    labels, label_of_key = _group_labels(index, groups)
-    NL = max(len(labels), 1)
-    if not len(rows):
-        raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
-    probs = both("all_actions_prob")
-    if performances is not None:                               # one row per entry: a head read by k subjects counts k times
-        probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
-    entry_label = label_of_key[key_of]
-    res = saccade_expectation(probs, entry_label, NL, min_length=min_length, max_steps=max_steps, map_shape=map_shape)
-    good = res["bad"] == 0
-
-    def entries(label_index):
-        mine = good if label_index is None else good & (entry_label == label_index)
-        lost = ~good if label_index is None else ~good & (entry_label == label_index)
-        if label_index is not None:
-            lattice = res["E"][label_index]
-        else:
-            lattice = res["E"][0].copy()
-            for g in range(1, NL):                              # ascending label: a fixed order
-                lattice = lattice + res["E"][g]
-        out = {"lattice_sum": lattice, "saccades_sum": float(res["saccades"][mine].sum()), "rows_count": int(mine.sum()),
-               "rows_bad": int(lost.sum())}
-        if amplitude_edges is None:
-            return out
-        label = None if label_index is None else labels[label_index]
-        return _saccade_derived(out, frame_size, amplitude_edges, n_directions, _human_of(human_lattice, label))
-
-    means = entries(None)
-    if groups is not None:
-        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
-    per_key = {"keys": list(index), "saccades": _pool(np.where(good, res["saccades"], np.nan), key_of, len(index))[0]}
-    return means, per_key
+    binning = None if amplitude_edges is None else dict(frame_size=frame_size, amplitude_edges=check_edges(amplitude_edges),
+                                                        n_directions=check_directions(n_directions))
+    return _model_statistics(_SACCADES, predict, keys, performances, groups, map_shape, human_lattice, binning, min_length=min_length,
+                             max_steps=max_steps)
 
 
-class SaccadeStatisticsTable(_SumTable):
+class SaccadeStatisticsTable(_StatisticsTable):
     """The pooled results of the saccade-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
     "_dropped" entry (also inside "by_group"); result(human_lattice=None) derives the summaries and the four comparison numbers from
     the SUMMED lattices, as one call on the union of the batches gives them.  The comparison is against "human_lattice_sum" when the
     table holds one, else against human_lattice (one lattice for the pooled entries, or a dict label -> lattice with the pooled one
     under None).  Integer lattices (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums and
     merge to rounding: the batches' lattices are added in the order of add, one call adds its rows in row order."""
-    _suffixes = ("_sum", "_count", "_bad", "_dropped")
+    _stat = _SACCADES
 
     def __init__(self, frame_size, map_shape, amplitude_edges, n_directions):
-        from .evaltools.saccade_statistics import _check_directions, _check_edges, _check_shape
         super().__init__()
-        self.frame_size, self.map_shape = check_frame(frame_size), _check_shape(map_shape)
-        self.amplitude_edges, self.n_directions = _check_edges(amplitude_edges), _check_directions(n_directions)
+        self.frame_size, self.map_shape = check_frame(frame_size), check_map_shape(map_shape)
+        self.amplitude_edges, self.n_directions = check_edges(amplitude_edges), check_directions(n_directions)
         self._shape = (2 * self.map_shape[0] - 1, 2 * self.map_shape[1] - 1)
+        self._binning = dict(frame_size=self.frame_size, amplitude_edges=self.amplitude_edges, n_directions=self.n_directions)
 
     def result(self, human_lattice=None) -> dict:
-        args = (self.frame_size, self.amplitude_edges, self.n_directions)
-        out = _saccade_derived(self.parts, *args, _human_of(human_lattice, None))
-        if self.by_group:
-            out["by_group"] = {label: _saccade_derived(p, *args, _human_of(human_lattice, label)) for label, p in self.by_group.items()}
-        return out
+        return self._result(human_lattice)
 
 
 # ---- turning angles (evaltools/turn_statistics.py, csrc/scanturn.hip; DESIGN.md §24) ------------------------------------------------------
-def _turn_derived(parts, human_table=None):
-    """the summed entries of one group -> the same with "summary" / "human_summary" (evaltools.turn_statistics.turn_summary) and,
-    against human_table (default: the group's own "human_table_sum"), the two comparison numbers "JSD_turn" and "JSD_transition" in bits"""
-    from .evaltools.turn_statistics import turn_comparison, turn_summary
-    out = dict(parts)
-    if "human_table_sum" in parts:
-        out["human_summary"] = turn_summary(parts["human_table_sum"])
-    if "table_sum" in parts:
-        out["summary"] = turn_summary(parts["table_sum"])
-        human = parts.get("human_table_sum") if human_table is None else human_table
-        if human is not None:
-            out.update(turn_comparison(parts["table_sum"], human))
-    return out
-
-
 def turn_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, frame_size, map_shape, max_steps, n_directions,
                                groups=None, image_keys=None):
     """How the direction of a saccade depends on the direction of the saccade before it (Tatler & Vincent 2009; Le Meur & Liu 2015): the
@@ -1306,44 +1299,10 @@ def turn_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, pre
     and, against the human side, ["JSD_turn"] and ["JSD_transition"] (bits).  With groups, means["by_group"][label] holds the same
     entries for the keys of that label.  per_key: "keys" and, per key in first-appearance order of gt_keys, the number of saccade pairs
     counted and of fixations dropped ("human_pairs", "human_dropped", "pairs", "dropped", int64 [G]) -- no table per key."""
-    from .evaltools.saccade_statistics import _check_shape
-    from .evaltools.turn_statistics import _check_n, turn_counts
-    max_steps, (Hm, Wm), _ = check_steps(max_steps), _check_shape(map_shape), check_frame(frame_size)
-    n_directions = _check_n(n_directions)
-    gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
-    labels, label_of_key = _group_labels(index, groups)
-    NL = max(len(labels), 1)
-    key_of = np.array([index[k] for k in gt_keys + predict_keys], dtype=np.int64)
-    H, G = len(gt_keys), len(index)
-    side = np.r_[np.zeros(H, dtype=np.int64), np.ones(len(predict_keys), dtype=np.int64)]
-    launch_group = side * NL + (label_of_key[key_of] if len(key_of) else key_of)
-    paths = [_xy(fv) for fv in gt_fix_vectors] + [_xy(fv) for fv in (predict_fix_vectors if predict_fix_vectors is not None else [])]
-    res = turn_counts(paths, launch_group, 2 * NL, frame_size, (Hm, Wm), max_steps=max_steps, n_directions=n_directions)
-    pairs, drop = res["pairs"].astype(np.int64), res["dropped"].astype(np.int64)
-    sides = (("human_", 0),) + ((("", 1),) if predict_fix_vectors is not None else ())
-
-    def entries(label_index):
-        out = {}
-        for prefix, s in sides:
-            mine = side == s
-            if label_index is None:
-                table = res["counts"][s * NL:(s + 1) * NL].sum(0)
-            else:
-                table = res["counts"][s * NL + label_index]
-                mine = mine & (label_of_key[key_of] == label_index)
-            out.update({prefix + "table_sum": table, prefix + "pairs_sum": int(pairs[mine].sum()),
-                        prefix + "scanpaths_count": int(mine.sum()), prefix + "fixations_dropped": int(drop[mine].sum())})
-        return _turn_derived(out)
-
-    means = entries(None)
-    if groups is not None:
-        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
-    per_key = {"keys": list(index)}
-    for prefix, s in sides:
-        mine = side == s
-        per_key[prefix + "pairs"] = np.bincount(key_of[mine], weights=pairs[mine], minlength=G).astype(np.int64)
-        per_key[prefix + "dropped"] = np.bincount(key_of[mine], weights=drop[mine], minlength=G).astype(np.int64)
-    return means, per_key
+    max_steps, map_shape, _ = check_steps(max_steps), check_map_shape(map_shape), check_frame(frame_size)
+    n_directions = check_directions(n_directions, MAX_DIRECTIONS)
+    return _scanpath_statistics(_TURNS, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, {},
+                                frame_size, map_shape, max_steps=max_steps, n_directions=n_directions)
 
 
 def turn_statistics_human_evaluation(gt_fix_vectors, gt_keys, *, frame_size, map_shape, max_steps, n_directions, groups=None,
@@ -1367,71 +1326,33 @@ def turn_statistics_model_evaluation(predict, keys, *, min_length, max_steps, n_
     groups, means["by_group"][label] the same per label (human_table: one table for the pooled entries, or a dict label -> table with
     the pooled one under None).  per_key: "keys" and "pairs" float64 [G], the expected number of pairs per entry of the key (NaN for a
     key without a good entry)."""
-    from .evaltools.scanpath_likelihood import MAX_CELLS
-    from .evaltools.turn_statistics import _check_n, _check_table, turn_expectation
-    max_steps, min_length, n_directions = check_steps(max_steps), check_min_length(min_length), _check_n(n_directions)
+    from .evaltools.turn_statistics import check_table
+    max_steps, min_length = check_steps(max_steps), check_min_length(min_length)
+    n_directions = check_directions(n_directions, MAX_DIRECTIONS)
     check_frame(frame_size)
     for h in (human_table.values() if isinstance(human_table, dict) else () if human_table is None else (human_table,)):
-        if _check_table(h).shape != (n_directions + 1, n_directions + 1):
+        if check_table(h).shape != (n_directions + 1, n_directions + 1):
             raise ValueError(f"human_table of shape {np.shape(h)}: [{n_directions + 1}, {n_directions + 1}] is required")
-    keys = list(keys)
-    N = len(keys)
-    if performances is not None and len(performances) != N:
-        raise ValueError("one list of performances per sample is required")
-    import torch
-    index, rows, key_of, shape, both = _head_entries(predict, keys, performances)
-    check_map(int(shape[-1]), map_shape, max_cells=MAX_CELLS)
-    labels, label_of_key = _group_labels(index, groups)
-    NL = max(len(labels), 1)
-    if not len(rows):
-        raise ValueError("no entry to evaluate: an empty batch (or no subject in performances)")
-    probs = both("all_actions_prob")
-    if performances is not None:                               # one row per entry: a head read by k subjects counts k times
-        probs = probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device))
-    entry_label = label_of_key[key_of]
-    res = turn_expectation(probs, entry_label, NL, min_length=min_length, max_steps=max_steps, frame_size=frame_size,
-                           n_directions=n_directions, map_shape=map_shape)
-    good = res["bad"] == 0
-
-    def entries(label_index):
-        mine = good if label_index is None else good & (entry_label == label_index)
-        lost = ~good if label_index is None else ~good & (entry_label == label_index)
-        if label_index is not None:
-            table = res["M"][label_index]
-        else:
-            table = res["M"][0].copy()
-            for g in range(1, NL):                              # ascending label: a fixed order
-                table = table + res["M"][g]
-        out = {"table_sum": table, "pairs_sum": float(res["pairs"][mine].sum()), "rows_count": int(mine.sum()), "rows_bad": int(lost.sum())}
-        return _turn_derived(out, _human_of(human_table, None if label_index is None else labels[label_index]))
-
-    means = entries(None)
-    if groups is not None:
-        means["by_group"] = {label: entries(i) for i, label in enumerate(labels)}
-    per_key = {"keys": list(index), "pairs": _pool(np.where(good, res["pairs"], np.nan), key_of, len(index))[0]}
-    return means, per_key
+    return _model_statistics(_TURNS, predict, keys, performances, groups, map_shape, human_table, {}, min_length=min_length,
+                             max_steps=max_steps, frame_size=frame_size, n_directions=n_directions)
 
 
-class TurnStatisticsTable(_SumTable):
+class TurnStatisticsTable(_StatisticsTable):
     """The pooled results of the turn-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
     "_dropped" entry (also inside "by_group"); result(human_table=None) derives the summaries and the two comparison numbers from the
     SUMMED tables, as one call on the union of the batches gives them.  The comparison is against "human_table_sum" when the table
     holds one, else against human_table (one table for the pooled entries, or a dict label -> table with the pooled one under None).
     Integer tables (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums of non-negative terms
     and merge to rounding: the batches' tables are added in the order of add, one call adds its rows in row order."""
-    _suffixes = ("_sum", "_count", "_bad", "_dropped")
+    _stat = _TURNS
 
     def __init__(self, n_directions):
-        from .evaltools.turn_statistics import _check_n
         super().__init__()
-        self.n_directions = _check_n(n_directions)
+        self.n_directions = check_directions(n_directions, MAX_DIRECTIONS)
         self._shape = (self.n_directions + 1, self.n_directions + 1)
 
     def result(self, human_table=None) -> dict:
-        out = _turn_derived(self.parts, _human_of(human_table, None))
-        if self.by_group:
-            out["by_group"] = {label: _turn_derived(p, _human_of(human_table, label)) for label, p in self.by_group.items()}
-        return out
+        return self._result(human_table)
 
 
 # ---- bootstrap intervals and paired comparisons for every keyed table (evaltools/bootstrap.py, csrc/scanboot.hip; DESIGN.md §23) ----------

@@ -1,11 +1,11 @@
 """Characterisation fixture of the host layer of the keyed evaluation calls (scanpaths_amd/utils/evaluation.py from likelihood_evaluation
-down, the three sum tables, and the batch loops of scanpaths_amd/inference.py), CPU only:
+down, the sum tables, and the batch loops of scanpaths_amd/inference.py), CPU only:
 
     python tests/golden/make_golden_keyed_tables.py
 
 The device entry points are replaced by the deterministic stand-ins of tests/keyed_tables_cases.py, whose values are dyadic rationals:
 what is recorded is what the host code makes of them -- pooled means, per-key tables, merged tables, refusal messages and, per batch
-loop, how the model was called.  The log-based saccade entries (keyed_tables_cases.DERIVED) are not stored: the test recomputes them
+loop, how the model was called.  The log-based saccade and turn entries (keyed_tables_cases.DERIVED) are not stored: the test recomputes them
 in-process.  Record it with the code whose behaviour is to be kept, BEFORE changing that code; the test then holds the changed code to it.
 Writes tests/golden/keyed_tables.npz."""
 import os

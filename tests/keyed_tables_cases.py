@@ -1,5 +1,5 @@
 """The cases of tests/test_keyed_tables_cpu.py and of its recording script tests/golden/make_golden_keyed_tables.py: deterministic
-stand-ins for the six device entry points under the keyed evaluation calls, the inputs, and the calls themselves.  No device and no
+stand-ins for the eight device entry points under the keyed evaluation calls, the inputs, and the calls themselves.  No device and no
 library is touched.  Every value a stand-in returns is a dyadic rational (an integer / 1024) drawn from a generator seeded by the
 call's own arguments, so every sum the host code forms is exact in float64 and independent of the order of summation, and a stand-in
 gives the same answer wherever in a run it is called.  Values read from the call's probability rows are mixed in, so that the row an
@@ -20,7 +20,8 @@ METRICS = ("LL", "IG", "NSS", "AUC", "DLL", "STOP")
 EDGES, DIRECTIONS = [0.0, 8.0, 16.0, 64.0], 4
 GROUPS = {"a": "find", "b": "count", "c": "find", "d": "count"}
 BOXES = {"a": [0.0, 0.0, 8.0, 8.0], "b": [8.0, 0.0, 24.0, 16.0], "c": [-4.0, 0.0, 4.0, 8.0], "d": [0.0, 8.0, 8.0, 16.0]}
-DERIVED = ("summary", "human_summary", "JSD_lattice", "JSD_amplitude", "JSD_direction", "W1_amplitude")    # log-based: compared in-process
+DERIVED = ("summary", "human_summary", "JSD_lattice", "JSD_amplitude", "JSD_direction", "W1_amplitude", "JSD_turn",
+           "JSD_transition")                                       # log-based: compared in-process
 
 
 def _rng(*what):
@@ -128,9 +129,34 @@ def saccade_expectation(probs, row_groups, n_groups, *, min_length, max_steps, m
     return {"E": E, "saccades": sacc, "bad": bad}
 
 
+def turn_counts(scanpaths, groups, n_groups, frame_size, map_shape, *, max_steps, n_directions):
+    grp, S = np.asarray(groups, dtype=np.int64), len(scanpaths)
+    g = _rng("turn_counts", grp.tolist(), n_groups, tuple(map_shape), max_steps, n_directions)
+    counts = g.integers(0, 20, (n_groups, n_directions + 1, n_directions + 1)).astype(np.int64)
+    counts[np.bincount(grp, minlength=n_groups) == 0] = 0
+    return {"counts": counts, "pairs": g.integers(0, 9, S).astype(np.int32), "dropped": g.integers(0, 3, S).astype(np.int32)}
+
+
+def turn_expectation(probs, row_groups, n_groups, *, min_length, max_steps, frame_size, n_directions, map_shape=None):
+    """row 1 is bad: NaN pairs, nothing added to its group"""
+    p, grp = _np(probs), np.asarray(row_groups, dtype=np.int64)
+    R = len(grp)
+    g = _rng("turn_expectation", p.shape, grp.tolist(), n_groups, min_length, max_steps, tuple(frame_size), n_directions)
+    bad = np.zeros(R, dtype=np.int32)
+    bad[1:2] = 1
+    pairs = _dyadic(g, R, 0, 4096) + p[:, 0, 0]
+    pairs[bad == 1] = np.nan
+    M = np.zeros((n_groups, n_directions + 1, n_directions + 1))
+    for r in range(R):
+        table = _dyadic(g, M.shape[1:], 0, 2048) + p[r, 1, 0]
+        if not bad[r]:
+            M[grp[r]] += table
+    return {"M": M, "pairs": pairs, "bad": bad}
+
+
 def install(setattr_):
-    """replace the six entry points; setattr_(module, name, value): monkeypatch.setattr in the test, setattr in the recording script"""
-    from scanpaths_amd.utils.evaltools import saccade_statistics, scanpath_kde, search_efficiency
+    """replace the eight entry points; setattr_(module, name, value): monkeypatch.setattr in the test, setattr in the recording script"""
+    from scanpaths_amd.utils.evaltools import saccade_statistics, scanpath_kde, search_efficiency, turn_statistics
     from scanpaths_amd.utils.evaltools import scanpath_likelihood as lik
     setattr_(lik, "scanpath_likelihood", scanpath_likelihood)
     setattr_(scanpath_kde, "kde_leave_out_likelihood", kde_leave_out_likelihood)
@@ -138,6 +164,8 @@ def install(setattr_):
     setattr_(search_efficiency, "target_hit_probability", target_hit_probability)
     setattr_(saccade_statistics, "saccade_counts", saccade_counts)
     setattr_(saccade_statistics, "saccade_expectation", saccade_expectation)
+    setattr_(turn_statistics, "turn_counts", turn_counts)
+    setattr_(turn_statistics, "turn_expectation", turn_expectation)
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------------------------
@@ -283,6 +311,31 @@ def collect(setattr_):
     out["saccade/eval/table"] = table.result()
     out["saccade/eval/table/lattice"] = table.result(lattice)
 
+    # turning angles: every saccade case again
+    ukw = dict(max_steps=6, n_directions=DIRECTIONS, **shape)
+    for name, groups in (("pooled", None), ("groups", GROUPS)):
+        out[f"turn/eval/{name}"] = E.turn_statistics_evaluation(gt, pred, gt_keys, predict_keys, groups=groups, **ukw)
+        out[f"turn/human/{name}"] = E.turn_statistics_human_evaluation(gt, gt_keys, groups=groups, **ukw)
+    human = out["turn/human/groups"][0]
+    turns = human["human_table_sum"]
+    turns_by_label = {None: turns, "find": human["by_group"]["find"]["human_table_sum"]}           # "count" has none: no comparison
+    tkw = dict(min_length=1, max_steps=3, n_directions=DIRECTIONS, **shape)
+    out["turn/model/plain/none"] = E.turn_statistics_model_evaluation(one, KEYS, **tkw)
+    out["turn/model/plain/table"] = E.turn_statistics_model_evaluation(one, KEYS, human_table=turns, **tkw)
+    for name, against in (("none", None), ("table", turns), ("dict", turns_by_label)):
+        out[f"turn/model/heads/{name}"] = E.turn_statistics_model_evaluation(two, KEYS, performances=ENTRIES, groups=GROUPS,
+                                                                             human_table=against, **tkw)
+    turn_table = E.TurnStatisticsTable(DIRECTIONS)
+    turn_table.add(out["turn/model/heads/none"][0])
+    turn_table.add(E.turn_statistics_model_evaluation(one, KEYS, groups=GROUPS, **tkw)[0])
+    for name, against in (("none", None), ("table", turns), ("dict", turns_by_label)):
+        out[f"turn/model/table/{name}"] = turn_table.result(against)
+    turn_table = E.TurnStatisticsTable(DIRECTIONS)
+    turn_table.add(out["turn/eval/groups"][0])
+    turn_table.add(out["turn/human/groups"][0])
+    out["turn/eval/table"] = turn_table.result()
+    out["turn/eval/table/table"] = turn_table.result(turns)
+
     # refusals of the model-side calls, word for word
     lik = dict(uniform_mix=0.25, **shape)
     out["refusals"] = [
@@ -304,6 +357,17 @@ def collect(setattr_):
         _refusal(E.saccade_statistics_model_evaluation, one, KEYS, min_length=1, max_steps=3, frame_size=FRAME, map_shape=(4, 4)),
         _refusal(table.add, {"lattice_sum": np.zeros((3, 3))}),
     ]
+    out["refusals_turn"] = [
+        _refusal(E.turn_statistics_model_evaluation, two, KEYS, **tkw),
+        _refusal(E.turn_statistics_model_evaluation, one, KEYS[:2], **tkw),
+        _refusal(E.turn_statistics_model_evaluation, two, KEYS, performances=[[], [], []], **tkw),
+        _refusal(E.turn_statistics_model_evaluation, one, KEYS, groups={"a": "find"}, **tkw),
+        _refusal(E.turn_statistics_model_evaluation, one, KEYS, human_table=np.zeros((3, 3)), **tkw),
+        _refusal(E.turn_statistics_model_evaluation, one, KEYS, min_length=1, max_steps=3, n_directions=DIRECTIONS, frame_size=FRAME,
+                 map_shape=(4, 4)),
+        _refusal(E.turn_statistics_model_evaluation, one, KEYS, min_length=1, max_steps=3, n_directions=17, **shape),
+        _refusal(turn_table.add, {"table_sum": np.zeros((3, 3))}),
+    ]
 
     # the batch loops: what the model was called with, and what came back
     setattr_(inference, "sample_batch", lambda predict, sampling, repeat_num: (torch.ones(repeat_num, 2, N, T, 3),
@@ -319,6 +383,7 @@ def collect(setattr_):
         "saccade_statistics": lambda m, ld, ab: inference.run_saccade_statistics_loop(
             m, ld, min_length=1, max_steps=3, amplitude_edges=EDGES, n_directions=DIRECTIONS, human_lattice=lattice, ablate_attention_info=ab,
             **shape),
+        "turn_statistics": lambda m, ld, ab: inference.run_turn_statistics_loop(m, ld, human_table=turns, ablate_attention_info=ab, **tkw),
         "test": lambda m, ld, ab: _test_loop(inference.run_test_loop(m, None, ld, repeat_num=2, ablate_attention_info=ab)),
     }
     for name, run in loops.items():

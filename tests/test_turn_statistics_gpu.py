@@ -90,6 +90,42 @@ def test_turn_counts_blocks_with_idle_waves(S):
     same(again["counts"], want["counts"], "second call")
 
 
+def prologue_paths(frame):
+    """lengths 0, 1, 2, 3, 9 and 64 with every fixation inside the frame, then the 9 and the 64 again with one fixation out of the frame
+    or NaN at the start, in the middle and at the end"""
+    fh, fw = frame
+    g = np.random.default_rng(7)
+
+    def inside(n):
+        return np.stack([g.uniform(0.0, fw, n), g.uniform(0.0, fh, n)], 1) % np.array([fw, fh])
+
+    paths = [inside(n) for n in (0, 1, 2, 3, 9, 64)]
+    for n in (9, 64):
+        for where in (0, n // 2, n - 1):
+            for value in (float("nan"), -1.0, 2.0 * fw):
+                p = inside(n)
+                p[where, 0] = value
+                paths.append(p)
+    return paths
+
+
+@pytest.mark.parametrize("max_steps", [1, 2, 3, 1000])
+@pytest.mark.parametrize("shape", [(1, 1), (1, 3), (7, 9)])
+def test_turn_and_saccade_counts_share_one_prologue(shape, max_steps):
+    """what scan_lane_cell makes structural: the two counts kernels drop the same fixations, and a scanpath that drops none has one
+    pair fewer than saccades (tests/saccade_statistics_ref.py and tests/turn_statistics_ref.py satisfy both on these inputs)"""
+    from scanpaths_amd.utils.evaltools import saccade_statistics
+    frame = MAPS[shape]
+    paths = prologue_paths(frame)
+    groups = [k % 2 for k in range(len(paths))]
+    sacc = saccade_statistics.saccade_counts(paths, groups, 2, frame, shape, max_steps=max_steps)
+    turn = M().turn_counts(paths, groups, 2, frame, shape, max_steps=max_steps, n_directions=4)
+    same(turn["dropped"], sacc["dropped"], ("dropped", shape, max_steps))
+    clean = sacc["dropped"] == 0
+    assert clean[:6].all() and (max_steps < 9 or not clean[6:].any())                  # both kinds of scanpath are among the inputs
+    same(turn["pairs"][clean], np.maximum(sacc["saccades"][clean] - 1, 0), ("pairs", shape, max_steps))
+
+
 def test_turn_counts_guards_itself_at_the_c_entry_point():
     """a count the kernel cannot hold or a group that does not exist (the Python layer refuses both earlier): -1, nothing read or
     counted; a sector-table entry outside [0, n] is read as n (what such a table counts is unspecified, the access stays in bounds)"""
