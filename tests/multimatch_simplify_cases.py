@@ -1,8 +1,6 @@
 """Inputs shared by tests/test_multimatch_simplify_cpu.py and tests/test_multimatch_simplify_gpu.py: seeded random
 scanpaths (half on a 40 x 30 lattice of 8 px with durations {1..6} * 0.1, where direction and amplitude decisions tie; half uniform),
 the constructed cases whose simplification is written out by hand, and the argument lists of the two C entry points."""
-import ctypes
-import os
 
 import numpy as np
 
@@ -72,19 +70,6 @@ CONSTRUCTED = {
     "walk 33": (walk(33), (45.0, 0.3, 0.0), [0, 32]),
     "walk 64": (walk(64), (45.0, 0.3, 0.0), [0, 63]),
 }
-
-
-def load_lib():
-    """the built library with the two new entry points typed (no device is needed for the refusals)"""
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in list(NEW) + ["sp_scan_multimatch", "sp_scan_max_fixations", "sp_abi_version"]:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
-    return lib
 
 
 def check_refusals(lib):

@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import abi
 import bootstrap_ref as R
 from sampling_ref import philox4x32_10
 
@@ -323,14 +324,8 @@ def test_information_gain_explained_is_one_contrast(on_host):
 
 # ---- the library --------------------------------------------------------------------------------------------------------------------------
 def test_the_library_exports_the_entry_points_and_the_limit():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in ("sp_boot_max_columns", "sp_boot_cluster_sums", "sp_boot_resample", "sp_boot_summarise"):
-        assert hasattr(lib, name) and name in hip.SIGNATURES
-        getattr(lib, name).restype, getattr(lib, name).argtypes = hip.SIGNATURES[name]
+    lib = abi.assert_declared({"sp_boot_max_columns": ("int", 0), "sp_boot_cluster_sums": ("int", 10), "sp_boot_resample": ("int", 12),
+                               "sp_boot_summarise": ("int", 12)})
     assert lib.sp_boot_max_columns() == M().MAX_COLUMNS
     assert "scanboot.hip" in open(os.path.join(ROOT, "scanpaths_amd", "csrc", "Makefile")).read()
     # the launchers refuse before any launch (no device needed): null pointers and shapes outside their domain

@@ -10,59 +10,35 @@ import numpy as np
 import pytest
 import torch
 
+import abi
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_symbols():
-    txt = open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sp_[A-Za-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_declared_symbol():
     from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    syms = _header_symbols()
+    lib = abi.raw_lib()
+    syms = abi.header_symbols()
     assert len(syms) >= 35
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/scanpaths_amd.h but not exported"
     assert sorted(hip.SIGNATURES) == syms, set(hip.SIGNATURES) ^ set(syms)
+    # the binding is derived from the header, so the list that stands beside the header is the library's own: nothing exported undeclared
+    assert abi.exported_functions() == syms, set(abi.exported_functions()) ^ set(syms)
     # pure host call, no GPU needed: the library, the header and the ctypes binding carry the same ABI version
-    hdr = int(re.search(r"#define SP_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read()).group(1))
-    assert lib.sp_abi_version() == hdr == hip.ABI_VERSION
+    assert lib.sp_abi_version() == abi.header_abi_version() == hip.ABI_VERSION
 
 
 def test_ctypes_signatures_match_the_header():
-    """ABI drift guard: for every entry point the ctypes binding (hip.SIGNATURES) has as many arguments as the header declares,
-    8-byte integers / doubles / floats where the header says so, and the return type (int / int64_t)."""
+    """ABI drift guard: for every entry point the ctypes binding (hip.SIGNATURES, derived from the header by scanpaths_amd/_abi.py) has
+    as many arguments as the independent reading of the header in tests/abi.py finds, 8-byte integers / doubles / floats where the header
+    says so, c_char_p for `const char*`, POINTER of the right descriptor class for a descriptor pointer, c_void_p for every other pointer,
+    and the return type (int / int64_t)."""
     from scanpaths_amd import hip
-    txt = open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    decls = dict()
-    for m in re.finditer(r"\b(int64_t|int)\s+(sp_[A-Za-z0-9_]+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S):
-        ret, name, args = m.group(1), m.group(2), " ".join(m.group(3).split())
-        decls[name] = (ret, [] if args in ("", "void") else [a.strip() for a in args.split(",")])
+    decls = abi.header_decls()
     assert set(decls) == set(hip.SIGNATURES), set(decls) ^ set(hip.SIGNATURES)
-    for name, (ret, args) in decls.items():
-        cret, cargs = hip.SIGNATURES[name]
-        assert len(cargs) == len(args), (name, len(cargs), args)
-        assert (cret is ctypes.c_int64) == (ret == "int64_t"), (name, ret, cret)
-        for a, c in zip(args, cargs):
-            if "*" in a:
-                assert c in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(c, ctypes._Pointer), (name, a, c)      # void* or POINTER(desc struct)
-            elif a.startswith("int64_t"):
-                assert c is ctypes.c_int64, (name, a, c)
-            elif a.startswith("uint64_t"):
-                assert c is ctypes.c_uint64, (name, a, c)
-            elif a.startswith("double"):
-                assert c is ctypes.c_double, (name, a, c)
-            elif a.startswith("float"):
-                assert c is ctypes.c_float, (name, a, c)
-            else:
-                assert a.startswith("int") and c is ctypes.c_int, (name, a, c)
+    for name, decl in decls.items():
+        abi.assert_bound(name, decl)
 
 
 @pytest.mark.parametrize("case,task", [("air_train_T4", "AiR"), ("osie_r18_train_T8", "OSIE"), ("coco_train_T6", "COCO_Search18")])
@@ -338,13 +314,9 @@ def test_kernel_sources_read_no_environment():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for fn in glob.glob(os.path.join(root, "scanpaths_amd", "csrc", "*.h*")):
         assert "getenv" not in open(fn).read(), fn
-    import ctypes
-    from scanpaths_amd import hip
-    if os.path.exists(hip.LIB_PATH):
-        lib = ctypes.CDLL(hip.LIB_PATH)
-        lib.sp_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_int]
-        assert lib.sp_timing_build() == 0
-        assert lib.sp_set_tuning(b"h2_dbg", 1) == -1 and lib.sp_set_tuning(b"amax_reset", 1) == 0
+    lib = abi.raw_lib()
+    assert lib.sp_timing_build() == 0
+    assert lib.sp_set_tuning(b"h2_dbg", 1) == -1 and lib.sp_set_tuning(b"amax_reset", 1) == 0
 
 
 def test_halo_block_swizzle_is_bank_conflict_free_for_every_base():

@@ -2,13 +2,12 @@
 by hand (halving of a collinear walk, the amplitude pass on a staircase, the even-offset rule within runs of candidates, the last
 fixation, zero-length saccades), its properties over seeded random scanpaths, docomparison(grouping=True) and its scoring rule, every
 argument refusal of the Python layer (raised before a device or the library is touched) and the two new C entry points."""
-import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import multimatch_simplify_cases as C
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,26 +171,12 @@ def test_a_callable_gets_the_package_signature():
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import multimatch as M
-    lib = C.load_lib()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in C.NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",")]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            assert c is (ctypes.c_void_p if "*" in a else kinds[a.split()[0]]), (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == lib.sp_abi_version() == 4
+    lib = abi.assert_declared(C.NEW)
     assert lib.sp_scan_max_fixations() == M.MAX_FIXATIONS == 64
     src = open(os.path.join(ROOT, "scanpaths_amd", "utils", "evaltools", "multimatch.py")).read()
     assert "NotImplementedError" not in src
 
 
 def test_launchers_refuse_bad_arguments_without_a_device():
-    C.check_refusals(C.load_lib())
+    C.check_refusals(abi.raw_lib())

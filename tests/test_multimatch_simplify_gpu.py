@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi
 import multimatch_simplify_cases as C
 
 pytestmark = pytest.mark.gpu
@@ -136,7 +137,7 @@ def test_zero_thresholds_and_equal_gate_change_nothing(scored):
 
 
 def test_c_entry_points_refuse_bad_arguments():
-    C.check_refusals(C.load_lib())
+    C.check_refusals(abi.raw_lib())
 
 
 def _fv(rng, n, k):

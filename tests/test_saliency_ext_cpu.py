@@ -1,43 +1,19 @@
 """CPU-only checks of the shuffled AUC / CC / SIM / information gain layer: the new entry points are declared, bound and exported with
 equal signatures; the numpy checker (tests/saliency_ext_ref.py) satisfies the identities its formulae imply; every argument refusal
 of the Python layer is raised before a device or the library is touched."""
-import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import saliency_ext_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sp_fixation_pool_counts": ("int", 9), "sp_saliency_scores": ("int", 19)}
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",")]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        assert name in hip.SIGNATURES, name
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            want = ctypes.c_void_p if "*" in a else kinds[a.split()[0]]
-            assert c is want, (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert not any(n.startswith("sp_saliency_metrics_") and n != "sp_saliency_metrics_lds_fixations" for n in hip.SIGNATURES), \
-        "no suffixed variants of sp_saliency_metrics"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4
+    abi.assert_declared(NEW, prefixes=("sp_saliency_metrics_",), allowed=("sp_saliency_metrics_lds_fixations",))
 
 
 def _maps(g, shape, levels=None):

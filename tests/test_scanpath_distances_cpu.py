@@ -2,57 +2,26 @@
 exported with equal signatures; the Python checker (tests/scanpath_dist_ref.py) holds the sanity values, inequalities and symmetries of
 DESIGN.md §16; the public signatures are the documented ones; every argument refusal of the Python layer is raised before a device or
 the library is touched."""
-import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import scanpath_dist_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sp_scan_distances": ("int", 12), "sp_scan_recurrence": ("int", 11)}
 
 
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import visual_attention_metrics as M
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",")]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        assert name in hip.SIGNATURES, name
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            want = ctypes.c_void_p if "*" in a else kinds[a.split()[0]]
-            assert c is want, (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert not any(n.startswith(("sp_scan_distances_", "sp_scan_recurrence_")) for n in hip.SIGNATURES), "no suffixed variants"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4
-    lib.sp_scan_max_fixations.restype = ctypes.c_int
+    lib = abi.assert_declared(NEW, prefixes=("sp_scan_distances_", "sp_scan_recurrence_"))
     assert lib.sp_scan_max_fixations() == M.MAX_FIXATIONS == 64      # the limit the Python layer refuses by, without the library
 
 
 def test_launchers_refuse_bad_arguments_without_a_device():
     """the argument checks of the two launchers come before the launch: SP_ENULL (-2) / SP_EINVAL (-1) on a machine without a GPU too"""
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in NEW:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
+    lib = abi.raw_lib()
     p = 4096                                                        # any non-NULL value: nothing is dereferenced before the checks
     D, Rc = lib.sp_scan_distances, lib.sp_scan_recurrence
     assert D(p, 2, p, p, p, 1, 1.0, None, None, None, None, None) == -2            # all four outputs NULL

@@ -7,29 +7,17 @@ import ctypes
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
 import scanpath_kde_cases as C
+import abi
 import scanpath_kde_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sp_scan_kde_max_bandwidths": ("int", 0), "sp_scan_kde": ("int", 26)}
-
-
-def _lib():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in list(NEW) + ["sp_scan_likelihood_max_cells"]:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
-    return lib
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------------
@@ -135,22 +123,8 @@ def test_summation_order_spread_on_the_shared_inputs():
 
 # ---- the library ------------------------------------------------------------------------------------------------------------------------------
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import scanpath_kde as M
-    lib = _lib()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",") if a.strip() != "void"]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            assert c is (ctypes.c_void_p if "*" in a else kinds[a.split()[0]]), (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4     # additions only
+    lib = abi.assert_declared(NEW)
     assert lib.sp_scan_kde_max_bandwidths() == M.MAX_BANDWIDTHS == R.MAX_BANDWIDTHS >= 16
     assert lib.sp_scan_likelihood_max_cells() == M.MAX_CELLS == R.MAX_CELLS
     assert "scankde.hip" in open(os.path.join(ROOT, "scanpaths_amd", "csrc", "Makefile")).read()
@@ -162,7 +136,7 @@ FIX, PATH, STEP, IMG, ISTART, BLOCKS, N, NCOL, NG, NB, BW, NK, HM, WM, FW, FH, U
 
 def test_launcher_refuses_bad_arguments_without_a_device():
     """SP_ENULL (-2) / SP_EINVAL (-1) come before the launch, so on a machine without a GPU too.  Every call below is a refused one."""
-    call = _lib().sp_scan_kde
+    call = abi.raw_lib().sp_scan_kde
     p = 4096                                                        # any non-NULL value: nothing is dereferenced before the checks
     nan, inf = float("nan"), float("inf")
     good = (ctypes.c_double * 16)(*([8.0] * 16))

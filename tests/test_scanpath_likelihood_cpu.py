@@ -2,16 +2,15 @@
 signatures and refuse bad arguments before any launch; the Python checker (tests/scanpath_likelihood_ref.py) holds the answers worked
 out by hand; the public signatures are the documented ones; every argument refusal of the Python layer is raised before a device or the
 library is touched."""
-import ctypes
 import inspect
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import scanpath_likelihood_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,40 +18,10 @@ NEW = {"sp_scan_likelihood_max_cells": ("int", 0), "sp_scan_likelihood": ("int",
 LOG2E = 1.0 / math.log(2.0)
 
 
-def _lib():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in NEW:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
-    return lib
-
-
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import scanpath_likelihood as M
-    lib = _lib()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",") if a.strip() != "void"]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        assert name in hip.SIGNATURES, name
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            want = ctypes.c_void_p if "*" in a else kinds[a.split()[0]]
-            assert c is want, (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert not any(n.startswith("sp_scan_likelihood_") and n != "sp_scan_likelihood_max_cells" for n in hip.SIGNATURES), "no suffixed variants"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4
+    lib = abi.assert_declared(NEW, prefixes=("sp_scan_likelihood_",))
     assert lib.sp_scan_likelihood_max_cells() == M.MAX_CELLS == R.MAX_CELLS == 2048
-    lib.sp_scan_max_fixations.restype = ctypes.c_int
     assert lib.sp_scan_max_fixations() == M.MAX_FIXATIONS == R.MAX_FIXATIONS == 64
     assert "scanlik.hip" in open(os.path.join(ROOT, "scanpaths_amd", "csrc", "Makefile")).read()
 
@@ -64,7 +33,7 @@ LL, IG, NSS, AUC, DLL, CONT, TERM, DROPPED, STREAM = range(20, 29)
 
 def test_launcher_refuses_bad_arguments_without_a_device():
     """SP_ENULL (-2) / SP_EINVAL (-1) come before the launch, so on a machine without a GPU too.  Every call below is a refused one."""
-    call = _lib().sp_scan_likelihood
+    call = abi.raw_lib().sp_scan_likelihood
     p = 4096                                                        # any non-NULL value: nothing is dereferenced before the checks
     nan, inf = float("nan"), float("inf")
     ok = [p] * 11 + [2, 4, 30, 40, 5, 3, 320.0, 240.0, 0.01] + [p] * 8 + [None]

@@ -3,57 +3,26 @@ signatures and refuse bad arguments before any launch; every argument refusal of
 library is touched; the Python checker (tests/search_efficiency_ref.py) holds answers worked out by hand and, for T = 3 on a 2 x 2 map,
 equals the exhaustive enumeration of all 5^3 action sequences under the sampler's rule in exact rational arithmetic -- which makes the
 checker independent of the closed form's own reasoning."""
-import ctypes
 import inspect
 import itertools
 import math
 import os
-import re
 from fractions import Fraction
 
 import numpy as np
 import pytest
 import torch
 
+import abi
 import search_efficiency_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sp_scan_target_hits": ("int", 11), "sp_scan_target_mass": ("int", 16)}
 
 
-def _lib():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in NEW:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
-    return lib
-
-
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import search_efficiency as M
-    lib = _lib()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",") if a.strip() != "void"]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        assert name in hip.SIGNATURES, name
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            want = ctypes.c_void_p if "*" in a else kinds[a.split()[0]]
-            assert c is want, (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert not any(n.startswith("sp_scan_target_") and n not in NEW for n in hip.SIGNATURES), "no suffixed variants"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4
-    lib.sp_scan_max_fixations.restype = ctypes.c_int
+    lib = abi.assert_declared(NEW, prefixes=("sp_scan_target_",))
     assert lib.sp_scan_max_fixations() == M.MAX_FIXATIONS == R.MAX_FIXATIONS == 64
     assert M.MAX_SIDE == R.MAX_SIDE == 1024
     assert "scansearch.hip" in open(os.path.join(ROOT, "scanpaths_amd", "csrc", "Makefile")).read()
@@ -61,7 +30,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
 
 def test_launchers_refuse_bad_arguments_without_a_device():
     """SP_ENULL (-2) / SP_EINVAL (-1) come before the launch, so on a machine without a GPU too.  Every call below is a refused one."""
-    lib = _lib()
+    lib = abi.raw_lib()
     p = 4096                                                        # any non-NULL value: nothing is dereferenced before the checks
     nan, inf = float("nan"), float("inf")
     # sp_scan_target_hits(fix, ncol, start, count, box, nscan, max_steps, hit, path, spr, stream)

@@ -2,17 +2,14 @@
 signatures and refuse bad arguments before any launch; the Python checker (tests/seqscore_ref.py) holds the known answers and the
 properties of the definitions, its quick variant equals its plain-loop variant bit for bit, and it agrees with sklearn's MeanShift where
 that is installed; every argument refusal of the Python layer is raised before a device or the library is touched."""
-import ctypes
 import inspect
-import os
-import re
 
 import numpy as np
 import pytest
 
+import abi
 import seqscore_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"sp_meanshift_max_points": ("int", 0), "sp_meanshift": ("int", 12), "sp_scan_cluster_strings": ("int", 11),
        "sp_scan_sequence": ("int", 9)}
 # four-fold symmetric: four clusters of three points, equal in k; (10, 10) and (10, -10) tie in x (y decides), two seeds of a cluster
@@ -20,47 +17,16 @@ NEW = {"sp_meanshift_max_points": ("int", 0), "sp_meanshift": ("int", 12), "sp_s
 SYMMETRIC = np.array([[s * 10.0 + a, t * 10.0 + b] for s in (1, -1) for t in (1, -1) for a, b in ((0, 0), (1, 0), (-1, 0))])
 
 
-def _lib():
-    from scanpaths_amd import hip
-    if not os.path.exists(hip.LIB_PATH):
-        import __graft_entry__ as g
-        g.build()
-    lib = ctypes.CDLL(hip.LIB_PATH)
-    for name in NEW:
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = hip.SIGNATURES[name]
-    return lib
-
-
 def test_new_entry_points_are_declared_bound_and_exported():
-    from scanpaths_amd import hip
     from scanpaths_amd.utils.evaltools import sequence_score as S
-    lib = _lib()
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "scanpaths_amd.h")).read(), flags=re.S)
-    kinds = {"int64_t": ctypes.c_int64, "double": ctypes.c_double, "int": ctypes.c_int}
-    for name, (ret, nargs) in NEW.items():
-        m = re.search(r"\b(int64_t|int)\s+" + name + r"\s*\(([^;{]*?)\)\s*;", txt, flags=re.S)
-        assert m, f"{name} is not declared in include/scanpaths_amd.h"
-        args = [a.strip() for a in " ".join(m.group(2).split()).split(",") if a.strip() != "void"]
-        assert m.group(1) == ret and len(args) == nargs, (name, args)
-        assert name in hip.SIGNATURES, name
-        cret, cargs = hip.SIGNATURES[name]
-        assert cret is ctypes.c_int and len(cargs) == nargs
-        for a, c in zip(args, cargs):
-            want = ctypes.c_void_p if "*" in a else kinds[a.split()[0]]
-            assert c is want, (name, a, c)
-        assert hasattr(lib, name), f"{name} is not exported"
-    assert not any(n.startswith(("sp_meanshift_", "sp_scan_sequence_", "sp_scan_cluster_strings_")) and n != "sp_meanshift_max_points"
-                   for n in hip.SIGNATURES), "no suffixed variants"
-    assert int(re.search(r"#define SP_ABI_VERSION (\d+)", txt).group(1)) == hip.ABI_VERSION == 4
+    lib = abi.assert_declared(NEW, prefixes=("sp_meanshift_", "sp_scan_sequence_", "sp_scan_cluster_strings_"))
     assert lib.sp_meanshift_max_points() == S.MAX_POINTS >= 1024
-    lib.sp_scan_max_fixations.restype = ctypes.c_int
     assert lib.sp_scan_max_fixations() == S.MAX_FIXATIONS == R.MAX_FIXATIONS == 64
 
 
 def test_launchers_refuse_bad_arguments_without_a_device():
     """SP_ENULL (-2) / SP_EINVAL (-1) come before the launch, so on a machine without a GPU too"""
-    lib = _lib()
+    lib = abi.raw_lib()
     p = 4096                                                        # any non-NULL value: nothing is dereferenced before the checks
     nan, inf = float("nan"), float("inf")
     MS, CS, SQ = lib.sp_meanshift, lib.sp_scan_cluster_strings, lib.sp_scan_sequence
