@@ -902,8 +902,6 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* dy, const fl
         dx[i] = y[i] > 0.f ? dy[i] : 0.f;
 }
 
-inline int ew_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, 256), 2048)); }
-
 }  // namespace
 
 extern "C" int64_t sp_bn_workspace(int64_t M, int C) {
@@ -940,7 +938,7 @@ extern "C" int sp_bn_apply(const float* x, const float* mean, const float* invst
     if (C % 4) return SP_EINVAL;
     const int64_t n4 = M * C / 4;
     SP_RESET_AMAX(y_amax, stream);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma,
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, (hipStream_t)stream, x, mean, invstd, gamma,
                        beta, residual, relu, n4, C, y, y_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -964,7 +962,7 @@ extern "C" int sp_bn_backward(const float* dy, const float* x, const float* y, c
     SP_LAUNCH_CHECK();
     const int64_t n4 = M * C / 4;
     SP_RESET_AMAX(dx_amax, s);
-    hipLaunchKernelGGL(bn_bwd_apply, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, coef, relu,
+    hipLaunchKernelGGL(bn_bwd_apply, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, s, dy, x, y, mean, invstd, gamma, coef, relu,
                        training, n4, C, dx, dres, dx_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1008,7 +1006,7 @@ extern "C" int sp_bn_fwd_split(const float* x, int64_t M, int C, float eps, floa
                            G, eps, momentum, gamma, beta, relu, mean, invstd, running_mean, running_var, ext, bound);
     SP_LAUNCH_CHECK();
     const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(bn_apply_split_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, x, mean, invstd, gamma, beta, residual, bound,
+    hipLaunchKernelGGL(bn_apply_split_kernel, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, s, x, mean, invstd, gamma, beta, residual, bound,
                        residual ? res_amax : nullptr, relu, n4, C, y, (uint16_t*)planes, y_scale, relu ? mask : nullptr);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1043,7 +1041,7 @@ extern "C" int sp_bn_bwd_split(const float* dy, const float* x, const unsigned l
                            G, gamma, mean, invstd, ext, dgamma, dbeta, coef, bound);
     SP_LAUNCH_CHECK();
     const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(bn_bwd_apply_split_kernel, dim3(ew_blocks(n4)), dim3(256), 0, s, dy, x, mask, mean, invstd, gamma, coef,
+    hipLaunchKernelGGL(bn_bwd_apply_split_kernel, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, s, dy, x, mask, mean, invstd, gamma, coef,
                        bound, n4, C, dx, dres, (uint16_t*)planes, dx_scale);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1072,8 +1070,7 @@ extern "C" int sp_colsum(const float* x, int64_t M, int C, int ld, float* out, i
 extern "C" int sp_rowsum(const float* x, int64_t M, int C, float scale, float* out, void* stream) {
     if (!x || !out) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(M, 4), 4096));
-    hipLaunchKernelGGL(rowsum_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, M, C, scale, out);
+    hipLaunchKernelGGL(rowsum_kernel, dim3(sp_ew_grid(M, 4096, 4)), dim3(256), 0, (hipStream_t)stream, x, M, C, scale, out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1082,7 +1079,7 @@ extern "C" int sp_rowsum_bwd(const float* dout, int64_t M, int C, float scale, f
     if (!dout || !dx) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
     const int64_t n4 = M * C / 4;
-    hipLaunchKernelGGL(rowsum_bwd_kernel, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, dout, n4, C, scale, dx);
+    hipLaunchKernelGGL(rowsum_bwd_kernel, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, (hipStream_t)stream, dout, n4, C, scale, dx);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1092,7 +1089,7 @@ extern "C" int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, flo
     if (!x || !y) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
     const int64_t total = (int64_t)N * Ho * Wo * (C / 4);
-    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, N, H, W, C, y, Ho, Wo,
+    hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(sp_ew_grid(total, 2048)), dim3(256), 0, (hipStream_t)stream, x, N, H, W, C, y, Ho, Wo,
                        argmax);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1103,7 +1100,7 @@ extern "C" int sp_maxpool3s2_bwd(const float* dy, const unsigned char* argmax, i
     if (!dy || !argmax || !dx) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
     const int64_t total = (int64_t)N * H * W * (C / 4);
-    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(ew_blocks(total) * 4), dim3(256), 0, (hipStream_t)stream, dy, argmax, N, H, W,
+    hipLaunchKernelGGL(maxpool_bwd_idx_kernel, dim3(sp_ew_grid(total, 2048) * 4), dim3(256), 0, (hipStream_t)stream, dy, argmax, N, H, W,
                        C, dx, Ho, Wo);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -1113,7 +1110,7 @@ extern "C" int sp_nchw_to_nhwc_pad(const float* x, int N, int C, int H, int W, i
     if (!x || !y) return SP_ENULL;
     if (Cp < C) return SP_EINVAL;
     const int64_t total = (int64_t)N * H * W * Cp;
-    hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, Cp, y);
+    hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel, dim3(sp_ew_grid(total, 2048)), dim3(256), 0, (hipStream_t)stream, x, N, C, H, W, Cp, y);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1121,7 +1118,7 @@ extern "C" int sp_nchw_to_nhwc_pad(const float* x, int N, int C, int H, int W, i
 extern "C" int sp_pad_lastdim(const float* x, int64_t rows, int Cin, int Cout, float* y, void* stream) {
     if (!x || !y) return SP_ENULL;
     const int64_t total = rows * Cout;
-    hipLaunchKernelGGL(pad_lastdim_kernel, dim3(ew_blocks(total)), dim3(256), 0, (hipStream_t)stream, x, rows, Cin, Cout, y);
+    hipLaunchKernelGGL(pad_lastdim_kernel, dim3(sp_ew_grid(total, 2048)), dim3(256), 0, (hipStream_t)stream, x, rows, Cin, Cout, y);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1130,7 +1127,7 @@ extern "C" int sp_add(const float* a, const float* b, float* out, int64_t n, voi
     if (!a || !b || !out) return SP_ENULL;
     const int64_t n4 = n / 4;
     if (n4 > 0) {
-        hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(n4)), dim3(256), 0, (hipStream_t)stream, a, b, out, n4);
+        hipLaunchKernelGGL(add_kernel, dim3(sp_ew_grid(n4, 2048)), dim3(256), 0, (hipStream_t)stream, a, b, out, n4);
         SP_LAUNCH_CHECK();
     }
     if (n4 * 4 < n) {
@@ -1156,8 +1153,8 @@ extern "C" int sp_sum_n(const float* const* inputs, int count, int64_t n, float*
         l.step[k] = steps ? steps[k] : -1;
     }
     SP_RESET_AMAX(out_amax, stream);
-    if (row_last) hipLaunchKernelGGL(sum_n_rows_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, l, out, n / 4, out_amax);
-    else hipLaunchKernelGGL(sum_n_kernel, dim3(ew_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, l, out, n / 4, out_amax);
+    if (row_last) hipLaunchKernelGGL(sum_n_rows_kernel, dim3(sp_ew_grid(n / 4, 2048)), dim3(256), 0, (hipStream_t)stream, l, out, n / 4, out_amax);
+    else hipLaunchKernelGGL(sum_n_kernel, dim3(sp_ew_grid(n / 4, 2048)), dim3(256), 0, (hipStream_t)stream, l, out, n / 4, out_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -1181,14 +1178,14 @@ extern "C" int sp_sum_n_mixed(const float* const* inputs, const void* const* pla
         l.sc[k] = scales[k];
     }
     SP_RESET_AMAX(out_amax, stream);
-    hipLaunchKernelGGL(sum_n_mixed_kernel, dim3(ew_blocks(n / 16)), dim3(256), 0, (hipStream_t)stream, l, out, n / 16, out_amax);
+    hipLaunchKernelGGL(sum_n_mixed_kernel, dim3(sp_ew_grid(n / 16, 2048)), dim3(256), 0, (hipStream_t)stream, l, out, n / 16, out_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 
 extern "C" int sp_relu_bwd(const float* dy, const float* y, int64_t n, float* dx, void* stream) {
     if (!dy || !y || !dx) return SP_ENULL;
-    hipLaunchKernelGGL(relu_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dy, y, n, dx);
+    hipLaunchKernelGGL(relu_bwd_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, dy, y, n, dx);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

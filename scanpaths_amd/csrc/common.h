@@ -1,7 +1,11 @@
 // Shared helpers for the gfx950 kernels.  wave = 64 lanes everywhere.
+// Host side, each launch rule stated once: sp_ew_grid (blocks of a grid-stride kernel), sp_span32_ok (operands within 32-bit byte
+// offsets), sp_launch_lds (dynamic LDS above the default: attribute latch, grid limits, launch, error check) and
+// sp_fill_wgrad_geom (the geometry the weight-gradient argument structs share).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include "../../include/scanpaths_amd.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -57,6 +61,48 @@ static inline bool sp_reset_needed(hipStream_t s) {
 
 
 static inline int64_t sp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Blocks of a grid-stride kernel over n items, `per_block` items per block and pass: at least 1, at most cap.  The kernels loop with
+// gridDim.x strides, so each kernel's cap (1024 / 2048 / 4096) stays at its call site.
+static inline int sp_ew_grid(int64_t n, int cap, int64_t per_block = 256) {
+    return (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, per_block), cap));
+}
+
+// Every operand (bytes without its 64-byte zero block) is addressable with the 32-bit byte offsets of the GEMM loaders.
+template <typename... B>
+static inline bool sp_span32_ok(B... bytes) { return (((int64_t)bytes + 64 < (1LL << 32)) && ...); }
+
+// Launch of a kernel that asks for more dynamic LDS than the default limit: MAX_LDS is granted once per kernel and process (the latch
+// is keyed on the kernel itself, a template VALUE: two instantiations of one kernel template share a type, not a latch; one device per
+// process), `lds` <= MAX_LDS is what this launch uses.  Grids outside x <= 2^31-1, y, z <= 65535 are SP_EINVAL.
+struct sp_grid { int64_t x, y = 1, z = 1; };
+template <auto Kern, int MAX_LDS, typename... A>
+static inline int sp_launch_lds(sp_grid g, int block, size_t lds, hipStream_t s, const A&... args) {
+    static bool attr_set = false;
+    if (!attr_set) {      // result discarded: a refused attribute shows up as the launch's own error below
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, MAX_LDS);
+        attr_set = true;
+    }
+    if (g.x < 1 || g.x > 0x7fffffff || g.y < 1 || g.y > 65535 || g.z < 1 || g.z > 65535) return SP_EINVAL;
+    hipLaunchKernelGGL(Kern, dim3((unsigned)g.x, (unsigned)g.y, (unsigned)g.z), dim3(block), lds, s, args...);
+    SP_LAUNCH_CHECK();
+    return SP_OK;
+}
+
+// The weight-gradient geometry every back-end's argument struct carries under the same member names (WgradArgs, HWArgs, HW2Args, W3Args):
+// M pixels in `splits` shares, each rounded up to whole K-tiles of `ktile` pixels.  What only some of them have (stride, ldy, the
+// operand pointers and scales) stays with the caller.
+template <typename Args>
+static inline void sp_fill_wgrad_geom(Args& a, const sp_wgrad_desc* d, int64_t M, int splits, int ktile) {
+    a.M = M;
+    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
+    a.KH = d->KH; a.KW = d->KW; a.pad = d->pad; a.dil = d->dil;
+    a.Ntot = d->KH * d->KW * d->Ci;
+    a.ldo = d->ldo;
+    a.splits = splits;
+    a.rows_per_split = sp_cdiv(sp_cdiv(M, splits), ktile) * ktile;
+    a.slab_stride = (int64_t)d->Co * d->ldo;
+}
 
 // Sites of the 7x7 stride-5 pad-2 duration conv (drt_layer_1) along a side of `len` pixels: floor((len + 4 - 7) / 5) + 1.  The ONE place
 // that computes it (decoder.hip head epilogue, head_direct.hip make_axis): written as the plain C expression, sides 1 and 2 gave 1 site

@@ -641,17 +641,8 @@ __global__ __launch_bounds__(256) void split3_wT_kernel(const float* w, int Co, 
 
 template <int MODE, int DBG>
 int launch_b3(const B3Args& a, hipStream_t s) {
-    auto kern = b3_kernel<MODE, DBG>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE * STAGE_B);
-        attr_set = true;
-    }
-    const int64_t grid = sp_cdiv(a.M, BM) * a.tiles_n;
-    if (grid <= 0 || grid > 0x7fffffff) return SP_EINVAL;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), NSTAGE * STAGE_B, s, a);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    constexpr int lds = NSTAGE * STAGE_B;
+    return sp_launch_lds<b3_kernel<MODE, DBG>, lds>({sp_cdiv(a.M, BM) * a.tiles_n}, 512, lds, s, a);
 }
 
 }  // namespace
@@ -660,8 +651,7 @@ extern "C" int sp_split3_bf16(const float* x, int64_t n, void* out, void* stream
     if (!x || !out) return SP_ENULL;
     if (n % 16) return SP_EINVAL;            // every row must be a multiple of 16 long
     const int64_t n4 = n / 4;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n4, 256), 4096));
-    hipLaunchKernelGGL(split3_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, n4, (uint16_t*)out);
+    hipLaunchKernelGGL(split3_kernel, dim3(sp_ew_grid(n4, 4096)), dim3(256), 0, (hipStream_t)stream, x, n4, (uint16_t*)out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -670,8 +660,7 @@ extern "C" int sp_split3_bf16_wT(const float* w, int Co, int taps, int Ci, void*
     if (!w || !out) return SP_ENULL;
     if (((int64_t)taps * Co) % 16) return SP_EINVAL;
     const int64_t total = (int64_t)Co * taps * Ci;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(total, 256), 4096));
-    hipLaunchKernelGGL(split3_wT_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, w, Co, taps, Ci, (uint16_t*)out);
+    hipLaunchKernelGGL(split3_wT_kernel, dim3(sp_ew_grid(total, 4096)), dim3(256), 0, (hipStream_t)stream, w, Co, taps, Ci, (uint16_t*)out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -695,7 +684,7 @@ extern "C" int sp_conv_igemm_bf16x3(const sp_conv_desc* d, const void* Xs, const
     a.tiles_n = (int)sp_cdiv(d->Nout, BN);
     a.alpha = d->alpha; a.beta = d->beta; a.relu = d->relu;
     const int64_t xb = 6LL * d->N_img * d->Hi * d->Wi * d->Kc, wb = 6LL * d->Nout * d->KH * d->KW * d->Kc;
-    if (xb + 64 >= (1LL << 32) || wb + 64 >= (1LL << 32)) return SP_EINVAL;      // 32-bit byte offsets in the loaders
+    if (!sp_span32_ok(xb, wb)) return SP_EINVAL;
     a.x_bytes = (uint32_t)xb; a.w_bytes = (uint32_t)wb;
     a.dbg = 0;
     if (a.M <= 0 || a.Nout <= 0) return SP_EINVAL;
@@ -722,36 +711,23 @@ extern "C" int sp_conv_wgrad_bf16x3(const sp_wgrad_desc* d, const void* Xsplit, 
     if (((uintptr_t)Xsplit | (uintptr_t)dYsplit) & 15) return SP_EINVAL;
     W3Args a;
     a.X = (const uint16_t*)Xsplit; a.dY = (const uint16_t*)dYsplit;
-    a.M = (int64_t)d->N_img * d->Ho * d->Wo;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-    a.Ntot = d->KH * d->KW * d->Ci;
-    a.ldo = d->ldo;
+    sp_fill_wgrad_geom(a, d, (int64_t)d->N_img * d->Ho * d->Wo, w3_splits(d), 16);
+    a.stride = d->stride;
     a.tiles_n = (int)sp_cdiv(a.Ntot, 128);
-    a.splits = w3_splits(d);
     if (a.splits > 1 && !workspace) return SP_ENULL;
-    a.rows_per_split = sp_cdiv(sp_cdiv(a.M, a.splits), 16) * 16;
-    a.slab_stride = (int64_t)d->Co * d->ldo;
     a.out = a.splits > 1 ? (float*)workspace : dW;
     a.alpha = d->alpha; a.beta = d->beta;
     if (a.M <= 0) return SP_EINVAL;
     const int64_t xb = 6LL * d->N_img * d->Hi * d->Wi * d->Ci, yb = 6LL * a.M * d->Co;
-    if (xb + 64 >= (1LL << 32) || yb + 64 >= (1LL << 32) || d->Ho * d->Wo < 1) return SP_EINVAL;
+    if (!sp_span32_ok(xb, yb) || d->Ho * d->Wo < 1) return SP_EINVAL;
     a.x_bytes = (uint32_t)xb; a.y_bytes = (uint32_t)yb;
     hipStream_t s = (hipStream_t)stream;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(w3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  NSTAGE * WSTAGE_B);
-        attr_set = true;
-    }
-    const int64_t grid = sp_cdiv(d->Co, 256) * a.tiles_n;
-    hipLaunchKernelGGL(w3_kernel, dim3((unsigned)grid, (unsigned)a.splits), dim3(512), NSTAGE * WSTAGE_B, s, a);
-    SP_LAUNCH_CHECK();
+    constexpr int lds = NSTAGE * WSTAGE_B;
+    const int rc = sp_launch_lds<w3_kernel, lds>({sp_cdiv(d->Co, 256) * a.tiles_n, a.splits}, 512, lds, s, a);
+    if (rc != SP_OK) return rc;
     if (a.splits > 1) {
         const int64_t total = (int64_t)d->Co * a.Ntot;
-        const int blocks = (int)std::min<int64_t>(sp_cdiv(total, 256), 4096);
-        hipLaunchKernelGGL(wgrad3_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)workspace, dW, d->Co, a.Ntot,
+        hipLaunchKernelGGL(wgrad3_reduce_kernel, dim3(sp_ew_grid(total, 4096)), dim3(256), 0, s, (const float*)workspace, dW, d->Co, a.Ntot,
                            d->ldo, a.splits, a.slab_stride, d->alpha, d->beta);
         SP_LAUNCH_CHECK();
     }

@@ -1983,39 +1983,20 @@ __global__ __launch_bounds__(256) void split2_cols_kernel(const float* x, int64_
 
 template <int MODE, int NPROD, bool CBM, bool LSTM = false, bool HALO = false, int DBG = 0>
 int launch_h2(const H2Args& a, hipStream_t s) {
-    auto kern = h2_kernel<MODE, NPROD, CBM, LSTM, HALO, DBG>;
     constexpr int lds = HALO ? HALO_LDS : HNSTAGE * HSTAGE;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    const int64_t grid = sp_cdiv(a.M, HBM) * a.tiles_n;
-    if (grid <= 0 || grid > 0x7fffffff) return SP_EINVAL;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, s, a);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return sp_launch_lds<h2_kernel<MODE, NPROD, CBM, LSTM, HALO, DBG>, lds>({sp_cdiv(a.M, HBM) * a.tiles_n}, 512, lds, s, a);
 }
 
 template <int NPROD, int DBG = 0>
 int launch_hw(const HWArgs& a, int Co, hipStream_t s) {
-    auto kern = hw_kernel<NPROD, DBG>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, HNSTAGE * HWSTAGE);
-        attr_set = true;
-    }
-    const int64_t grid = sp_cdiv(Co, 256) * a.tiles_n;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)a.splits), dim3(512), HNSTAGE * HWSTAGE, s, a);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    constexpr int lds = HNSTAGE * HWSTAGE;
+    return sp_launch_lds<hw_kernel<NPROD, DBG>, lds>({sp_cdiv(Co, 256) * a.tiles_n, a.splits}, 512, lds, s, a);
 }
 
 int launch_amax(const float* x, int64_t n, unsigned* amax, hipStream_t s) {
     SP_RESET_AMAX(amax, s);   // scratch word of the caller's scale buffer: zeroed here unless the host hands in zeroed single-use slots (see common.h)
     const int64_t n4 = n / 4;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n4, 256 * 4), 1024));
-    hipLaunchKernelGGL(amax_kernel, dim3(blocks), dim3(256), 0, s, x, n4, n, amax);
+    hipLaunchKernelGGL(amax_kernel, dim3(sp_ew_grid(n4, 1024, 256 * 4)), dim3(256), 0, s, x, n4, n, amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -2033,8 +2014,7 @@ extern "C" int sp_split2_f16(const float* x, int64_t n, void* out, float* scale_
         if (rc != SP_OK) return rc;
     }
     const int64_t n4 = n / 4;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n4, 256), 4096));
-    hipLaunchKernelGGL(split2_kernel, dim3(blocks), dim3(256), 0, s, x, n4, amax, (uint16_t*)out, scale_amax);
+    hipLaunchKernelGGL(split2_kernel, dim3(sp_ew_grid(n4, 4096)), dim3(256), 0, s, x, n4, amax, (uint16_t*)out, scale_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -2047,8 +2027,7 @@ extern "C" int sp_split2_f16_wT(const float* w, int Co, int taps, int Ci, void* 
     const int64_t total = (int64_t)Co * taps * Ci;
     const int rc = launch_amax(w, total, amax, s);
     if (rc != SP_OK) return rc;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(total, 256), 4096));
-    hipLaunchKernelGGL(split2_wT_kernel, dim3(blocks), dim3(256), 0, s, w, Co, taps, Ci, amax, (uint16_t*)out, scale_amax);
+    hipLaunchKernelGGL(split2_wT_kernel, dim3(sp_ew_grid(total, 4096)), dim3(256), 0, s, w, Co, taps, Ci, amax, (uint16_t*)out, scale_amax);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -2083,7 +2062,7 @@ extern "C" int sp_split2_f16_wT_rows(const float* w, int nbatch, int Co, int tap
 // activations x [rows][C] (C % 16 == 0) with one scale per channel; scratch: sp_split2_f16_cols_workspace(rows, C) bytes
 static int colamax_blocks(int64_t rows, int C_) {
     const int C4 = C_ / 4, cg_per = std::min(C4, 256), rpb = 256 / cg_per;
-    return (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(rows, (int64_t)rpb * 4), COLAMAX_MAXBLK));
+    return sp_ew_grid(rows, COLAMAX_MAXBLK, rpb * 4);
 }
 extern "C" int64_t sp_split2_f16_cols_workspace(int64_t rows, int C_) {
     if (rows < 1 || C_ < 16 || C_ % 16) return 0;
@@ -2099,8 +2078,7 @@ extern "C" int sp_split2_f16_cols(const float* x, int64_t rows, int C_, void* ou
     hipLaunchKernelGGL(colamax_final_kernel, dim3((unsigned)sp_cdiv(C_, 32)), dim3(256), 0, s, (const float*)scratch, nblk, C_, col_scale);
     SP_LAUNCH_CHECK();
     const int64_t n4 = rows * (C_ / 4);
-    const int blocks2 = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n4, 256), 4096));
-    hipLaunchKernelGGL(split2_cols_kernel, dim3(blocks2), dim3(256), 0, s, x, n4, C_, (const float*)col_scale, (uint16_t*)out);
+    hipLaunchKernelGGL(split2_cols_kernel, dim3(sp_ew_grid(n4, 4096)), dim3(256), 0, s, x, n4, C_, (const float*)col_scale, (uint16_t*)out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -2110,6 +2088,23 @@ extern "C" int sp_split2_f16_cols(const float* x, int64_t rows, int C_, void* ou
 static bool halo_applies(const sp_conv_desc* d) {
     return d->KH == 3 && d->KW == 3 && d->stride == 1 && d->dil == 1 && d->pad == 1 && d->Wo == HALO_W && d->Wi == HALO_W &&
            d->Hi == d->Ho && (d->Ho * d->Wo) % HBM == 0 && d->Kc % 32 == 0;
+}
+
+// What the descriptor alone decides of a zero-initialised H2Args: operands and scales, geometry, K-tile counts, operand spans.  The
+// epilogue, batching, row sparsity and tiles_n are the caller's.  false: an operand span or M is beyond the kernels' 32-bit arithmetic.
+static bool h2_args_from_desc(const sp_conv_desc* d, const void* Xs, const float* x_scale, const void* Ws, const float* w_scale, H2Args& a) {
+    a.X = (const uint16_t*)Xs; a.W = (const uint16_t*)Ws;
+    a.sx = x_scale; a.sw = w_scale; a.sw_rows = d->w_scale_rows ? 1 : 0;
+    a.M = (int64_t)d->N_img * d->Ho * d->Wo * d->nbatch;
+    a.Hi = d->Hi; a.Wi = d->Wi; a.Kc = d->Kc; a.ldx = d->ldx;
+    a.Ho = d->Ho; a.Wo = d->Wo; a.Nout = d->Nout; a.ldc = d->ldc;
+    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
+    a.ldwb = 4 * (int64_t)d->KH * d->KW * d->Kc;
+    a.ncblk = d->Kc / 32;
+    a.nkt = d->KH * d->KW * a.ncblk;
+    const int64_t xb = 4LL * d->nbatch * d->N_img * d->Hi * d->Wi * d->ldx, wb = 4LL * d->nbatch * d->Nout * d->KH * d->KW * d->Kc;
+    a.x_bytes = (uint32_t)xb; a.w_bytes = (uint32_t)wb;
+    return sp_span32_ok(xb, wb) && a.M > 0 && a.M < (1LL << 31);
 }
 
 static int conv_igemm_f16(const sp_conv_desc* d, const void* Xs, const float* x_scale, const void* Ws, const float* w_scale,
@@ -2127,27 +2122,16 @@ static int conv_igemm_f16(const sp_conv_desc* d, const void* Xs, const float* x_
         if (st_partial || nprod != 3) return SP_EINVAL;
     }
     H2Args a{};
-    a.X = (const uint16_t*)Xs; a.W = (const uint16_t*)Ws; a.bias = bias; a.C = out;
-    a.sx = x_scale; a.sw = w_scale; a.sw_rows = d->w_scale_rows ? 1 : 0;
+    if (!h2_args_from_desc(d, Xs, x_scale, Ws, w_scale, a) || a.Nout <= 0) return SP_EINVAL;
+    a.bias = bias; a.C = out;
     // row sparsity: the data gradient of a conv (tiles inside one sample) or a batched forward GEMM with one item per sample
     a.row_last = ((d->mode == 1 && d->nbatch == 1) || (d->mode == 0 && d->nbatch > 1)) ? d->row_last : nullptr; a.row_step = d->row_step;
     a.row_nimg = (a.row_last && d->mode == 1 && d->nbatch == 1 && d->N_img <= 64 && ((int64_t)d->Ho * d->Wo) % HBM == 0 &&
                   sp_tuning_get(SP_TUNE_ROW_ORDER, 1) == 1) ? d->N_img : 0;
-    a.M = rows_b * d->nbatch;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Kc = d->Kc; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Nout = d->Nout; a.ldc = d->ldc;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
     a.w_bstride = d->nbatch > 1 ? 4 * d->strideW : 0;
     a.rows_per_batch = (int)rows_b;
-    a.ldwb = 4 * (int64_t)d->KH * d->KW * d->Kc;
-    a.ncblk = d->Kc / 32;
-    a.nkt = d->KH * d->KW * a.ncblk;
     a.tiles_n = (int)sp_cdiv(d->Nout, HBN);
     a.alpha = d->alpha; a.beta = d->beta; a.relu = d->relu;
-    const int64_t xb = 4LL * d->nbatch * d->N_img * d->Hi * d->Wi * d->ldx, wb = 4LL * d->nbatch * d->Nout * d->KH * d->KW * d->Kc;
-    if (xb + 64 >= (1LL << 32) || wb + 64 >= (1LL << 32)) return SP_EINVAL;      // 32-bit byte offsets in the loaders
-    a.x_bytes = (uint32_t)xb; a.w_bytes = (uint32_t)wb;
-    if (a.M <= 0 || a.M >= (1LL << 31) || a.Nout <= 0) return SP_EINVAL;             // 32-bit pixel arithmetic in the kernels
     hipStream_t st = (hipStream_t)stream;
     const bool f = d->mode == 0;
     // channel-block-major K order: only where it is defined (several taps, mask fits, stride-1 data gradient)
@@ -2217,20 +2201,10 @@ extern "C" int sp_gateconv_lstm_f16x2(const sp_conv_desc* d, const void* Hs, con
     if (((uintptr_t)xg | (uintptr_t)c_prev | (uintptr_t)gates | (uintptr_t)c_out | (uintptr_t)h_out) & 15) return SP_EINVAL;
     if (d->w_scale_rows && ((uintptr_t)w_scale & 15)) return SP_EINVAL;
     H2Args a{};
-    a.X = (const uint16_t*)Hs; a.W = (const uint16_t*)Ws; a.bias = nullptr; a.C = nullptr;
-    a.sx = h_scale; a.sw = w_scale; a.sw_rows = d->w_scale_rows ? 1 : 0;
-    a.M = (int64_t)d->N_img * P;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Kc = d->Kc; a.ldx = d->Kc;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Nout = d->Nout; a.ldc = d->Nout;
-    a.KH = d->KH; a.KW = d->KW; a.stride = 1; a.pad = d->pad; a.dil = d->dil;
-    a.ldwb = 4 * (int64_t)d->KH * d->KW * d->Kc;
-    a.ncblk = d->Kc / 32;
-    a.nkt = d->KH * d->KW * a.ncblk;
+    if (!h2_args_from_desc(d, Hs, h_scale, Ws, w_scale, a)) return SP_EINVAL;      // (nbatch 1, stride 1, ldx = Kc, Hi x Wi = P: checked above)
+    a.ldc = d->Nout;                                                               // d->ldc is ignored: the cell epilogue writes no C
     a.tiles_n = d->Kc / 32;
-    a.alpha = 1.f; a.beta = 0; a.relu = 0;
-    const int64_t xb = 4LL * a.M * d->Kc, wb = 4LL * d->Nout * d->KH * d->KW * d->Kc;
-    if (xb + 64 >= (1LL << 32) || wb + 64 >= (1LL << 32) || a.M <= 0) return SP_EINVAL;
-    a.x_bytes = (uint32_t)xb; a.w_bytes = (uint32_t)wb;
+    a.alpha = 1.f;
     a.l_xg = xg; a.l_cprev = c_prev; a.l_spcol = spcol; a.l_wc = wc;
     if (hout_planes && (!hout_scale || !(hout_bound > 0.f) || ((uintptr_t)hout_planes & 15))) return SP_EINVAL;
     a.l_gates = gates; a.l_c = c_out; a.l_h = h_out; a.l_hamax = h_amax;
@@ -2254,11 +2228,9 @@ static int launch_hw_reduce(const HWScales& sc, const float* slab, float* dW, in
                             float alpha, int beta, hipStream_t s) {
     const int64_t total = (int64_t)Co * Ntot;
     if (Ntot % 4 == 0 && ldo % 4 == 0 && slab_stride % 4 == 0 && sc.Ci % 4 == 0 && (((uintptr_t)slab | (uintptr_t)dW) & 15) == 0) {
-        const int blocks = (int)std::min<int64_t>(sp_cdiv(total / 4, 256), 4096);
-        hipLaunchKernelGGL(hw_reduce4_kernel, dim3(blocks), dim3(256), 0, s, slab, dW, Co, Ntot / 4, ldo / 4, splits, slab_stride / 4, alpha, sc, beta);
+        hipLaunchKernelGGL(hw_reduce4_kernel, dim3(sp_ew_grid(total / 4, 4096)), dim3(256), 0, s, slab, dW, Co, Ntot / 4, ldo / 4, splits, slab_stride / 4, alpha, sc, beta);
     } else {
-        const int blocks = (int)std::min<int64_t>(sp_cdiv(total, 256), 4096);
-        hipLaunchKernelGGL(hw_reduce_kernel, dim3(blocks), dim3(256), 0, s, slab, dW, Co, Ntot, ldo, splits, slab_stride, alpha, sc, beta);
+        hipLaunchKernelGGL(hw_reduce_kernel, dim3(sp_ew_grid(total, 4096)), dim3(256), 0, s, slab, dW, Co, Ntot, ldo, splits, slab_stride, alpha, sc, beta);
     }
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -2283,23 +2255,18 @@ static int conv_wgrad_f16(const sp_wgrad_desc* d, const void* Xsplit, const floa
     a.sx_vec = d->x_scale_vec ? 1 : 0; a.sy_vec = d->y_scale_vec ? 1 : 0;
     if (batched && (a.sx_vec || a.sy_vec)) return SP_EINVAL;      // per-channel scales: one vector per GEMM
     a.row_last = batched ? d->row_last : nullptr; a.row_step = d->row_step;
-    a.M = rows_b * d->nbatch;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.ldy = d->ldy;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-    a.Ntot = d->KH * d->KW * d->Ci;
-    a.ldo = d->ldo;
+    // batched: one "split" per item, rows_b pixels each (a multiple of 32, checked above)
+    sp_fill_wgrad_geom(a, d, rows_b * d->nbatch, batched ? d->nbatch : hw_splits(d), 32);
+    a.ldy = d->ldy; a.stride = d->stride;
     a.tiles_n = (int)sp_cdiv(a.Ntot, 128);
     a.Nvalid = std::min(a.Ntot, d->ldo);          // batched with Ci padded up to 16 k: only the first ldo columns exist
     a.batched = batched ? 1 : 0;
-    a.splits = batched ? d->nbatch : hw_splits(d);
     if (!batched && a.splits > 1 && !workspace) return SP_ENULL;
-    a.rows_per_split = batched ? rows_b : sp_cdiv(sp_cdiv(a.M, a.splits), 32) * 32;
-    a.slab_stride = (int64_t)d->Co * d->ldo;
     a.out = (!batched && a.splits > 1) ? (float*)workspace : dW;
     a.alpha = d->alpha; a.beta = d->beta;
     if (a.M <= 0) return SP_EINVAL;
     const int64_t xb = 4LL * d->nbatch * d->N_img * d->Hi * d->Wi * d->Ci, yb = 4LL * a.M * d->ldy;
-    if (xb + 64 >= (1LL << 32) || yb + 64 >= (1LL << 32) || d->Ho * d->Wo < 1) return SP_EINVAL;
+    if (!sp_span32_ok(xb, yb) || d->Ho * d->Wo < 1) return SP_EINVAL;
     a.x_bytes = (uint32_t)xb; a.y_bytes = (uint32_t)yb;
     hipStream_t s = (hipStream_t)stream;
     int rc = -1000;
@@ -2368,7 +2335,7 @@ static bool hw2_applies(const sp_wgrad_desc* d, int nseg) {
     const int64_t M = (int64_t)d->N_img * d->Ho * d->Wo;
     return d->stride == 1 && d->Wo % 32 == 0 && d->Co % 256 == 0 && d->Ci % 16 == 0 && ((int64_t)d->KH * d->KW * d->Ci) % 256 == 0 &&
            d->ldx == d->Ci && d->ldy >= d->Co && d->ldy % 16 == 0 && d->ldo % 4 == 0 && d->ldo >= d->KH * d->KW * d->Ci && M >= 2048 &&
-           M < (1LL << 31) && d->Hi < 32768 && d->Wi < 32768 && 4LL * d->N_img * d->Hi * d->Wi * d->Ci + 64 < (1LL << 32);
+           M < (1LL << 31) && d->Hi < 32768 && d->Wi < 32768 && sp_span32_ok(4LL * d->N_img * d->Hi * d->Wi * d->Ci);
 }
 extern "C" int64_t sp_conv_wgrad_f16x2_multi_workspace(const sp_wgrad_desc* d, int nseg) {
     if (!d || !hw2_applies(d, nseg)) return 0;
@@ -2393,23 +2360,13 @@ extern "C" int sp_conv_wgrad_f16x2_multi(const sp_wgrad_desc* d, int nseg, const
     }
     sc.sx_vec = d->x_scale_vec ? 1 : 0; sc.sy_vec = d->y_scale_vec ? 1 : 0; sc.nseg = nseg; sc.Ci = d->Ci;
     a.slab = (float*)workspace;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.ldy = d->ldy;
-    a.KH = d->KH; a.KW = d->KW; a.pad = d->pad; a.dil = d->dil;
-    a.Ntot = d->KH * d->KW * d->Ci; a.ldo = d->ldo; a.tiles_n = a.Ntot / 256;
-    a.splits = hw2_splits(d, nseg);
-    a.M = (int)((int64_t)d->N_img * d->Ho * d->Wo);
-    a.rows_per_split = (int)(sp_cdiv(sp_cdiv(a.M, a.splits), 32) * 32);
-    a.slab_stride = (int64_t)d->Co * d->ldo;
+    sp_fill_wgrad_geom(a, d, (int64_t)d->N_img * d->Ho * d->Wo, hw2_splits(d, nseg), 32);
+    a.ldy = d->ldy;
+    a.tiles_n = a.Ntot / 256;
     a.x_bytes = (uint32_t)(4LL * d->N_img * d->Hi * d->Wi * d->Ci);
     hipStream_t s = (hipStream_t)stream;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(hw2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, HW2_LDS);
-        attr_set = true;
-    }
-    const unsigned tiles = (unsigned)((d->Co / 256) * a.tiles_n);
-    hipLaunchKernelGGL(hw2_kernel, dim3(tiles, (unsigned)(nseg * a.splits)), dim3(512), HW2_LDS, s, a);
-    SP_LAUNCH_CHECK();
+    const int rc = sp_launch_lds<hw2_kernel, HW2_LDS>({(d->Co / 256) * a.tiles_n, nseg * a.splits}, 512, HW2_LDS, s, a);
+    if (rc != SP_OK) return rc;
     return launch_hw_reduce(sc, (const float*)workspace, dW, d->Co, a.Ntot, d->ldo, a.splits, a.slab_stride, d->alpha, d->beta, s);
 }
 

@@ -345,35 +345,25 @@ template <int BM, int BN, int WAVES_M, int WAVES_N, int MODE, bool SMALLC>
 int launch(const IgemmArgs& a, int nbatch, hipStream_t s, void* b_workspace = nullptr) {
     constexpr int LDB = (MODE == 0) ? (BK + 4) : (BN + 4);
     constexpr int STAGE = BM * LDA + ((MODE == 0) ? BN * LDB : BK * LDB);
-    const size_t lds = 2 * STAGE * sizeof(float);
-    auto kern = igemm_kernel<BM, BN, WAVES_M, WAVES_N, MODE, SMALLC>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    const int64_t tiles_m = sp_cdiv(a.M, BM);
+    constexpr int lds = 2 * STAGE * (int)sizeof(float);
+    constexpr auto kern = igemm_kernel<BM, BN, WAVES_M, WAVES_N, MODE, SMALLC>;
     IgemmArgs b = a;
     b.tiles_n = (int)sp_cdiv(a.Nout, BN);
-    const int64_t grid = tiles_m * b.tiles_n;
-    if (grid <= 0 || grid > 0x7fffffff) return SP_EINVAL;
+    const int64_t grid = sp_cdiv(a.M, BM) * b.tiles_n;
     if (b.ksplit > 1) {
         float* final_out = b.C;
         const float* bias = b.bias;
         b.C = (float*)b_workspace;      // slabs
         b.slab_stride = b.M * b.Nout;
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid, 1, (unsigned)b.ksplit), dim3(256), lds, s, b);
-        SP_LAUNCH_CHECK();
+        const int rc = sp_launch_lds<kern, lds>({grid, 1, b.ksplit}, 256, lds, s, b);
+        if (rc != SP_OK) return rc;
         const int64_t total = b.M * b.Nout;
-        const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(total, 256), 2048));
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)b_workspace, b.ksplit, b.slab_stride,
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(sp_ew_grid(total, 2048)), dim3(256), 0, s, (const float*)b_workspace, b.ksplit, b.slab_stride,
                            b.M, b.Nout, b.ldc, bias, b.alpha, b.beta, b.relu, final_out);
         SP_LAUNCH_CHECK();
         return SP_OK;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid, (unsigned)nbatch), dim3(256), lds, s, b);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return sp_launch_lds<kern, lds>({grid, nbatch}, 256, lds, s, b);
 }
 
 }  // namespace

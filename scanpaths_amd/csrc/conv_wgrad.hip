@@ -236,35 +236,21 @@ extern "C" int sp_conv_wgrad(const sp_wgrad_desc* d, const float* X, const float
     if (d->nbatch < 1) return SP_EINVAL;
     WgradArgs a;
     a.X = X; a.dY = dY;
-    a.M = (int64_t)d->N_img * d->Ho * d->Wo;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ci = d->Ci; a.ldx = d->ldx;
-    a.Ho = d->Ho; a.Wo = d->Wo; a.Co = d->Co; a.ldy = d->ldy;
-    a.KH = d->KH; a.KW = d->KW; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
-    a.Ntot = d->KH * d->KW * d->Ci;
-    a.ldo = d->ldo;
+    sp_fill_wgrad_geom(a, d, (int64_t)d->N_img * d->Ho * d->Wo, choose_splits(d), BKP);
+    a.ldx = d->ldx; a.ldy = d->ldy; a.stride = d->stride;
     a.tiles_n = (int)sp_cdiv(a.Ntot, BN);
-    a.splits = choose_splits(d);
     if (a.splits > 1 && !workspace) return SP_ENULL;
-    a.rows_per_split = sp_cdiv(sp_cdiv(a.M, a.splits), BKP) * BKP;
-    a.slab_stride = (int64_t)d->Co * d->ldo;
     a.out = a.splits > 1 ? (float*)workspace : dW;
     a.alpha = d->alpha; a.beta = d->beta;
     a.strideX = d->strideX; a.strideY = d->strideY; a.strideO = d->strideO;
     if (a.M <= 0) return SP_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t grid = sp_cdiv(d->Co, BM) * a.tiles_n;
-    const size_t lds = 2 * 2 * BKP * LDS_LD * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)grid, (unsigned)a.splits, (unsigned)d->nbatch), dim3(256), lds, s, a);
-    SP_LAUNCH_CHECK();
+    constexpr int lds = 2 * 2 * BKP * LDS_LD * (int)sizeof(float);
+    const int rc = sp_launch_lds<wgrad_kernel, lds>({sp_cdiv(d->Co, BM) * a.tiles_n, a.splits, d->nbatch}, 256, lds, s, a);
+    if (rc != SP_OK) return rc;
     if (a.splits > 1) {
         const int64_t total = (int64_t)d->Co * a.Ntot;
-        const int blocks = (int)std::min<int64_t>(sp_cdiv(total, 256), 4096);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(blocks), dim3(256), 0, s, (const float*)workspace, dW, d->Co,
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(sp_ew_grid(total, 4096)), dim3(256), 0, s, (const float*)workspace, dW, d->Co,
                            a.Ntot, d->ldo, a.splits, a.slab_stride, d->alpha, d->beta);
         SP_LAUNCH_CHECK();
     }

@@ -6,8 +6,6 @@
 
 namespace {
 
-inline int ew_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, 256), 2048)); }
-
 __device__ __forceinline__ float sigmoidf_(float x) { return sp_sigmoid(x); }      // common.h: the fused cell epilogue uses the same pair
 
 // ------------------------------------------------------------------------------------------------
@@ -780,7 +778,7 @@ extern "C" int sp_lstm_pointwise_fwd(const float* xg, const float* hg, const flo
                                      float* gates, float* c_out, float* h_out, void* stream) {
     if (!xg || !gates || !c_out || !h_out) return SP_ENULL;
     if (C % 4) return SP_EINVAL;
-    hipLaunchKernelGGL(lstm_fwd_kernel, dim3(ew_blocks(rows * C / 4)), dim3(256), 0, (hipStream_t)stream, xg, hg, c_prev,
+    hipLaunchKernelGGL(lstm_fwd_kernel, dim3(sp_ew_grid(rows * C / 4, 2048)), dim3(256), 0, (hipStream_t)stream, xg, hg, c_prev,
                        rows, C, gates, c_out, h_out);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -812,7 +810,7 @@ extern "C" int sp_rank1_dwc(const float* dpre, const float* spcol, int B, int P,
                        N3, KP, nchunk, (float*)workspace);
     SP_LAUNCH_CHECK();
     const int64_t n = (int64_t)B * N3 * KP;
-    hipLaunchKernelGGL(rank1_dwc_reduce_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, n,
+    hipLaunchKernelGGL(rank1_dwc_reduce_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, n,
                        nchunk, dwc);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -831,7 +829,7 @@ extern "C" int sp_sempool_fwd(const float* a, const float* vf, int S, int B, int
     hipLaunchKernelGGL(sempool_fwd_kernel, dim3(nch, B), dim3(256), 0, (hipStream_t)stream, a, vf, S, B, P, C, (float*)workspace);
     SP_LAUNCH_CHECK();
     const int64_t n = (int64_t)B * S * C;
-    hipLaunchKernelGGL(sempool_finish_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nch,
+    hipLaunchKernelGGL(sempool_finish_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, (const float*)workspace, nch,
                        n, alpha, out, S, C, osb, oss);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -842,7 +840,7 @@ extern "C" int sp_sempool_bwd(const float* dout, const float* out, const float* 
     if (!dout || !out || !a || !vf || !da || !dvf) return SP_ENULL;
     if (S < 1 || S > 2 || B < 1 || P < 1 || C % 4) return SP_EINVAL;
     const int64_t zsb = sbc ? C : (int64_t)S * C, zss = sbc ? (int64_t)B * C : C;
-    hipLaunchKernelGGL(sempool_bwd_kernel, dim3(ew_blocks((int64_t)B * P * 64)), dim3(256), 0, (hipStream_t)stream, dout, out, a,
+    hipLaunchKernelGGL(sempool_bwd_kernel, dim3(sp_ew_grid((int64_t)B * P * 64, 2048)), dim3(256), 0, (hipStream_t)stream, dout, out, a,
                        vf, S, B, P, C, alpha, da, dvf, row_last, row_step, zsb, zss);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -859,7 +857,7 @@ extern "C" int sp_lstm_pointwise_bwd(const float* dh, const float* dc, const flo
     if (row_last && (rows_per_sample < 1 || rows % rows_per_sample)) return SP_EINVAL;
     SP_RESET_AMAX(dpre_amax, stream);
     SP_RESET_AMAX(dcp_amax, stream);
-    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(ew_blocks(rows * C / 4)), dim3(256), 0, (hipStream_t)stream, dh, dc, gates,
+    hipLaunchKernelGGL(lstm_bwd_kernel, dim3(sp_ew_grid(rows * C / 4, 2048)), dim3(256), 0, (hipStream_t)stream, dh, dc, gates,
                        c_prev, c_out, rows, C, dpre, dc_prev, dpre_amax, dcp_amax, dh_amax, dc_amax, c_bound, cprev_bound,
                        (uint16_t*)planes, dpre_scale, row_last, row_step, row_last ? rows_per_sample : 1);
     SP_LAUNCH_CHECK();
@@ -869,14 +867,14 @@ extern "C" int sp_lstm_pointwise_bwd(const float* dh, const float* dc, const flo
 extern "C" int sp_im2col3x3_1ch(const float* maps, int S, int R, int H, int W, int ldk, float* col, void* stream) {
     if (!maps || !col) return SP_ENULL;
     if (S < 1 || 9 * S > ldk) return SP_EINVAL;
-    hipLaunchKernelGGL(im2col1_multi_kernel, dim3(ew_blocks((int64_t)R * H * W * ldk)), dim3(256), 0, (hipStream_t)stream, maps, S, R, H, W, ldk, col);
+    hipLaunchKernelGGL(im2col1_multi_kernel, dim3(sp_ew_grid((int64_t)R * H * W * ldk, 2048)), dim3(256), 0, (hipStream_t)stream, maps, S, R, H, W, ldk, col);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
 extern "C" int sp_col2im3x3_1ch(const float* dcol, int S, int R, int H, int W, int ldk, float* dmaps, void* stream) {
     if (!dcol || !dmaps) return SP_ENULL;
     if (S < 1 || 9 * S > ldk) return SP_EINVAL;
-    hipLaunchKernelGGL(col2im1_multi_kernel, dim3(ew_blocks((int64_t)S * R * H * W)), dim3(256), 0, (hipStream_t)stream, dcol, S, R, H, W, ldk, dmaps);
+    hipLaunchKernelGGL(col2im1_multi_kernel, dim3(sp_ew_grid((int64_t)S * R * H * W, 2048)), dim3(256), 0, (hipStream_t)stream, dcol, S, R, H, W, ldk, dmaps);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -901,7 +899,7 @@ extern "C" int sp_listatt_bwd(const float* dmem, const float* L, const float* u,
 
 extern "C" int sp_mulrelu_fwd(const float* a, const float* b, int64_t n, int64_t nb, float* out, void* stream) {
     if (!a || !b || !out) return SP_ENULL;
-    hipLaunchKernelGGL(mulrelu_fwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, a, b, n, nb, out);
+    hipLaunchKernelGGL(mulrelu_fwd_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, a, b, n, nb, out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -909,7 +907,7 @@ extern "C" int sp_mulrelu_fwd(const float* a, const float* b, int64_t n, int64_t
 extern "C" int sp_mulrelu_bwd(const float* dout, const float* a, const float* b, const float* out, int64_t n, int64_t nb,
                               float* da, float* db_partial, void* stream) {
     if (!dout || !a || !b || !out || !da || !db_partial) return SP_ENULL;
-    hipLaunchKernelGGL(mulrelu_bwd_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, dout, a, b, out, n, nb, da,
+    hipLaunchKernelGGL(mulrelu_bwd_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, dout, a, b, out, n, nb, da,
                        db_partial);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -918,7 +916,7 @@ extern "C" int sp_mulrelu_bwd(const float* dout, const float* a, const float* b,
 extern "C" int sp_select_rows(const float* a, const float* b, const unsigned char* sel, int64_t rows, int64_t len, float* out,
                               void* stream) {
     if (!a || !b || !sel || !out) return SP_ENULL;
-    hipLaunchKernelGGL(select_rows_kernel, dim3(ew_blocks(rows * len)), dim3(256), 0, (hipStream_t)stream, a, b, sel, rows, len,
+    hipLaunchKernelGGL(select_rows_kernel, dim3(sp_ew_grid(rows * len, 2048)), dim3(256), 0, (hipStream_t)stream, a, b, sel, rows, len,
                        out);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -927,7 +925,7 @@ extern "C" int sp_select_rows(const float* a, const float* b, const unsigned cha
 extern "C" int sp_select_rows_bwd(const float* dout, const unsigned char* sel, int64_t rows, int64_t len, float* da, float* db,
                                   void* stream) {
     if (!dout || !sel || !da || !db) return SP_ENULL;
-    hipLaunchKernelGGL(select_rows_bwd_kernel, dim3(ew_blocks(rows * len)), dim3(256), 0, (hipStream_t)stream, dout, sel, rows,
+    hipLaunchKernelGGL(select_rows_bwd_kernel, dim3(sp_ew_grid(rows * len, 2048)), dim3(256), 0, (hipStream_t)stream, dout, sel, rows,
                        len, da, db);
     SP_LAUNCH_CHECK();
     return SP_OK;

@@ -199,19 +199,14 @@ extern "C" int sp_gaussian_blur_maps(const double* in, int G, int H, int W, cons
     if (G < 1 || (int64_t)G * sp_cdiv(std::max(H, W), BL) > 0x7fffffff || H < 1 || W < 1 || H > BLUR_MAX_AXIS || W > BLUR_MAX_AXIS || ry < 0 || rx < 0 || ry > (1 << 24) || rx > (1 << 24) ||
         mode < MODE_CONSTANT || mode > MODE_NEAREST || norm < 0 || norm > 2)
         return SP_EINVAL;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blur_axis_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, BLUR_LDS_MAX);
-        attr_set = true;
-    }
     const int64_t P = (int64_t)H * W;
     double* tmp = (double*)workspace;
-    hipLaunchKernelGGL(blur_axis_kernel, dim3((unsigned)(sp_cdiv(W, BL) * G)), dim3(NT), (size_t)H * BP * 8, (hipStream_t)stream, in, tmp, H, W,
-                       (int64_t)W, (int64_t)1, P, wy, ry, mode);
-    SP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(blur_axis_kernel, dim3((unsigned)(sp_cdiv(H, BL) * G)), dim3(NT), (size_t)W * BP * 8, (hipStream_t)stream,
-                       (const double*)tmp, out, W, H, (int64_t)1, (int64_t)W, P, wx, rx, mode);
-    SP_LAUNCH_CHECK();
+    int rc = sp_launch_lds<blur_axis_kernel, BLUR_LDS_MAX>({sp_cdiv(W, BL) * G}, NT, (size_t)H * BP * 8, (hipStream_t)stream, in, tmp,
+                                                           H, W, (int64_t)W, (int64_t)1, P, wy, ry, mode);
+    if (rc != SP_OK) return rc;
+    rc = sp_launch_lds<blur_axis_kernel, BLUR_LDS_MAX>({sp_cdiv(H, BL) * G}, NT, (size_t)W * BP * 8, (hipStream_t)stream, (const double*)tmp, out,
+                                                       W, H, (int64_t)1, (int64_t)W, P, wx, rx, mode);
+    if (rc != SP_OK) return rc;
     if (norm) {
         hipLaunchKernelGGL(normalise_maps_kernel, dim3(G), dim3(NT), 0, (hipStream_t)stream, out, (int)P, norm);
         SP_LAUNCH_CHECK();

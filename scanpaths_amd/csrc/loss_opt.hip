@@ -112,7 +112,7 @@ __global__ void reduce_final_f(const double* partial, int nblk, float* out) {
     }
 }
 
-inline int red_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, 1024), 1024)); }
+inline int red_blocks(int64_t n) { return sp_ew_grid(n, 1024, 1024); }
 
 __global__ __launch_bounds__(256) void clip_adam_kernel(float* p, const float* g, float* m, float* v, int64_t n,
                                                         const double* sumsq, float gscale, float clip, float lr, float beta1,
@@ -228,8 +228,7 @@ extern "C" int sp_rows_last(const float* const* grads, const int64_t* row_len, i
 
 extern "C" int sp_scale_by(const float* x, const float* scale, int64_t n, float* out, void* stream) {
     if (!x || !scale || !out) return SP_ENULL;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, 256), 2048));
-    hipLaunchKernelGGL(scale_by_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, scale, n, out);
+    hipLaunchKernelGGL(scale_by_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, x, scale, n, out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }
@@ -312,8 +311,7 @@ extern "C" int sp_clip_adam(float* p, const float* g, float* m, float* v, int64_
                             float clip, float lr, float beta1, float beta2, float eps, float weight_decay, float bc1,
                             float bc2, void* stream) {
     if (!p || !g || !m || !v || !sumsq) return SP_ENULL;
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(sp_cdiv(n, 256), 4096));
-    hipLaunchKernelGGL(clip_adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, gscale, clip,
+    hipLaunchKernelGGL(clip_adam_kernel, dim3(sp_ew_grid(n, 4096)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, gscale, clip,
                        lr, beta1, beta2, eps, weight_decay, bc1, bc2);
     SP_LAUNCH_CHECK();
     return SP_OK;
@@ -342,8 +340,7 @@ extern "C" int sp_rowscale(const float* coef, const float* g, int B, int T, floa
     if (!coef || !g || !out) return SP_ENULL;
     if (B < 1 || T < 1) return SP_EINVAL;
     const int64_t n = (int64_t)B * T;
-    hipLaunchKernelGGL(rowscale_kernel, dim3((unsigned)std::min<int64_t>(sp_cdiv(n, 256), 2048)), dim3(256), 0, (hipStream_t)stream,
-                       coef, g, n, T, out);
+    hipLaunchKernelGGL(rowscale_kernel, dim3(sp_ew_grid(n, 2048)), dim3(256), 0, (hipStream_t)stream, coef, g, n, T, out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

@@ -298,15 +298,7 @@ __global__ __launch_bounds__(256) void rank1_reduce_kernel(const float* __restri
 
 template <int KP>
 int launch_rank1(const R1Args& a, hipStream_t s) {
-    auto kern = rank1_grads_kernel<KP>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, R1_LDS);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)a.chunks, (unsigned)a.B), dim3(256), R1_LDS, s, a);
-    SP_LAUNCH_CHECK();
-    return SP_OK;
+    return sp_launch_lds<rank1_grads_kernel<KP>, R1_LDS>({a.chunks, a.B}, 256, R1_LDS, s, a);
 }
 
 int64_t r1_slab_bytes(int B, int P, int N3, int KP) {
@@ -340,8 +332,7 @@ extern "C" int sp_rank1_grads_f16x2(const void* dpre_planes, const float* dpre_s
     const int rc = KP == 20 ? launch_rank1<20>(a, s) : launch_rank1<12>(a, s);
     if (rc != SP_OK) return rc;
     const int64_t per = (int64_t)N3 * KP;
-    const int64_t nb = sp_cdiv((int64_t)B * per, 256);
-    hipLaunchKernelGGL(rank1_reduce_kernel, dim3((unsigned)(nb < 1 ? 1 : (nb > 4096 ? 4096 : nb))), dim3(256), 0, s, (const float*)workspace,
+    hipLaunchKernelGGL(rank1_reduce_kernel, dim3(sp_ew_grid((int64_t)B * per, 4096)), dim3(256), 0, s, (const float*)workspace,
                        (const float*)a.slab_inv, dpre_scale, B, a.chunks, per, dwc, row_last, row_step);
     SP_LAUNCH_CHECK();
     return SP_OK;

@@ -928,8 +928,7 @@ extern "C" int sp_rowscale_idx(const float* coef, const float* g, const int* idx
     if (!coef || !g || !idx || !out) return SP_ENULL;
     if (R < 1 || P < 1) return SP_EINVAL;
     const int64_t n = (int64_t)R * P;
-    hipLaunchKernelGGL(rowscale_idx_kernel, dim3((unsigned)std::min<int64_t>(sp_cdiv(n, NT), 2048)), dim3(NT), 0, (hipStream_t)stream,
-                       coef, g, idx, n, P, out);
+    hipLaunchKernelGGL(rowscale_idx_kernel, dim3(sp_ew_grid(n, 2048, NT)), dim3(NT), 0, (hipStream_t)stream, coef, g, idx, n, P, out);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

@@ -187,8 +187,7 @@ extern "C" int sp_scanmatch_submatrix(int Xbin, int Ybin, double threshold, doub
     if (!sub || !maxsub) return SP_ENULL;
     if (Xbin < 1 || Ybin < 1 || (int64_t)Xbin * Ybin > 32768) return SP_EINVAL;
     const int64_t n = (int64_t)Xbin * Ybin * Xbin * Ybin;
-    hipLaunchKernelGGL(submatrix_kernel, dim3((unsigned)std::min<int64_t>(sp_cdiv(n, 256), 4096)), dim3(256), 0,
-                       (hipStream_t)stream, Xbin, Ybin, threshold, sub, maxsub);
+    hipLaunchKernelGGL(submatrix_kernel, dim3(sp_ew_grid(n, 4096)), dim3(256), 0, (hipStream_t)stream, Xbin, Ybin, threshold, sub, maxsub);
     SP_LAUNCH_CHECK();
     return SP_OK;
 }

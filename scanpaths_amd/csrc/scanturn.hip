@@ -255,14 +255,9 @@ extern "C" int sp_scan_turn_expectation(const float* probs, const int* row_group
         return SP_EINVAL;
     const ExpArgs a{probs, row_group, sector, R, T, Tm, nT, Hm, Wm, ngroups, min_length, n_directions, work, M, pairs, bad};
     const size_t lds = ((size_t)3 * P + (size_t)2 * E1 * 256) * sizeof(double) + (size_t)D;     // at most 49,152 + 69,632 + 8,001 bytes
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_turn_expect_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (3 * MAXCELLS + 2 * (MAXDIR + 1) * 256) * (int)sizeof(double) + 4 * MAXCELLS);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(scan_turn_expect_kernel, dim3((unsigned)((int64_t)R * nT)), dim3(256), lds, (hipStream_t)stream, a);
-    SP_LAUNCH_CHECK();
+    constexpr int max_lds = (3 * MAXCELLS + 2 * (MAXDIR + 1) * 256) * (int)sizeof(double) + 4 * MAXCELLS;
+    const int rc = sp_launch_lds<scan_turn_expect_kernel, max_lds>({(int64_t)R * nT}, 256, lds, (hipStream_t)stream, a);
+    if (rc != SP_OK) return rc;
     if (Tm >= 3) {
         hipLaunchKernelGGL(scan_turn_rows_kernel, dim3((unsigned)sp_cdiv((int64_t)R * E, 256)), dim3(256), 0, (hipStream_t)stream, a);
         SP_LAUNCH_CHECK();
