@@ -427,8 +427,11 @@ int sp_drt_direct_fwd(const float* h, const float* W11, const float* cbsum, cons
                       int nsel, float* Dpre, void* stream);
 /* Both gradients skip the (row, head slot) pairs whose gradient is exactly zero (bit-identical sums): live (nullable) [nsel][B] from
  * sp_head_finish_bwd; row_last (nullable): row b -- decode step b / rowB of sample b % rowB when one launch covers several steps, rowB = B
- * for a per-step launch -- is dead when row_last[b % rowB] < row_step + b / rowB (B % rowB == 0).  Dead rows of dh are written as zeros;
- * the weight gradient's slabs of dead rows are zeros and h is not read for them.  workspace >= sp_drt_direct_bwd_weight_workspace bytes. */
+ * for a per-step launch -- is dead when row_last[b % rowB] < row_step + b / rowB (B % rowB == 0).  Dead rows of dh are written as zeros
+ * (accumulate = 0) or keep their value (accumulate = 1); the weight gradient's slabs of dead pairs are not written and not summed (exact
+ * zeros) and h is not read for dead rows.  sp_drt_direct_bwd_data ignores both flag arrays when nsel > 8 (it then computes the zero terms:
+ * the same bits); dcbsum sums dDpre over all pairs, dead ones included (zeros by the contract above).
+ * workspace >= sp_drt_direct_bwd_weight_workspace bytes = B * nsel * ncls * 121 * C * 4 (-1 for an illegal map side). */
 int sp_drt_direct_bwd_data(const float* dDpre, const float* W11, const int* hmap, int B, int Hm, int Wm, int C, int nsel,
                            int accumulate, float* dh, const int* live, const int* row_last, int row_step, int rowB, void* stream);
 int64_t sp_drt_direct_bwd_weight_workspace(int B, int Hm, int Wm, int C, int nsel);
