@@ -12,7 +12,7 @@ TWO CONTRACTIONS PER LAUNCH, both in fp64:
 The gathers are gemm_ref.im2col / im2col_dgrad; the weight operand is always [Nout][K] with k = (tap, channel).
 
 TWO BARS, both derived, neither tuned on results:
-    kernel against R_planes   gemm_ref.bar(S, c): c 2^-24 S + 2^-149, S the contraction over absolute values of the planes (a subnormal plane
+    kernel against R_planes   parity.bar(S, c): c 2^-24 S + 2^-149, with S the contraction over absolute values of the planes (a subnormal plane
                               entry counted at the format's smallest exponent: hw_abs), c the launch's longest chain of dependent roundings in
                               units of 2^-24 (chain_h2, chain_hw, chain_hw2).
                               ASSUMPTION (nobody here has measured what v_mfma_f32_16x16x32_f16 does inside one instruction and the
@@ -30,7 +30,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from gemm_ref import U, cdiv, conv_out_size, im2col, im2col_dgrad, seed_of
+from gemm_ref import conv_out_size, im2col, im2col_dgrad
+from parity import U, cdiv, seed_of
 
 F32, F16 = np.float32, np.float16
 PROD_UNITS = 2          # one truncation (2^-23) per product, in units of 2^-24: the assumption of the module docstring
@@ -667,3 +668,13 @@ class HWProblem:
     def last_live_k(self):
         live = ((self.A1 != 0).reshape(-1, self.K).any(0) & (self.B1 != 0).transpose(1, 2).reshape(-1, self.K).any(0)).nonzero()
         return int(live[-1])
+
+
+def hw_desc(hip, p, **kw):
+    """the sp_wgrad_desc of an HWProblem (hip: scanpaths_amd.hip); kw overrides fields"""
+    c = p.c
+    a = dict(N_img=c.N_img, Hi=c.Hi, Wi=c.Wi, Ci=c.Ci, ldx=c.Ci, Ho=c.Ho, Wo=c.Wo, Co=c.Co, ldy=p.ldy, KH=c.KH, KW=c.KW, stride=c.stride, pad=c.pad,
+             dil=c.dil, ldo=p.ldo, beta=c.beta, alpha=c.alpha, nbatch=c.nbatch, x_scale_vec=int(c.xvec), y_scale_vec=int(c.yvec),
+             strideX=p.xrows * c.Ci if c.nbatch > 1 else 0, strideY=p.M * p.ldy if c.nbatch > 1 else 0, strideO=c.Co * p.ldo if c.nbatch > 1 else 0)
+    a.update(kw)
+    return hip.WgradDesc(**a)

@@ -8,27 +8,17 @@ Every launch is restated as ONE contraction  acc[b][m][n] = sum_k A[b][m][k] B[b
 so that "the last k left out" and the contraction over absolute values S are the same two lines for all of them.  tests/test_gemm_ref_cpu.py
 holds the gathers to torch's fp64 conv2d and its autograd at 1e-12.
 
-THE BAR (element-wise):  |got - ref| <= c 2^-24 S + 2^-149,  S = |alpha| (|A| @ |B|) + |bias| + |beta out0|.
+THE BAR (element-wise, parity.bar):  |got - ref| <= c 2^-24 S + 2^-149,  S =|alpha| (|A| @ |B|) + |bias| + |beta out0|.
 fp32 MFMA multiplies exactly and rounds each accumulation once to nearest (unit roundoff u = 2^-24), every other operation of the kernels is one
 rounded fp32 operation.  A product that passes through d dependent roundings on its way into an output carries a relative error of at most
 (1 + u)^d - 1, so the output's error is at most ((1 + u)^c - 1) S with c the LONGEST such chain of the launch; relu is 1-Lipschitz and changes
 nothing.  (1 + u)^c - 1 <= (c + 1) u for every c below 2^12, so each chain_* function below returns its count plus one; that one also covers the
 fp64 reference's own error (K 2^-53 S).  The counts are read off the kernels and written next to each function; nothing here was tuned on results."""
-import zlib
 from collections import namedtuple
 
-import numpy as np
 import torch
 
-U = 2.0 ** -24
-TINY = 2.0 ** -149
-SENTINEL = 0x7FC5A5A5          # int32 bit pattern of every output pad / gap / guard / workspace-tail word: a NaN, so a read of it shows too
-GUARD = 64                     # words before and after every allocation (256 bytes: the 16-byte alignment of the live part is kept)
-NAN = float("nan")
-
-
-def cdiv(a, b):
-    return -(-a // b)
+from parity import Guarded, cdiv, randn, seed_of
 
 
 # ====================================================================================================================
@@ -123,19 +113,6 @@ def last_live_k(A):
     return int(live[-1])
 
 
-def bar(S, c):
-    return c * U * S + TINY
-
-
-def worst(got, ref, S, c):
-    """(max err / bar, flat index of it, err there, bar there); got must be finite"""
-    g = got.double()
-    assert torch.isfinite(g).all(), "a live output word is not finite"
-    q = (g - ref).abs() / bar(S, c)
-    i = int(q.argmax())
-    return float(q.reshape(-1)[i]), i, float((g - ref).abs().reshape(-1)[i]), float(bar(S, c).reshape(-1)[i])
-
-
 # ====================================================================================================================
 # the gathers of the header (include/scanpaths_amd.h, sp_conv_desc), index by index
 # ====================================================================================================================
@@ -176,52 +153,6 @@ def im2col_dgrad(dY, KH, KW, stride, pad, dil, Ho, Wo):
 
 def conv_out_size(H, K, stride, pad, dil):
     return (H + 2 * pad - dil * (K - 1) - 1) // stride + 1
-
-
-# ====================================================================================================================
-# guarded buffers
-# ====================================================================================================================
-class Guarded:
-    """[nb] items of [rows][cols] with row stride ld and item stride `stride` inside one flat fp32 allocation: GUARD words, `offset` words, the
-    items, GUARD words.  fill "nan": every word that is not data is NaN (operands); "sentinel": SENTINEL (outputs, workspaces).  data None
-    leaves the live words at the fill (an output under beta = 0, a workspace)."""
-    def __init__(self, nb, rows, cols, ld, stride=None, *, fill, data=None, offset=0):
-        stride = rows * ld if stride is None else stride
-        assert cols <= ld and (nb == 1 or stride >= (rows - 1) * ld + cols)
-        self.nb, self.rows, self.cols, self.ld, self.stride, self.start = nb, rows, cols, ld, stride, GUARD + offset
-        n = self.start + (nb - 1) * stride + rows * ld + GUARD
-        if fill == "nan":
-            self.flat = torch.full((n,), NAN, dtype=torch.float32)
-        else:
-            self.flat = torch.full((n,), SENTINEL, dtype=torch.int32).view(torch.float32)
-        self.has_data = data is not None
-        if data is not None:
-            self.live(self.flat).copy_(data.reshape(nb, rows, cols))
-
-    def live(self, flat):
-        return flat.as_strided((self.nb, self.rows, self.cols), (self.stride, self.ld, 1), self.start)
-
-    def pad_mask(self):
-        m = torch.ones(self.flat.numel(), dtype=torch.bool)
-        self.live(m).fill_(False)
-        return m
-
-    def pads_untouched(self, flat_after):
-        """every word outside the live region still holds what it held"""
-        m = self.pad_mask()
-        return bool((flat_after.view(torch.int32)[m] == self.flat.view(torch.int32)[m]).all())
-
-    def all_untouched(self, flat_after):
-        return bool((flat_after.view(torch.int32) == self.flat.view(torch.int32)).all())
-
-
-def randn(*shape, seed):
-    g = np.random.Generator(np.random.PCG64(seed))
-    return torch.from_numpy(g.standard_normal(shape).astype(np.float32))
-
-
-def seed_of(name):
-    return zlib.crc32(name.encode())
 
 
 # ====================================================================================================================

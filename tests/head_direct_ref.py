@@ -2,7 +2,7 @@
 side of tests/test_head_direct_ref_cpu.py and tests/test_head_direct_gpu.py.  Nothing here touches a GPU.
 
 Every function returns (ref, S): S is the same contraction over absolute values, the scale of the element-wise bar
-|got - ref| <= c 2^-24 S + 2^-149 (gemm_ref.bar) with c the kernel's longest chain of dependent fp32 roundings plus one (gemm_ref's convention:
+|got - ref| <= c 2^-24 S + 2^-149 (parity.bar) with c the kernel's longest chain of dependent fp32 roundings plus one (gemm_ref's convention:
 (1 + u)^c - 1 <= (c + 1) u, the one also covers the fp64 reference's own error).  The chains are read off the kernels and written next to each
 chain_* function; nothing here was tuned on results.  tests/test_head_direct_ref_cpu.py holds the restatement to torch's fp64 conv2d and autograd
 on the literal two-conv formulation.  `drop=True` leaves one term out of every sum (the teeth of the bars).
@@ -14,7 +14,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from gemm_ref import cdiv, seed_of
+from parity import cdiv, seed_of
 
 MAXSITE, NV = 32, 121
 
@@ -282,7 +282,7 @@ def drt_bwd_weight(dD, h, hmap, geo, nsel, nheads, on=None, drop=None):
 
 
 # ====================================================================================================================
-# chains of dependent roundings (each plus one, gemm_ref's convention)
+# chains of dependent roundings (each plus one, the convention of gemm_ref.py)
 # ====================================================================================================================
 def chain_compose11_fwd():
     """compose11_fwd_kernel: `acc += G4[..]` over at most 49 taps from 0.f (cbsum: the same 49 adds)"""

@@ -140,6 +140,103 @@ def metrics_table(d):
     return np.array([[float(d[c][g][k]) for g, k in EVAL_COLUMNS] for c in EVAL_CATEGORIES], dtype=np.float64)
 
 
+def _flags(flat, counts):
+    """a flat flag array -> one list of bools per image"""
+    out, k = [], 0
+    for c in counts:
+        out.append([bool(v) for v in flat[k:k + int(c)]])
+        k += int(c)
+    return out
+
+
+def eval_golden():
+    """tests/golden/eval_metrics.npz as the arguments of evaluation_performance_related / human_evaluation:
+    (arrays, (gt, pred, perf, alloc), loader, question ids)"""
+    g = np.load(os.path.join(GOLDEN, "eval_metrics.npz"))
+    gt, perf = unpack_scanpaths(g["epr_gt_fix"], g["epr_gt_len"], g["epr_gt_count"]), _flags(g["epr_perf"], g["epr_gt_count"])
+    pred = unpack_scanpaths(g["epr_pred_fix"], g["epr_pred_len"])
+    alloc = [bool(v) for v in g["epr_alloc"]]
+    hfix, hperf = unpack_scanpaths(g["hum_fix"], g["hum_len"], g["hum_count"]), _flags(g["hum_perf"], g["hum_count"])
+    qids = [f"q{i:03d}" for i in range(len(hfix))]
+    loader = [{"fix_vectors": hfix[:3], "performances": hperf[:3], "question_ids": qids[:3]},
+              {"fix_vectors": hfix[3:], "performances": hperf[3:], "question_ids": qids[3:]}]
+    return g, (gt, pred, perf, alloc), loader, qids
+
+
+# ---- RL reward glue (tests/golden/rl.npz): host grouping logic against the reference ------------------------------------------
+def same(a, b):
+    """equal as float64, bit for bit (NaN equals NaN)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    assert np.array_equal(a, b, equal_nan=True), np.nanmax(np.abs(a - b))
+
+
+def rl_case():
+    """(ground-truth scanpaths per image, their performance flags, predicted scanpaths) of tests/golden/rl.npz"""
+    g = np.load(os.path.join(GOLDEN, "rl.npz"))
+    return unpack_scanpaths(g["gt_fix"], g["gt_len"], g["gt_count"]), _flags(g["perf"], g["gt_count"]), unpack_scanpaths(g["pred_fix"], g["pred_len"])
+
+
+def check_rl_glue(wd, wod):
+    """the reward glue of scanpaths_amd.utils.evaluation with the scorers wd (with duration) / wod (without) against the reference's outputs"""
+    from scanpaths_amd.utils.evaluation import (gtpairs_eval_scanmatch_performance_related,
+                                                pairs_eval_scanmatch_performance_related)
+    g = np.load(os.path.join(GOLDEN, "rl.npz"))
+    gt, perf, pred = rl_case()
+    for given, tag in ((True, "good"), (False, "poor")):
+        s, d, acc = pairs_eval_scanmatch_performance_related(gt, pred, wd, wod, perf, given)
+        same(s, g[f"pairs_{tag}_same"])
+        same(d, g[f"pairs_{tag}_diff"])
+        assert int(acc) == int(g[f"pairs_{tag}_accept"])
+    gg, p, dd = gtpairs_eval_scanmatch_performance_related(gt, wd, wod, perf)
+    same(gg, g["gtpairs_good"])
+    same(p, g["gtpairs_poor"])
+    same(dd, g["gtpairs_diff"])
+
+
+# ---- the model on the device (tests/test_model_gpu.py and the GPU tests that train it) ----------------------------------------
+DEV = "cuda:0"
+
+
+def build_model(meta, Hm=30, Wm=40):
+    from scanpaths_amd.models.scanpath_model import ScanpathModel
+    from scanpaths_amd.procedural import fill_module
+    m = ScanpathModel(meta["task"], convLSTM_length=meta["T"], map_width=Wm, map_height=Hm, arch=meta["arch"])
+    fill_module(m, seed=meta["weight_seed"], family=meta.get("weight_family", "default"))
+    return m.to(DEV)
+
+
+def call_model(model, meta, b):
+    img = b["images"].to(DEV)
+    if meta["task"] == "AiR":
+        return model(img, b["attention_maps"].to(DEV), b["performances"].to(DEV) if model.training else None)
+    if meta["task"] == "OSIE":
+        return model(img)
+    return model(img, b["attention_maps"].to(DEV), b["tasks"].to(DEV))
+
+
+def sparsity_case(task, T=8, NB=5, seed=4, lengths=(1, 4, 8, 2, 0)):
+    from scanpaths_amd.synth import make_batch
+    meta = dict(task=task, arch="resnet18", T=T, weight_seed=seed, weight_family="tame")
+    b = {k: v.to(DEV) for k, v in make_batch(task, NB, 320, 512, T, seed=seed).items()}
+    am, dm = torch.zeros(NB, T, device=DEV), torch.zeros(NB, T, device=DEV)
+    for i, L in enumerate(lengths):                                # last loss step per sample: L - 1 (none for L = 0)
+        am[i, :L] = 1
+        dm[i, :max(L - 1, 0)] = 1
+    b["action_masks"], b["duration_masks"] = am, dm
+    return meta, b
+
+
+def param_grads(model):
+    return {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+
+
+def assert_same_grads(a, b_):
+    assert a.keys() == b_.keys()
+    diff = [k for k in a if not torch.equal(a[k], b_[k])]
+    assert not diff, diff[:8]
+
+
 def kink_candidates(sd, tap, tol=1e-5, heads=("True", "False")):
     """ReLU sites of an oracle run (tap = the dict oracle.forward(..., tap=) filled) whose mask a fp32 implementation may take the other
     way -- |pre-activation| < tol x max|pre-activation| of that tensor (the HIP path's forward values are within ~1e-5 of scale of the

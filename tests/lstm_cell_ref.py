@@ -114,12 +114,6 @@ def stress_inputs(rows, C, seed=0):
     return torch.from_numpy(xg), torch.from_numpy(cp)
 
 
-def stress_bar(base, r32, r64):
-    """max(existing bar, 10 max|ref32 - ref64|) in the metric of _close (error over max(1, max|ref64|))"""
-    r32, r64 = r32.detach().double(), r64.detach().double()
-    return max(base, 10.0 * (r32 - r64).abs().max().item() / max(1.0, r64.abs().max().item()))
-
-
 def bound_attained_inputs(C, c_bound, cprev_bound, a_dh, a_dc, seed=0):
     """hand-built saved state of 8 rows x C channels that makes each term of the cell backward's documented bound
         max(D, max|dh| c_bound / 4, D cprev_bound / 4),  D = max|dh| + max|dc|

@@ -12,7 +12,7 @@ TWO CONTRACTIONS, both fp64, as in f16x2_ref.py:
     R_planes   exactly the three products each side takes (high x high, high x low, low x high), divided by the scales; for dwc per chunk, the
                chunks added in chunk order
     R_true     the same contraction on the fp32 operands
-BARS.  Kernel against R_planes: gemm_ref.bar(S, chain) with S the contraction over f16x2_ref.hw_abs magnitudes and the chains below (the
+BARS.  Kernel against R_planes: parity.bar(S, chain) with S the contraction over f16x2_ref.hw_abs magnitudes and the chains below (the
 conventions and the UNMEASURED assumption of f16x2_ref.py: PROD_UNITS per product of v_mfma_f32_16x16x32_f16).  R_planes against R_true:
 f16x2_ref.rep_bound(.., 3), per chunk for dwc.  Nothing here was tuned on results.
 
@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 import f16x2_ref as X
-from gemm_ref import cdiv, seed_of
+from parity import cdiv, seed_of
 
 F32, F16 = np.float32, np.float16
 PX, NT = 32, 5                     # R1_PX, R1_NT: pixels per LDS tile, tiles per workgroup

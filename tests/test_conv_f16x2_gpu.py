@@ -4,7 +4,7 @@ library selects: forward / data gradient, tap-major / channel-block-major / halo
 torch's fp64 conv and autograd and to its own claims by tests/test_f16x2_ref_cpu.py).
 
 Splitters: bit equality of planes, zero block and scales with the numpy emulation.  GEMMs: the operands are the emulation's planes (wider rows hold
-fp16 NaNs in their pad channels), outputs and workspaces lie in gemm_ref.Guarded allocations whose pads, gaps and guards hold a sentinel word and
+fp16 NaNs in their pad channels), outputs and workspaces lie in parity.Guarded allocations whose pads, gaps and guards hold a sentinel word and
 must be unchanged after the launch, workspaces are exactly the queried size.  Every case runs on Gaussian data -- every live word finite and inside
 the ELEMENT-WISE derived bar against R_planes (f16x2_ref: chain_*), the max-norm bars of tests/test_ops_gpu.py against R_true on top -- and on
 LATTICE data, where every summation order is exact and the kernel must equal R_planes exactly (torch.equal in fp64: bit for bit up to the sign of
@@ -13,73 +13,20 @@ Out of scope here: sp_gateconv_lstm_f16x2 (tests/test_lstm_cell_gpu.py), sp_rank
 the timing-library variants."""
 import ctypes
 import functools
-import time
 
 import numpy as np
 import pytest
 import torch
 
 import f16x2_ref as R
-import gemm_ref as G
-import test_gemm_fp32_gpu as FP32
-from test_gemm_fp32_gpu import _abi, _at, _judge, _same_bits, _up, _vec
-from test_ops_gpu import _close, _dev
+import parity as P
 
 pytestmark = pytest.mark.gpu
 
 EINVAL, ENULL = -1, -2
-GROUPS = []
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _summary():
-    t0 = time.time()
-    yield
-    for group in GROUPS:
-        rows = FP32.SUMMARY.pop(group, None)
-        if rows:
-            q, name, err, b, chain = max(rows)
-            print(f"\nPARITY-SUMMARY {group}: {len(rows)} comparisons, worst err/bar {q:.3f} at {name} (err {err:.2e}, bar {b:.2e}, c {chain})", end="")
-    print(f"\nPARITY-SUMMARY f16x2 total {time.time() - t0:.1f} s")
-
-
-def _group(name):
-    if name not in GROUPS:
-        GROUPS.append(name)
-    return name
-
-
-def _u16(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(_dev())
-
-
-def _f32(a):
-    return torch.from_numpy(np.array(a, dtype=np.float32).reshape(-1)).to(_dev())
-
-
-class Raw:
-    """nbytes of device memory between GUARD sentinel words on either side: the output of a splitter, a scale vector, a scratch buffer"""
-    def __init__(self, nbytes, init=None):
-        assert nbytes % 4 == 0
-        self.words = nbytes // 4
-        host = torch.full((2 * G.GUARD + self.words,), G.SENTINEL, dtype=torch.int32)
-        if init is not None:
-            host[G.GUARD:G.GUARD + self.words] = torch.from_numpy(np.asarray(init).view(np.int32).reshape(-1))
-        self.host, self.dev = host, host.to(_dev())
-        self.ptr = self.dev.data_ptr() + 4 * G.GUARD
-
-    def read(self):
-        """the live words after the launch (int32, numpy); the guards must hold the sentinel"""
-        after = self.dev.cpu()
-        assert (after[:G.GUARD] == G.SENTINEL).all() and (after[G.GUARD + self.words:] == G.SENTINEL).all(), "a guard word around a buffer changed"
-        return after[G.GUARD:G.GUARD + self.words].numpy()
-
-    def untouched(self):
-        return bool((self.dev.cpu() == self.host).all())
-
-
-def _sync():
-    torch.cuda.synchronize()
+SUM = P.Summary("f16x2")
+_summary = SUM.fixture()
+_h2, _hw = functools.lru_cache(maxsize=None)(R.H2Problem), functools.lru_cache(maxsize=None)(R.HWProblem)          # (case, kind) -> operands and restatement, built once
 
 
 # ====================================================================================================================
@@ -113,14 +60,14 @@ def _planes_equal(got_words, want_u16, what):
 
 @pytest.mark.parametrize("name,n,kind,bound", SPLIT2, ids=[s[0] for s in SPLIT2])
 def test_split2_f16(name, n, kind, bound):
-    hip, L = _abi()
-    x = _data(kind, n, G.seed_of(name))
+    hip, L = P.abi()
+    x = _data(kind, n, P.seed_of(name))
     b = None if bound is None else np.float32(bound) * np.abs(x).max()
     want, s = R.split2_f16(x, bound=b)
-    dx, out = _f32(x), Raw(4 * n + 64)
-    sa = Raw(8, init=np.array([np.float32(np.nan), np.float32(0.0) if b is None else b], dtype=np.float32))      # {scale, max|x| bits: zero or the bound}
+    dx, out = P.f32(x), P.raw(4 * n + 64)
+    sa = P.raw(8, init=np.array([np.float32(np.nan), np.float32(0.0) if b is None else b], dtype=np.float32))      # {scale, max|x| bits: zero or the bound}
     assert L.sp_split2_f16(dx.data_ptr(), n, out.ptr, sa.ptr, 0 if b is None else 1, hip.stream()) == 0
-    _sync()
+    torch.cuda.synchronize()
     got_s = sa.read().view(np.float32)
     assert got_s[0] == s, (got_s, s)
     if b is None:
@@ -130,19 +77,19 @@ def test_split2_f16(name, n, kind, bound):
 
 @pytest.mark.parametrize("Co,taps,Ci", [(16, 1, 4), (48, 9, 36), (16, 9, 4), (48, 1, 36)])
 def test_split2_f16_wT(Co, taps, Ci):
-    hip, L = _abi()
+    hip, L = P.abi()
     w = _data("gauss", Co * taps * Ci, Co + taps + Ci).reshape(Co, taps, Ci)
     want, s = R.split2_f16_wT(w)
-    dw, out, sa = _f32(w), Raw(4 * w.size + 64), Raw(8, init=np.zeros(2, np.float32))
+    dw, out, sa = P.f32(w), P.raw(4 * w.size + 64), P.raw(8, init=np.zeros(2, np.float32))
     assert L.sp_split2_f16_wT(dw.data_ptr(), Co, taps, Ci, out.ptr, sa.ptr, hip.stream()) == 0
-    _sync()
+    torch.cuda.synchronize()
     assert sa.read().view(np.float32)[0] == s
     _planes_equal(out.read(), want, f"wT {Co} {taps} {Ci}")
 
 
 @pytest.mark.parametrize("rows,K,Kc,absorb", [(1, 16, 16, False), (3, 288, 32, False), (1, 288, 32, True), (3, 16, 16, True), (3, 288, 96, True)])
 def test_split2_f16_rows(rows, K, Kc, absorb):
-    hip, L = _abi()
+    hip, L = P.abi()
     g = np.random.Generator(np.random.PCG64(rows * K))
     w = _data("gauss", rows * K, rows + K).reshape(rows, K)
     if rows > 1:
@@ -152,25 +99,25 @@ def test_split2_f16_rows(rows, K, Kc, absorb):
         ab = (2.0 ** g.integers(-6, 7, Kc)).astype(np.float32)
         ab[Kc // 2] = 2.0 ** -30
     want, s = R.split2_f16_rows(w, Kc, ab)
-    dw, dab, out, sc = _f32(w), (None if ab is None else _f32(ab)), Raw(4 * w.size + 64), Raw(4 * rows)
+    dw, dab, out, sc = P.f32(w), (None if ab is None else P.f32(ab)), P.raw(4 * w.size + 64), P.raw(4 * rows)
     assert L.sp_split2_f16_rows(dw.data_ptr(), rows, K, Kc, None if ab is None else dab.data_ptr(), out.ptr, sc.ptr, hip.stream()) == 0
-    _sync()
+    torch.cuda.synchronize()
     assert (sc.read().view(np.float32) == s).all()
     _planes_equal(out.read(), want, f"rows {rows} {K} {Kc} {absorb}")
 
 
 @pytest.mark.parametrize("nbatch,Ci,absorb", [(1, 4, False), (3, 12, False), (3, 20, True), (1, 20, True)])
 def test_split2_f16_wT_rows(nbatch, Ci, absorb):
-    hip, L = _abi()
+    hip, L = P.abi()
     Co, taps = 16, 3
     g = np.random.Generator(np.random.PCG64(nbatch * Ci))
     w = _data("gauss", nbatch * Co * taps * Ci, nbatch + Ci).reshape(nbatch, Co, taps, Ci)
     w[-1, :, :, Ci - 1] = 0                                            # a row of zeros
     ab = (2.0 ** g.integers(-6, 7, Co)).astype(np.float32) if absorb else None
     want, s = R.split2_f16_wT_rows(w, ab)
-    dw, dab, out, sc = _f32(w), (None if ab is None else _f32(ab)), Raw(4 * w.size + 64), Raw(4 * nbatch * Ci)
+    dw, dab, out, sc = P.f32(w), (None if ab is None else P.f32(ab)), P.raw(4 * w.size + 64), P.raw(4 * nbatch * Ci)
     assert L.sp_split2_f16_wT_rows(dw.data_ptr(), nbatch, Co, taps, Ci, None if ab is None else dab.data_ptr(), out.ptr, sc.ptr, hip.stream()) == 0
-    _sync()
+    torch.cuda.synchronize()
     got_s = sc.read().view(np.float32)
     assert (got_s == s).all() and got_s[-1] == 1.0
     _planes_equal(out.read(), want, f"wT_rows {nbatch} {Ci} {absorb}")
@@ -178,16 +125,16 @@ def test_split2_f16_wT_rows(nbatch, Ci, absorb):
 
 @pytest.mark.parametrize("rows,C", [(1, 16), (5, 16), (5, 272), (1, 1040), (5, 1040), (512 * 64 * 4 + 3, 16)])
 def test_split2_f16_cols(rows, C):
-    hip, L = _abi()
+    hip, L = P.abi()
     g = np.random.Generator(np.random.PCG64(rows + C))
     x = _data("gauss", rows * C, rows * C).reshape(rows, C) * (2.0 ** g.integers(-8, 9, C)).astype(np.float32)
     x[:, C // 3] = 0                                                   # a dead channel: scale 2^100
     want, s = R.split2_f16_cols(x)
     nbytes = L.sp_split2_f16_cols_workspace(rows, C)
     assert nbytes == R.colamax_blocks(rows, C) * C * 4
-    dx, out, sc, scratch = _f32(x), Raw(4 * x.size + 64), Raw(4 * C), Raw(nbytes)
+    dx, out, sc, scratch = P.f32(x), P.raw(4 * x.size + 64), P.raw(4 * C), P.raw(nbytes)
     assert L.sp_split2_f16_cols(dx.data_ptr(), rows, C, out.ptr, sc.ptr, scratch.ptr, hip.stream()) == 0
-    _sync()
+    torch.cuda.synchronize()
     scratch.read()
     got_s = sc.read().view(np.float32)
     assert (got_s == s).all() and got_s[C // 3] == np.float32(2.0 ** 100)
@@ -197,13 +144,8 @@ def test_split2_f16_cols(rows, C):
 # ====================================================================================================================
 # sp_conv_igemm_f16x2 / _f16x1 / _stats
 # ====================================================================================================================
-@functools.lru_cache(maxsize=None)
-def _h2(case, kind):
-    return R.H2Problem(case, kind)
-
-
 def _h2_out(p):
-    return G.Guarded(p.c.nbatch, p.M, p.c.Nout, p.ldc, p.M * p.ldc, fill="sentinel", data=p.out0)
+    return P.Guarded(p.c.nbatch, p.M, p.c.Nout, p.ldc, p.M * p.ldc, fill="sentinel", data=p.out0)
 
 
 def _h2_desc(hip, p, **kw):
@@ -218,24 +160,23 @@ def _h2_desc(hip, p, **kw):
 
 def _launch_h2(p, *, Xp=None, row_last=None, row_step=0, null=(), off=None, desc=None, expect=0):
     """one launch of the entry the case names on fresh buffers -> (output allocation on the host, (st_partial, st_mm) or None)"""
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
     off = off or {}
-    dX, dW = _u16(p.Xp if Xp is None else Xp), _u16(p.Wp)
-    dsx, dsw = _f32(p.sx), _f32(p.sw)
+    dX, dW = P.u16(p.Xp if Xp is None else Xp), P.u16(p.Wp)
+    dsx, dsw = P.f32(p.sx), P.f32(p.sw)
     out = _h2_out(p)
-    dO = _up(out)
-    gb = _vec(p.bias)
-    dB = _up(gb)
-    drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=_dev())
+    dO = P.up(out)
+    dB = P.operand(p.bias)
+    drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=P.dev())
     d = _h2_desc(hip, p, row_last=None if drl is None else drl.data_ptr(), row_step=row_step, **(desc or {}))
     ptr = {"X": dX.data_ptr() + off.get("X", 0), "W": dW.data_ptr() + off.get("W", 0), "sx": dsx.data_ptr(), "sw": dsw.data_ptr(),
-           "bias": _at(dB, gb), "out": _at(dO, out)}
+           "bias": P.at(dB), "out": P.at(dO)}
     st = None
     if c.stats:
         tiles = L.sp_conv_stats_tiles(ctypes.byref(d))
-        assert tiles == G.cdiv(p.M, 256)
-        st = (Raw(tiles * 2 * c.Nout * 8), Raw(tiles * 2 * c.Nout * 4))
+        assert tiles == P.cdiv(p.M, 256)
+        st = (P.raw(tiles * 2 * c.Nout * 8), P.raw(tiles * 2 * c.Nout * 4))
         ptr["stp"], ptr["stm"] = st[0].ptr, st[1].ptr
     for k in null:
         ptr[k] = None
@@ -244,30 +185,45 @@ def _launch_h2(p, *, Xp=None, row_last=None, row_step=0, null=(), off=None, desc
     else:
         fn = L.sp_conv_igemm_f16x2 if c.nprod == 3 else L.sp_conv_igemm_f16x1
         rc = fn(ctypes.byref(d), ptr["X"], ptr["sx"], ptr["W"], ptr["sw"], ptr["bias"], ptr["out"], hip.stream())
-    _sync()
+    torch.cuda.synchronize()
     assert rc == expect, (c.name, rc, expect)
-    flat = dO.cpu()
+    flat = dO.flat()
     if expect != 0:
         assert out.all_untouched(flat), f"{c.name}: a refused call wrote to the output"
         assert st is None or (st[0].untouched() and st[1].untouched())
     return flat, st
 
 
-def _check_h2(group, p, flat):
-    c = p.c
-    out = _h2_out(p)
-    ref, S = p.planes()
-    name = f"{c.name} [{p.kind}] {p.build}"
-    _judge(_group(group), name, out, flat, ref, S, p.chain, 2e-6)
-    got = out.live(flat).double()
-    if c.nprod == 3:
-        _close(got, p.true(), 2e-6, name)
+def _check(group, p, out, flat, name, legacy, cols=slice(None)):
+    """one launch against R_planes (guards, the element-wise bar, exactly on lattice data) and against R_true (the max-norm bar; with one product
+    the representation bar); cols: the columns of the problem that the output has"""
+    ref, S = (v[..., cols] for v in p.planes())
+    SUM.judge(group, name, out, flat, ref, S, p.chain, legacy)
+    got, true = out.live(flat).double(), p.true()[..., cols]
+    if p.c.nprod == 3:
+        P.close(got, true, legacy, name)
     else:
-        assert ((got - p.true()).abs() <= p.rep_bar() + G.bar(S, p.chain)).all(), f"{name}: outside the 2^-11 representation bar of the true product"
+        assert ((got - true).abs() <= p.rep_bar()[..., cols] + P.bar(S, p.chain)).all(), f"{name}: outside the 2^-11 representation bar of the true product"
     if p.kind == "lattice":
         assert p.exact_span() <= 2.0 ** 24
-        bad = (got != ref).nonzero()
-        assert bad.numel() == 0, f"{name}: {bad.shape[0]} words differ from the exact result, first at {bad[0].tolist()}: {got[tuple(bad[0])]} != {ref[tuple(bad[0])]}"
+        SUM.exact(group, name, got, ref)
+
+
+def _check_h2(group, p, flat):
+    _check(group, p, _h2_out(p), flat, f"{p.c.name} [{p.kind}] {p.build}", 2e-6)
+
+
+def _dead_items(out, flat, dense, dead, held, what):
+    """a launch with row_last against the dense one: guards, live items bit for bit, dead items exact zeros (beta 0) or what they held (beta 1)"""
+    assert out.pads_untouched(flat)
+    got, want = out.live(flat), out.live(dense)
+    for i in range(got.shape[0]):
+        if i not in dead:
+            assert P.same_bits(got[i], want[i]), (*what, i)
+        elif held is not None:
+            assert P.same_bits(got[i], held[i]), (*what, i)
+        else:
+            assert (got[i].view(torch.int32) == 0).all(), (*what, i)
 
 
 def _run_h2(group, case, kinds=("gauss", "lattice")):
@@ -309,7 +265,7 @@ def test_igemm_stats(case):
         flat, st = _launch_h2(p)
         _check_h2("f16x2_stats", p, flat)
         got = _h2_out(p).live(flat)[0].double()                                                       # [M, Nout]
-        tiles = G.cdiv(p.M, 256)
+        tiles = P.cdiv(p.M, 256)
         stp = torch.from_numpy(st[0].read().view(np.float64).reshape(tiles, 2, case.Nout).copy())
         stm = torch.from_numpy(st[1].read().view(np.float32).reshape(tiles, 2, case.Nout).copy())
         for g in range(tiles):
@@ -329,7 +285,7 @@ def test_igemm_batched_forward_and_dead_items(case):
         p = _h2(case, kind)
         dense, _ = _launch_h2(p)
         _check_h2("f16x2_batched", p, dense)
-        assert _same_bits(dense, _launch_h2(p, row_last=[3, 9, 5], row_step=3)[0]), "row_last >= row_step everywhere must change nothing"
+        assert P.same_bits(dense, _launch_h2(p, row_last=[3, 9, 5], row_step=3)[0]), "row_last >= row_step everywhere must change nothing"
         out = _h2_out(p)
         for row_last in ([5, 1, 7], [0, 0, 0], [2, 3, 2]):
             dead = [i for i, r in enumerate(row_last) if r < 3]
@@ -337,15 +293,7 @@ def test_igemm_batched_forward_and_dead_items(case):
             x = Xp[:-32].reshape(3, -1)
             x[dead] = R.F16_NAN
             flat, _ = _launch_h2(p, Xp=Xp, row_last=row_last, row_step=3)
-            assert out.pads_untouched(flat)
-            got, want = out.live(flat), out.live(dense)
-            for i in range(3):
-                if i not in dead:
-                    assert _same_bits(got[i], want[i]), (case.name, row_last, i)
-                elif case.beta:
-                    assert _same_bits(got[i], p.out0[i]), (case.name, row_last, i)
-                else:
-                    assert (got[i].view(torch.int32) == 0).all(), (case.name, row_last, i)
+            _dead_items(out, flat, dense, dead, p.out0 if case.beta else None, (case.name, row_last))
 
 
 # ---- row-sparse data gradient ---------------------------------------------------------------------------------------------------
@@ -366,7 +314,7 @@ def test_row_sparse_data_gradient_equals_dense_on_zeroed_rows(name, case):
     operands whose dead samples hold NaN planes equals, bit for bit, the dense launch on planes zeroed there; dead samples under beta 1 keep what
     they held.  Where tiles cross images (Ho Wo % 256 != 0) the call is dense: the result is the dense launch's."""
     N, PP = case.N_img, case.Ho * case.Wo
-    g = np.random.Generator(np.random.PCG64(G.seed_of(name)))
+    g = np.random.Generator(np.random.PCG64(P.seed_of(name)))
     mixed = [int(v) for v in g.integers(0, 6, N)]
     mixed[0], mixed[-1] = 5, 0
     tiled = PP % 256 == 0
@@ -392,9 +340,9 @@ def test_row_sparse_data_gradient_equals_dense_on_zeroed_rows(name, case):
                 assert torch.isfinite(a).all(), (name, beta, kind, "a dead sample's operand rows were read")
                 assert torch.equal(a, b), (name, beta, kind, row_last)
                 live = [i for i in range(N) if i not in dead]
-                assert _same_bits(a[live], b[live]), (name, beta, kind, row_last)
+                assert P.same_bits(a[live], b[live]), (name, beta, kind, row_last)
                 if beta and tiled:
-                    assert _same_bits(a[dead], p.out0[0].reshape(N, PP, -1)[dead])
+                    assert P.same_bits(a[dead], p.out0[0].reshape(N, PP, -1)[dead])
                 elif tiled:
                     assert (a[dead].view(torch.int32) == 0).all()
 
@@ -407,7 +355,7 @@ class _Light:
 def _light_h2(c, kind):
     """operands of a many-sample case without its fp64 restatement (the comparison is between two launches)"""
     p = _Light()
-    s = G.seed_of("light" + kind + c.name)
+    s = P.seed_of("light" + kind + c.name)
     p.c, p.kind, p.K, p.M, p.xrows = c, kind, c.KH * c.KW * c.Kc, c.N_img * c.Ho * c.Wo, c.N_img * c.Hi * c.Wi
     p.ldx, p.ldc = c.Kc + c.ldx_pad, c.Nout + c.ldc_pad
     x, w = R.make(kind, (1, p.xrows, c.Kc), (), s), R.make(kind, (1, c.Nout, p.K), (), s + 1)
@@ -425,68 +373,42 @@ def _light_h2(c, kind):
 # ====================================================================================================================
 # sp_conv_wgrad_f16x2 / _f16x1
 # ====================================================================================================================
-@functools.lru_cache(maxsize=None)
-def _hw(case, kind):
-    return R.HWProblem(case, kind)
-
-
 def _hw_out(p):
-    return G.Guarded(p.c.nbatch, p.c.Co, p.Nvalid, p.ldo, p.c.Co * p.ldo, fill="sentinel", data=None if p.out0 is None else p.out0[..., :p.Nvalid])
-
-
-def _hw_desc(hip, p, **kw):
-    from test_f16x2_ref_cpu import hw_desc
-    return hw_desc(hip, p, **kw)
+    return P.Guarded(p.c.nbatch, p.c.Co, p.Nvalid, p.ldo, p.c.Co * p.ldo, fill="sentinel", data=None if p.out0 is None else p.out0[..., :p.Nvalid])
 
 
 def _launch_hw(p, *, Yp=None, row_last=None, row_step=0, null=(), off=None, desc=None, expect=0):
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
     off = off or {}
-    dX, dY, dsx, dsy = _u16(p.Xp), _u16(p.Yp if Yp is None else Yp), _f32(p.sx), _f32(p.sy)
+    dX, dY, dsx, dsy = P.u16(p.Xp), P.u16(p.Yp if Yp is None else Yp), P.f32(p.sx), P.f32(p.sy)
     out = _hw_out(p)
-    dO = _up(out)
-    drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=_dev())
-    d = _hw_desc(hip, p, row_last=None if drl is None else drl.data_ptr(), row_step=row_step, **(desc or {}))
+    dO = P.up(out)
+    drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=P.dev())
+    d = R.hw_desc(hip, p, row_last=None if drl is None else drl.data_ptr(), row_step=row_step, **(desc or {}))
     nbytes = L.sp_conv_wgrad_f16x2_workspace(ctypes.byref(d))
     if expect == 0:
         assert nbytes == (p.splits * c.Co * p.ldo * 4 if p.splits > 1 else 0), (c.name, nbytes, p.splits)
-    ws = G.Guarded(1, 1, nbytes // 4, nbytes // 4, fill="sentinel") if nbytes else None          # exactly the queried size between sentinels
-    dWs = _up(ws)
-    ptr = {"X": dX.data_ptr() + off.get("X", 0), "Y": dY.data_ptr() + off.get("Y", 0), "sx": dsx.data_ptr(), "sy": dsy.data_ptr(), "out": _at(dO, out),
-           "ws": _at(dWs, ws)}
+    dWs = P.output(nbytes // 4) if nbytes else None          # exactly the queried size between sentinels
+    ptr = {"X": dX.data_ptr() + off.get("X", 0), "Y": dY.data_ptr() + off.get("Y", 0), "sx": dsx.data_ptr(), "sy": dsy.data_ptr(), "out": P.at(dO),
+           "ws": P.at(dWs)}
     for k in null:
         ptr[k] = None
     fn = L.sp_conv_wgrad_f16x2 if c.nprod == 3 else L.sp_conv_wgrad_f16x1
     rc = fn(ctypes.byref(d), ptr["X"], ptr["sx"], ptr["Y"], ptr["sy"], ptr["out"], ptr["ws"], hip.stream())
-    _sync()
+    torch.cuda.synchronize()
     assert rc == expect, (c.name, rc, expect)
-    flat = dO.cpu()
-    if ws is not None:
-        after = dWs.cpu()
-        assert ws.pads_untouched(after), f"{c.name}: a word around the slab workspace changed"
-        assert expect == 0 or ws.all_untouched(after)
+    flat = dO.flat()
+    if dWs is not None:
+        assert dWs.pads_untouched(), f"{c.name}: a word around the slab workspace changed"
+        assert expect == 0 or dWs.untouched()
     if expect != 0:
         assert out.all_untouched(flat), f"{c.name}: a refused call wrote to the output"
     return flat
 
 
 def _check_hw(group, p, flat):
-    c = p.c
-    out = _hw_out(p)
-    ref, S = (v[..., :p.Nvalid] for v in p.planes())
-    name = f"{c.name} [{p.kind}] {p.build} (splits {p.splits})"
-    _judge(_group(group), name, out, flat, ref, S, p.chain, 3e-6)
-    got = out.live(flat).double()
-    true = p.true()[..., :p.Nvalid]
-    if c.nprod == 3:
-        _close(got, true, 3e-6, name)
-    else:
-        assert ((got - true).abs() <= p.rep_bar()[..., :p.Nvalid] + G.bar(S, p.chain)).all(), f"{name}: outside the 2^-11 representation bar"
-    if p.kind == "lattice":
-        assert p.exact_span() <= 2.0 ** 24
-        bad = (got != ref).nonzero()
-        assert bad.numel() == 0, f"{name}: {bad.shape[0]} words differ from the exact result, first at {bad[0].tolist()}"
+    _check(group, p, _hw_out(p), flat, f"{p.c.name} [{p.kind}] {p.build} (splits {p.splits})", 3e-6, slice(p.Nvalid))
 
 
 def _run_hw(group, case, kinds=("gauss", "lattice")):
@@ -495,7 +417,7 @@ def _run_hw(group, case, kinds=("gauss", "lattice")):
         flat = _launch_hw(p)
         _check_hw(group, p, flat)
         if p.splits > 1:
-            assert _same_bits(flat, _launch_hw(p)), f"{case.name}: two slab launches differ"
+            assert P.same_bits(flat, _launch_hw(p)), f"{case.name}: two slab launches differ"
 
 
 @pytest.mark.parametrize("case", R.hw_cases(), ids=lambda c: c.name)
@@ -522,15 +444,7 @@ def test_wgrad_batched_and_dead_items(case):
             Yp = p.Yp.copy()
             Yp[:-32].reshape(3, -1)[dead] = R.F16_NAN
             flat = _launch_hw(p, Yp=Yp, row_last=row_last, row_step=3)
-            assert out.pads_untouched(flat)
-            got, want = out.live(flat), out.live(dense)
-            for i in range(3):
-                if i not in dead:
-                    assert _same_bits(got[i], want[i]), (case.name, row_last, i)
-                elif case.beta:
-                    assert _same_bits(got[i], p.out0[i][..., :p.Nvalid]), (case.name, row_last, i)
-                else:
-                    assert (got[i].view(torch.int32) == 0).all(), (case.name, row_last, i)
+            _dead_items(out, flat, dense, dead, p.out0[..., :p.Nvalid] if case.beta else None, (case.name, row_last))
 
 
 # ====================================================================================================================
@@ -551,7 +465,7 @@ def test_wgrad_multi(row):
     """dW = alpha sum_g dY_g^T X_g (+ dW) in ONE launch, against the sum of the per-application references, every application with its own scales;
     pixels of samples with row_last[img] < seg_steps[g] hold NaN planes and are skipped; slabs twice bit-identical; on lattice data exact"""
     name, N, H, W, k, nseg, muls, row_last, seg_steps, beta, kinds = row
-    hip, L = _abi()
+    hip, L = P.abi()
     Ci = Co = 256
     base = R._wc("multi-" + name, N, H, W, Ci, Co, k, 1, k // 2, 1, alpha=-0.5, beta=0, ldo_pad=4, ldy_pad=16)
     PP = H * W
@@ -568,38 +482,37 @@ def test_wgrad_multi(row):
         M, Ntot, ldo = p0.M, p0.Ntot, p0.ldo
         assert R.hw2_applies(base, nseg, ldo)
         splits = R.hw2_splits(M, Co, Ntot, nseg)
-        d = _hw_desc(hip, p0, beta=beta)
+        d = R.hw_desc(hip, p0, beta=beta)
         nbytes = L.sp_conv_wgrad_f16x2_multi_workspace(ctypes.byref(d), nseg)
         assert nbytes == nseg * splits * Co * ldo * 4, (nbytes, splits)
         ref = sum(p.planes()[0] for p in ps)
         S = sum(p.planes()[1] for p in ps)
         unit = min(p.unit.min() for p in ps)
-        g = np.random.Generator(np.random.PCG64(G.seed_of(name + kind)))
+        g = np.random.Generator(np.random.PCG64(P.seed_of(name + kind)))
         out0 = None
         if beta:
             out0 = torch.from_numpy((g.integers(-8, 9, (1, Co, Ntot)) * (unit if kind == "lattice" else 1.0)).astype(np.float32))
             ref, S = ref + out0.double(), S + out0.double().abs()
-        out = G.Guarded(1, Co, Ntot, ldo, fill="sentinel", data=out0)
-        ws = G.Guarded(1, 1, nbytes // 4, nbytes // 4, fill="sentinel")
-        keep = [(_u16(p.Xp), _u16(p.Yp), _f32(p.sx), _f32(p.sy)) for p in ps]
+        out = P.Guarded(1, Co, Ntot, ldo, fill="sentinel", data=out0)
+        keep = [(P.u16(p.Xp), P.u16(p.Yp), P.f32(p.sx), P.f32(p.sy)) for p in ps]
         arr = lambda i: (ctypes.c_void_p * nseg)(*[t[i].data_ptr() for t in keep])
-        drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=_dev())
+        drl = None if row_last is None else torch.tensor(row_last, dtype=torch.int32, device=P.dev())
         steps = None if seg_steps is None else (ctypes.c_int * nseg)(*seg_steps)
 
         def launch():
-            dO, dWs = _up(out), _up(ws)
-            rc = L.sp_conv_wgrad_f16x2_multi(ctypes.byref(d), nseg, arr(0), arr(2), arr(1), arr(3), _at(dO, out), _at(dWs, ws),
+            dO, dWs = P.up(out), P.output(nbytes // 4)
+            rc = L.sp_conv_wgrad_f16x2_multi(ctypes.byref(d), nseg, arr(0), arr(2), arr(1), arr(3), P.at(dO), P.at(dWs),
                                              None if drl is None else drl.data_ptr(), None if steps is None else ctypes.addressof(steps), hip.stream())
-            _sync()
+            torch.cuda.synchronize()
             assert rc == 0, (name, rc)
-            assert ws.pads_untouched(dWs.cpu()), f"{name}: a word around the slab workspace changed"
-            return dO.cpu()
+            assert dWs.pads_untouched(), f"{name}: a word around the slab workspace changed"
+            return dO.flat()
         flat = launch()
         chain = R.chain_hw2(M, splits, nseg)
-        _judge(_group("f16x2_wgrad_multi"), f"{name} [{kind}] hw2+hw_reduce4 (splits {splits})", out, flat, ref, S, chain, 3e-6)
+        SUM.judge("f16x2_wgrad_multi", f"{name} [{kind}] hw2+hw_reduce4 (splits {splits})", out, flat, ref, S, chain, 3e-6)
         true = sum(p.true() for p in ps) + (0 if out0 is None else out0.double())
-        _close(out.live(flat), true, 3e-6, name)
-        assert _same_bits(flat, launch()), f"{name}: two launches differ"
+        P.close(out.live(flat), true, 3e-6, name)
+        assert P.same_bits(flat, launch()), f"{name}: two launches differ"
         if kind == "lattice":
             assert float((S / unit).max()) <= 2.0 ** 24
             assert torch.equal(out.live(flat).double(), ref), f"{name}: not the exact result"
@@ -670,7 +583,7 @@ MULTI_REFUSALS = [("Xsplits-null", dict(null=0), ENULL), ("x_scales-null", dict(
 @pytest.mark.parametrize("name,how,rc", MULTI_REFUSALS, ids=[r[0] for r in MULTI_REFUSALS])
 def test_wgrad_multi_refusals(name, how, rc):
     """the workspace query returns 0 where the shape constraints do not hold, and the launch its code; dW and the workspace stay all-sentinel"""
-    hip, L = _abi()
+    hip, L = P.abi()
     nseg = how.get("nseg", 2)
     n = max(1, min(nseg, 16))
     a = dict(N_img=1, Hi=32, Wi=64, Ci=256, ldx=256, Ho=32, Wo=64, Co=256, ldy=256, KH=1, KW=1, stride=1, pad=0, dil=1, ldo=256, beta=0, alpha=1.0, nbatch=1)
@@ -678,24 +591,23 @@ def test_wgrad_multi_refusals(name, how, rc):
     d = hip.WgradDesc(**a)
     if "desc" in how or "nseg" in how:
         assert L.sp_conv_wgrad_f16x2_multi_workspace(ctypes.byref(d), nseg) == 0
-    planes = torch.zeros(2048 * 256 * 2 + 32, dtype=torch.int16, device=_dev())
-    one = _f32([1.0])
-    out, ws = G.Guarded(1, 256, 256, 260, fill="sentinel"), G.Guarded(1, 1, 4096, 4096, fill="sentinel")
-    dO, dWs = _up(out), _up(ws)
+    planes = torch.zeros(2048 * 256 * 2 + 32, dtype=torch.int16, device=P.dev())
+    one = P.f32([1.0])
+    dO, dWs = P.up(P.Guarded(1, 256, 256, 260, fill="sentinel")), P.output(4096)
     cols = [[planes.data_ptr()] * n, [one.data_ptr()] * n, [planes.data_ptr()] * n, [one.data_ptr()] * n]
     if "inner" in how:
         i, v = how["inner"]
         cols[i][n - 1] = None if v is None else cols[i][n - 1] + v
-    args = [(ctypes.c_void_p * n)(*col) for col in cols] + [_at(dO, out), _at(dWs, ws)]
+    args = [(ctypes.c_void_p * n)(*col) for col in cols] + [P.at(dO), P.at(dWs)]
     if "null" in how:
         args[how["null"]] = None
-    drl = torch.zeros(1, dtype=torch.int32, device=_dev())
+    drl = torch.zeros(1, dtype=torch.int32, device=P.dev())
     steps = (ctypes.c_int * n)(*([0] * n))
     rc_got = L.sp_conv_wgrad_f16x2_multi(ctypes.byref(d), nseg, *args, drl.data_ptr() if how.get("row_last") else None,
                                          ctypes.addressof(steps) if how.get("seg_steps") else None, hip.stream())
-    _sync()
+    torch.cuda.synchronize()
     assert rc_got == rc, (name, rc_got)
-    assert out.all_untouched(dO.cpu()) and ws.all_untouched(dWs.cpu()), f"{name}: a refused call wrote"
+    assert dO.untouched() and dWs.untouched(), f"{name}: a refused call wrote"
 
 
 SPLIT_REFUSALS = [
@@ -733,10 +645,10 @@ SPLIT_REFUSALS = [
 
 @pytest.mark.parametrize("name,fn,args,rc", SPLIT_REFUSALS, ids=[r[0] for r in SPLIT_REFUSALS])
 def test_splitter_refusals(name, fn, args, rc):
-    hip, L = _abi()
-    x, out, sc = Raw(4096 * 4, init=np.ones(4096, np.float32)), Raw(4096 * 4), Raw(256)
+    hip, L = P.abi()
+    x, out, sc = P.raw(4096 * 4, init=np.ones(4096, np.float32)), P.raw(4096 * 4), P.raw(256)
     assert getattr(L, fn)(*args(x.ptr, out.ptr, sc.ptr), hip.stream()) == rc, name
-    _sync()
+    torch.cuda.synchronize()
     assert out.untouched() and sc.untouched() and x.untouched(), f"{name}: a refused call wrote"
     if fn == "sp_split2_f16_cols" and rc == EINVAL and "+4B" not in name:
         a = args(x.ptr, out.ptr, sc.ptr)

@@ -245,7 +245,7 @@ def test_validation_metrics_match_the_real_reference():
     enter bit-exact, STDE <= 4 ulp; the reference collects rows in float32, so table entries are held to 1e-6 and the float64
     per-image score rows to 1e-9."""
     from helpers import metrics_table, toy_multimatch
-    from test_oracle_golden import _eval_golden
+    from helpers import eval_golden as _eval_golden
     from scanpaths_amd.utils.evaluation import evaluation_performance_related, human_evaluation
     g, (gt, pred, perf, alloc), loader, qids = _eval_golden()
     cur, cur_std, scores = evaluation_performance_related(gt, pred, perf, alloc, multimatch=toy_multimatch)

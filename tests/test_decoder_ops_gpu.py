@@ -2,7 +2,7 @@
 friendly op-level case never reaches: every HIP op -- through scanpaths_amd.functional or the ctypes ABI -- against a plain torch fp64 CPU
 restatement of the same lines of the reference, forward and every input gradient.
 
-Bars: ordinary-magnitude cases use the bar tests/test_ops_gpu.py already holds the op to, with the same metric (_close: max error over
+Bars: ordinary-magnitude cases use the bar tests/test_ops_gpu.py already holds the op to, with the same metric (parity.close: max error over
 max(1, max |ref|)).  Stress cases (scores / logits spanning tens of units, where expf's error grows with its argument) use the rule of
 tests/test_salmaps_gpu.py: bar = max(existing bar, 10 x max|ref32 - ref64|), ref32 = the SAME restatement in fp32 on the CPU -- both sides
 of that difference come from the reference, never from the kernel; the factor 10 is the margin for another summation order.
@@ -15,36 +15,11 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-from test_ops_gpu import _close, _dev, _rand
+from parity import Worst, dev as _dev, rand as _rand, stress_bar
 
 pytestmark = pytest.mark.gpu
 
 HC = 64
-
-
-class _Worst:
-    """_close with the figure kept: err / bar of every comparison of one test, the worst printed at its end (or at the failing one)"""
-    def __init__(self, name):
-        self.name, self.rows = name, []
-
-    def close(self, got, ref, bar, what):
-        a, b = got.detach().cpu().double(), ref.detach().cpu().double()
-        assert a.shape == b.shape, (self.name, what, a.shape, b.shape)
-        err = (a - b).abs().max().item() / max(1.0, b.abs().max().item()) if a.numel() else 0.0
-        self.rows.append((err / bar, what, err, bar))
-        if not err <= bar:
-            self.report()
-        _close(got, ref, bar, f"{self.name} {what}")
-
-    def report(self):
-        r = max(self.rows, key=lambda t: (t[0] != t[0], t[0]))
-        print(f"PARITY {self.name}: worst err/bar {r[0]:.3f} ({r[1]}: err {r[2]:.2e}, bar {r[3]:.1e}; {len(self.rows)} comparisons)")
-
-
-def _stress_bar(base, r32, r64):
-    """max(existing bar, 10 max|ref32 - ref64|) in _close's metric"""
-    r32, r64 = r32.detach().double(), r64.detach().double()
-    return max(base, 10.0 * (r32 - r64).abs().max().item() / max(1.0, r64.abs().max().item()))
 
 
 def _leaf(t, dtype):
@@ -94,7 +69,7 @@ def test_list_attention_at_edge_shapes(T, R, D):
     """listatt_fwd/bwd_kernel (baseline_attention.py:67-88, 99-123): T = 1, T a multiple of 4 (four entries per reduction round), T = MAXT
     and MAXT - 1, D below / at / around one 256-thread pass.  T = 1: the softmax is exactly 1, so mem is L[0], dL is dmem and du is 0, bit
     for bit.  Two calls give identical bits."""
-    w = _Worst(f"list_attention T={T} R={R} D={D}")
+    w = Worst(f"list_attention T={T} R={R} D={D}")
     Lst, u, gm = _rand(T, R, D, seed=11), _rand(D, seed=12, scale=1.5 / math.sqrt(D)), _rand(R, D, seed=13)
     memr, dLr, dur = _att_ref(Lst, u, gm, torch.float64)
     mem, dL, du = _att_hip(Lst, u, gm)
@@ -114,7 +89,7 @@ def test_list_attention_stress(kind):
     """one dominant score (the scores of row 0 span about +-60: the softmax saturates, exp of the others underflows towards 0) and T
     identical entries (all weights 1/T, the score gradient a difference of equal numbers).  Bars by the ref32 rule."""
     T, R, D = 8, 3, 513
-    w = _Worst(f"list_attention {kind}")
+    w = Worst(f"list_attention {kind}")
     Lst, u, gm = _rand(T, R, D, seed=21), _rand(D, seed=22, scale=1.5 / math.sqrt(D)), _rand(R, D, seed=23)
     if kind == "scores_span_60":
         sc = (Lst.double() * u.double()).sum(-1)[:, 0]
@@ -126,7 +101,7 @@ def test_list_attention_stress(kind):
     r64, r32 = _att_ref(Lst, u, gm, torch.float64), _att_ref(Lst, u, gm, torch.float32)
     got = _att_hip(Lst, u, gm)
     for g, a, b, base, what in zip(got, r32, r64, (3e-6, 1e-5, 1e-5), ("mem", "dL", "du")):
-        w.close(g, b, _stress_bar(base, a, b), what)
+        w.close(g, b, stress_bar(base, a, b), what)
     w.report()
 
 
@@ -158,7 +133,7 @@ def test_semantic_pool_at_edge_shapes(S, B, P, C, seed, sbc):
     exactly / plus one, three chunks, C = 4 (one channel quad), C = 260 (a second quad round of the backward wave; not a multiple of 256),
     C = 512 (every thread of the forward block).  The [S,B,C] form is bit-equal to the [B,S,C] one."""
     from scanpaths_amd import functional as F
-    w = _Worst(f"semantic_pool S={S} B={B} P={P} C={C} sbc={sbc}")
+    w = Worst(f"semantic_pool S={S} B={B} P={P} C={C} sbc={sbc}")
     a, vf, g = _pool_inputs(S, B, P, C, seed)
     ref, dar, dvr, pre = _pool_ref(a, vf, g)
     _margin(pre, "pooled")
@@ -213,7 +188,7 @@ def test_semantic_pool_backward_writes_exact_zeros_for_dead_samples(sbc):
     # and against fp64 (the dense call)
     _, dar, dvr, pre = _pool_ref(a.cpu(), vf.cpu(), g.cpu())
     _margin(pre, "pooled")
-    w = _Worst(f"semantic_pool row_last sbc={sbc}")
+    w = Worst(f"semantic_pool row_last sbc={sbc}")
     w.close(da, dar, 3e-6, "d amaps")
     w.close(dvf, dvr, 3e-6, "d vf")
     w.report()
@@ -236,7 +211,7 @@ def test_im2col3x3_and_its_adjoint(S, R, H, W_, KP):
     """im2col1_multi_kernel / col2im1_multi_kernel: one to three streams, no padding columns (KP = 9) and some, 1 x 1 / 1 x N / N x 1 maps
     (every tap but the centre column / row falls into the zero padding).  Forward is a gather: equal bits; the adjoint sums <= 9 values."""
     from scanpaths_amd import functional as F
-    w = _Worst(f"im2col3x3 S={S} R={R} {H}x{W_} KP={KP}")
+    w = Worst(f"im2col3x3 S={S} R={R} {H}x{W_} KP={KP}")
     maps, g = _rand(S, R, H, W_, seed=31), _rand(R, H * W_, KP, seed=32)
     ref = _im2col_ref(maps, KP)
     mr = maps.double().requires_grad_(True)
@@ -328,10 +303,10 @@ _GRAD_NAMES = ("dZ", "dcb", "dw2", "db2", "ddpre")
 def _head_compare(w, got, ref, r32=None):
     (o, g), (o64, g64, _) = got, ref
     for k, name in enumerate(_OUT_NAMES[:len(o64)]):
-        w.close(o[k], o64[k], _OUT_BARS[k] if r32 is None else _stress_bar(_OUT_BARS[k], r32[0][k], o64[k]), name)
+        w.close(o[k], o64[k], _OUT_BARS[k] if r32 is None else stress_bar(_OUT_BARS[k], r32[0][k], o64[k]), name)
     for k, name in enumerate(_GRAD_NAMES):
         if g64[k] is not None:
-            w.close(g[k], g64[k], 3e-5 if r32 is None else _stress_bar(3e-5, r32[1][k], g64[k]), name)
+            w.close(g[k], g64[k], 3e-5 if r32 is None else stress_bar(3e-5, r32[1][k], g64[k]), name)
 
 
 _ALL = [(1, False, False), (2, True, True), (2, False, True), (1, True, False)]        # (nheads, per_sample, softmax): every value of every axis
@@ -346,7 +321,7 @@ def test_head_finish_at_edge_shapes(hw, nh, per_sample, softmax):
     around one 256-thread pass of the softmax loops, and 78 x 78 with S = MAXS = 256 duration sites; S = 1 at 3 x 3.  softmax = True forward AND
     backward (the RL phase differentiates it), one and two heads, shared and per-sample composed biases; cotangents on all four outputs."""
     Hm, Wm = hw
-    w = _Worst(f"head_finish {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
+    w = Worst(f"head_finish {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
     ins = _head_inputs(Hm, Wm, nh, per_sample, 2, seed=40)
     cots = _head_cots(2, Hm * Wm, nh, 40)
     ref = _head_ref(*ins, nh, 2, softmax, per_sample, cots, torch.float64)
@@ -359,7 +334,7 @@ def test_head_finish_at_edge_shapes(hw, nh, per_sample, softmax):
 def test_head_finish_with_wider_rows_leaves_the_unused_columns_zero():
     """ldz = used columns + 6: the kernel addresses rows by ldz and dZ's columns behind the heads' are exact zeros"""
     Hm, Wm, nh = 7, 8, 2
-    w = _Worst("head_finish ldz = used + 6")
+    w = Worst("head_finish ldz = used + 6")
     ins = _head_inputs(Hm, Wm, nh, False, 2, extra=6, seed=50)
     cots = _head_cots(2, Hm * Wm, nh, 50)
     ref = _head_ref(*ins, nh, 2, True, False, cots, torch.float64)
@@ -382,7 +357,7 @@ def test_head_finish_without_dpre_sums_the_49_taps_itself(hw, nh, per_sample, so
     semantics (a tap outside the intermediate map carries neither value nor composed bias) are the reference's; the gradients include
     dcb[2:51] (a sum over the sites at which the tap is inside) and dZ[..., 2:51] (the scatter of the site gradients)."""
     Hm, Wm = hw
-    w = _Worst(f"head_finish dpre=None {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
+    w = Worst(f"head_finish dpre=None {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
     ins = _head_inputs(Hm, Wm, nh, per_sample, HC, seed=seed)
     assert ins[4] is None and ins[0].shape[-1] == nh * HC
     cots = _head_cots(2, Hm * Wm, nh, seed)
@@ -400,7 +375,7 @@ def test_head_finish_softmax_stress():
     """logits spanning about +-40 (terminate logit near -40, action map up to +40): the softmax saturates on a few pixels; bars by the ref32
     rule"""
     Hm, Wm, nh = 15, 17, 2
-    w = _Worst("head_finish softmax logits span 80")
+    w = Worst("head_finish softmax logits span 80")
     Z, cb, w2, b2, dpre = _head_inputs(Hm, Wm, nh, False, 2, seed=70)
     for hd in range(nh):
         Z[..., hd * 2 + 1] *= 40.0 / Z[..., hd * 2 + 1].abs().max()
@@ -425,7 +400,7 @@ def test_head_sal_reads_its_logit_gradient_in_place(hw, nh, per_sample, softmax)
     from scanpaths_amd import functional as F
     Hm, Wm = hw
     B, P, T = 2, Hm * Wm, 2
-    w = _Worst(f"head_sal {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
+    w = Worst(f"head_sal {Hm}x{Wm} nh={nh} per_sample={per_sample} softmax={softmax}")
     dev = _dev()
     G, GA = _rand(nh, B, T, P + 1, seed=86), _rand(T, nh, B, P, seed=87)
     Zs = [_head_inputs(Hm, Wm, nh, per_sample, 2, seed=80 + 3 * t)[0] for t in range(T)]
@@ -470,7 +445,7 @@ def test_mul_relu_beyond_the_block_cap():
     of 256 threads cover in one pass (grid-stride loop), the broadcast b[i % nb] crossing the wrap"""
     from scanpaths_amd import functional as F
     n = 2048 * 256 + 3
-    w = _Worst(f"mul_relu a=(2, {n})")
+    w = Worst(f"mul_relu a=(2, {n})")
     a, b, go = _away(_rand(2, n, seed=91), 0.5), _away(_rand(n, seed=92), 0.5), _rand(2, n, seed=93)
     ar, br = a.double().requires_grad_(True), b.double().requires_grad_(True)
     pre = ar * br
@@ -512,7 +487,7 @@ def test_channel_mean_at_edge_shapes(C, M):
     one 256-wide wave pass less / exactly / plus a quad, eight passes; M = 16385 rows = one more than the 4096 blocks x 4 waves of the capped
     grid take in one round"""
     from scanpaths_amd import functional as F
-    w = _Worst(f"channel_mean C={C} M={M}")
+    w = Worst(f"channel_mean C={C} M={M}")
     x, g = _rand(M, C, seed=98), _rand(M, seed=99)
     xr = x.double().requires_grad_(True)
     mr = xr.mean(-1)
@@ -588,7 +563,7 @@ def test_scanpath_loss_on_hand_built_rows(B, T, A):
     """loss_rows_kernel / loss_final_kernel (loss.py:10-14, 27-32; train.py:192-197) against oracle.supervised_loss in fp64: A = 2 and one
     256-thread pass less / exactly / plus one class; soft and terminate targets, masked rows, duration 0, sigma2 1e-3 and 10, lambda_1 =
     0.37, explicit mask sums.  Masked rows receive exact zeros."""
-    w = _Worst(f"scanpath_loss B={B} T={T} A={A}")
+    w = Worst(f"scanpath_loss B={B} T={T} A={A}")
     ins = _loss_inputs(B, T, A)
     ref, got = _loss_ref(*ins, 0.37, torch.float64), _loss_hip(*ins, 0.37)
     for g, r, name in zip(got, ref, _LOSS_NAMES):
@@ -601,11 +576,11 @@ def test_scanpath_loss_on_hand_built_rows(B, T, A):
 
 def test_scanpath_loss_with_an_underflowing_target_probability():
     """one row whose target logit lies 100 below the row maximum: p underflows in fp32, log(p + eps) is log(eps); bars by the ref32 rule"""
-    w = _Worst("scanpath_loss target logit 100 below the maximum")
+    w = Worst("scanpath_loss target logit 100 below the maximum")
     ins = _loss_inputs(2, 3, 257, stress=True)
     ref, r32, got = _loss_ref(*ins, 0.37, torch.float64), _loss_ref(*ins, 0.37, torch.float32), _loss_hip(*ins, 0.37)
     for g, a, r, name in zip(got, r32, ref, _LOSS_NAMES):
-        w.close(g, r, _stress_bar(2e-6, a, r), name)
+        w.close(g, r, stress_bar(2e-6, a, r), name)
     w.report()
 
 
@@ -658,7 +633,7 @@ def test_clip_adam_and_scale_by_through_the_abi(n):
     from scanpaths_amd import hip
     from scanpaths_amd.functional import check
     dev, L = _dev(), hip.lib()
-    w = _Worst(f"sp_clip_adam / sp_scale_by n={n}")
+    w = Worst(f"sp_clip_adam / sp_scale_by n={n}")
     p0, g0, m0 = _rand(n, seed=130), _rand(n, seed=131) * 3, _rand(n, seed=132) * 0.1
     v0 = (_rand(n, seed=133) * 0.1) ** 2 + 1e-4
     zero = slice(1, 2) if n == 3 else slice(1000, 1300) if n > 3 else slice(0, 0)
@@ -703,7 +678,7 @@ def test_rl_log_probabilities(B, T):
     scanpaths_amd.models.loss: one step, one 64-lane pass less / exactly / plus one, three passes; an all-zero mask row (exact zero value
     and gradients), probabilities of exactly 0 (log(eps))"""
     from scanpaths_amd.models.loss import LogAction, LogDuration
-    w = _Worst(f"LogAction / LogDuration B={B} T={T}")
+    w = Worst(f"LogAction / LogDuration B={B} T={T}")
     g = np.random.Generator(np.random.PCG64(140 + T))
     p = torch.from_numpy(g.random((B, T)).astype(np.float32))
     mask = torch.from_numpy((g.random((B, T)) < 0.7).astype(np.float32))

@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as TF
 
 import f16x2_ref as R
-import gemm_ref as G
+import parity as P
 
 F32, F16 = np.float32, np.float16
 KINDS = ("gauss", "lattice")
@@ -201,26 +201,12 @@ def test_planes_are_within_the_representation_bound_of_the_true_product(group, k
 
 
 # ---- plans -----------------------------------------------------------------------------------------------------------------------
-def _abi():
-    from scanpaths_amd import hip
-    return hip, hip.lib()
-
-
-def hw_desc(hip, p, **kw):
-    c = p.c
-    a = dict(N_img=c.N_img, Hi=c.Hi, Wi=c.Wi, Ci=c.Ci, ldx=c.Ci, Ho=c.Ho, Wo=c.Wo, Co=c.Co, ldy=p.ldy, KH=c.KH, KW=c.KW, stride=c.stride, pad=c.pad,
-             dil=c.dil, ldo=p.ldo, beta=c.beta, alpha=c.alpha, nbatch=c.nbatch, x_scale_vec=int(c.xvec), y_scale_vec=int(c.yvec),
-             strideX=p.xrows * c.Ci if c.nbatch > 1 else 0, strideY=p.M * p.ldy if c.nbatch > 1 else 0, strideO=c.Co * p.ldo if c.nbatch > 1 else 0)
-    a.update(kw)
-    return hip.WgradDesc(**a)
-
-
 def test_split_plans_are_the_librarys():
-    hip, L = _abi()
+    hip, L = P.abi()
     for group in ("hw", "hw_x1", "hw_batched"):
         for p in _problems(group, "gauss"):
             want = p.splits * p.c.Co * p.ldo * 4 if p.splits > 1 else 0
-            assert L.sp_conv_wgrad_f16x2_workspace(ctypes.byref(hw_desc(hip, p))) == want, p.c.name
+            assert L.sp_conv_wgrad_f16x2_workspace(ctypes.byref(R.hw_desc(hip, p))) == want, p.c.name
     g = np.random.Generator(np.random.PCG64(5))
     for _ in range(300):
         M, Co, Ci, taps = int(g.integers(1, 200000)), 16 * int(g.integers(1, 40)), 16 * int(g.integers(1, 40)), int(g.choice([1, 9]))
@@ -295,7 +281,7 @@ def test_the_bar_sees_one_lost_k(group):
             continue
         ref, S = p.planes()
         broken, _ = p.planes(drop=p.last_live_k())
-        assert ((broken - ref).abs() > G.bar(S, p.chain)).any(), (group, p.c.name, p.chain)
+        assert ((broken - ref).abs() > P.bar(S, p.chain)).any(), (group, p.c.name, p.chain)
         pl = _problem(group, p.c, "lattice")
         assert not torch.equal(pl.planes(drop=pl.last_live_k())[0].float(), pl.planes()[0].float()), p.c.name
         n += 1
@@ -313,7 +299,7 @@ def test_the_bar_sees_one_lost_cross_term(group):
             continue
         ref, S = p.planes()
         broken, _ = p.planes(cross=nkt - 1)
-        seen = bool(((broken - ref).abs() > G.bar(S, p.chain)).any())
+        seen = bool(((broken - ref).abs() > P.bar(S, p.chain)).any())
         if nkt <= 2:
             assert seen, (group, p.c.name, p.chain)
         else:

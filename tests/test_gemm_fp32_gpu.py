@@ -2,7 +2,7 @@
 against the plain fp64 restatement of tests/gemm_ref.py (held to torch's fp64 conv and autograd by tests/test_gemm_ref_cpu.py), at the tile, chunk,
 slice and split edges listed there.
 
-Every operand and output lies inside a larger allocation (gemm_ref.Guarded): operand pads, batch gaps and guards are NaN, output pads, gaps, guards
+Every operand and output lies inside a larger allocation (parity.Guarded): operand pads, batch gaps and guards are NaN, output pads, gaps, guards
 and workspace tails a sentinel word.  After each launch every sentinel word must be unchanged and every live word finite and inside the ELEMENT-WISE
 bar |got - ref| <= c 2^-24 S + 2^-149 (S the contraction over absolute values, c the launch's longest chain of dependent roundings, derived in
 gemm_ref.py).  The max-norm bars of tests/test_ops_gpu.py (3e-6 sqrt(K / 32) for GEMMs, 2e-6 / 3e-6 for convs, against max(1, max|ref|)) stay as a
@@ -11,60 +11,19 @@ summary line per group at its end (profiles/gemm_fp32_parity.md)."""
 import ctypes
 import functools
 import math
-import time
 
 import pytest
 import torch
 
 import gemm_ref as R
-from test_ops_gpu import _close, _dev
+import parity as P
 
 pytestmark = pytest.mark.gpu
 
-SUMMARY = {}          # group -> [(err / bar, case, err, bar, chain)]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _summary():
-    t0 = time.time()
-    yield
-    for group, rows in SUMMARY.items():
-        q, name, err, b, chain = max(rows)
-        print(f"\nPARITY-SUMMARY {group}: {len(rows)} comparisons, worst err/bar {q:.3f} at {name} (err {err:.2e}, bar {b:.2e}, c {chain})", end="")
-    print(f"\nPARITY-SUMMARY total {time.time() - t0:.1f} s")
-
-
-def _abi():
-    from scanpaths_amd import hip
-    return hip, hip.lib()
-
-
-def _up(g):
-    return None if g is None else g.flat.to(_dev())
-
-
-def _at(dflat, g, extra_bytes=0):
-    return None if dflat is None else dflat.data_ptr() + 4 * g.start + extra_bytes
-
-
-def _vec(t):
-    """a bias vector inside NaN guards"""
-    return None if t is None else R.Guarded(1, 1, t.numel(), t.numel(), fill="nan", data=t)
-
-
-def _judge(group, name, out, flat_after, ref, S, chain, legacy):
-    """guards, finiteness, the element-wise bar, the max-norm bar; the figure is kept and printed"""
-    assert out.pads_untouched(flat_after), f"{group} {name}: a word outside the live output changed"
-    got = out.live(flat_after)
-    q, i, err, b = R.worst(got, ref, S, chain)
-    SUMMARY.setdefault(group, []).append((q, name, err, b, chain))
-    print(f"PARITY {group} {name}: err/bar {q:.3f} (err {err:.2e}, bar {b:.2e}, c {chain}, element {i})")
-    assert q <= 1.0, f"{group} {name}: err {err:.3e} > bar {b:.3e} at element {i} (c = {chain})"
-    _close(got, ref, legacy, f"{group} {name}")
-
-
-def _same_bits(a, b):
-    return bool((a.view(torch.int32) == b.view(torch.int32)).all())
+SUM = P.Summary()
+_summary = SUM.fixture()
+# the operands and the fp64 restatement of a case, built once
+_igemm_problem, _skinny_problem, _wgrad_problem = (functools.lru_cache(maxsize=None)(cls) for cls in (R.IgemmProblem, R.SkinnyProblem, R.WgradProblem))
 
 
 def _gemm_legacy(K):
@@ -83,44 +42,36 @@ def _igemm_desc(hip, p, ws_ptr=None, ksplit=0):
 
 def _launch_igemm(p, ksplit):
     """one sp_conv_igemm launch on fresh copies of the guarded buffers -> (output allocation, workspace allocation or None), on the host"""
-    hip, L = _abi()
-    dX, dW, dO = _up(p.X), _up(p.W), _up(p.out)
-    gb = _vec(p.bias)
-    dB = _up(gb)
-    ws = p.ws if ksplit > 1 else None
-    dWs = _up(ws)
-    d = _igemm_desc(hip, p, _at(dWs, ws), ksplit)
-    rc = L.sp_conv_igemm(ctypes.byref(d), _at(dX, p.X), _at(dW, p.W), _at(dB, gb), _at(dO, p.out), hip.stream())
+    hip, L = P.abi()
+    dX, dW, dO = P.up(p.X), P.up(p.W), P.up(p.out)
+    dB, dWs = P.operand(p.bias), P.up(p.ws if ksplit > 1 else None)
+    d = _igemm_desc(hip, p, P.at(dWs), ksplit)
+    rc = L.sp_conv_igemm(ctypes.byref(d), P.at(dX), P.at(dW), P.at(dB), P.at(dO), hip.stream())
     torch.cuda.synchronize()
     assert rc == 0, (p.c.name, rc)
-    return dO.cpu(), (None if dWs is None else dWs.cpu())
+    return dO.flat(), (None if dWs is None else dWs.flat())
 
 
 def _run_igemm(group, p, legacy):
     c = p.c
     ref, S = p.reference()
     flat, ws_after = _launch_igemm(p, c.ksplit)
-    _judge(group, c.name, p.out, flat, ref, S, p.chain, legacy)
+    SUM.judge(group, c.name, p.out, flat, ref, S, p.chain, legacy)
     if c.ksplit > 1:
         assert p.ws.pads_untouched(ws_after), f"{c.name}: a word around the split-K workspace changed"
         split = R.igemm_plan(c.Kc, c.KH * c.KW, c.ksplit, c.nbatch, c.mode)[2] > 1
         if split:
             again, _ = _launch_igemm(p, c.ksplit)
-            assert _same_bits(flat, again), f"{c.name}: two split-K launches differ"
+            assert P.same_bits(flat, again), f"{c.name}: two split-K launches differ"
             live = p.ws.live(ws_after).reshape(c.ksplit, -1)
             used = R.igemm_plan(c.Kc, 1, c.ksplit)[2]
-            assert torch.isfinite(live[:used]).all() and p.ws.live(ws_after.view(torch.int32)).reshape(c.ksplit, -1)[used:].eq(R.SENTINEL).all(), \
+            assert torch.isfinite(live[:used]).all() and p.ws.live(ws_after.view(torch.int32)).reshape(c.ksplit, -1)[used:].eq(P.SENTINEL).all(), \
                 f"{c.name}: the slabs in use are {used} of {c.ksplit}"
         else:            # ksplit is not honoured (batched, or more than one tap): the unsplit result, and the workspace is never touched
             assert p.ws.all_untouched(ws_after), f"{c.name}: the workspace of an ignored ksplit was written"
             plain, _ = _launch_igemm(p, 0)
-            assert _same_bits(flat, plain), f"{c.name}: an ignored ksplit changed the result"
+            assert P.same_bits(flat, plain), f"{c.name}: an ignored ksplit changed the result"
     return flat
-
-
-@functools.lru_cache(maxsize=None)
-def _igemm_problem(case):
-    return R.IgemmProblem(case)
 
 
 @pytest.mark.parametrize("case", R.igemm_gemm_cases(), ids=lambda c: c.name)
@@ -136,62 +87,54 @@ def test_igemm_as_conv(case):
 def _launch_skinny(p, *, offs=None, null=()):
     """one sp_gemm_skinny launch -> (rc, output allocation on the host).  offs: byte offsets added to A, B, C, bias, workspace; null: names passed as
     NULL"""
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
     offs = offs or {}
-    dA, dB, dO = _up(p.A_buf), _up(p.B_buf), _up(p.out)
-    gb = _vec(p.bias)
-    dBias = _up(gb)
+    dA, dB, dO = P.up(p.A_buf), P.up(p.B_buf), P.up(p.out)
+    dBias = P.operand(p.bias)
     nbytes = L.sp_gemm_skinny_workspace(c.M, c.N, c.K, c.layout)
-    ws = R.Guarded(1, 1, nbytes // 4, nbytes // 4, fill="sentinel") if nbytes else None
-    dWs = _up(ws)
-    ptrs = {"A": _at(dA, p.A_buf, offs.get("A", 0)), "B": _at(dB, p.B_buf, offs.get("B", 0)), "C": _at(dO, p.out, offs.get("C", 0)),
-            "bias": _at(dBias, gb, offs.get("bias", 0)), "ws": _at(dWs, ws, offs.get("ws", 0))}
+    dWs = P.output(nbytes // 4) if nbytes else None
+    ptrs = {"A": P.at(dA, offs.get("A", 0)), "B": P.at(dB, offs.get("B", 0)), "C": P.at(dO, offs.get("C", 0)),
+            "bias": P.at(dBias, offs.get("bias", 0)), "ws": P.at(dWs, offs.get("ws", 0))}
     for k in null:
         ptrs[k] = None
     rc = L.sp_gemm_skinny(ptrs["A"], ptrs["B"], ptrs["bias"], ptrs["C"], c.M, c.N, c.K, p.lda, p.ldb, p.ldc, c.layout, c.alpha, int(c.relu),
                           ptrs["ws"], hip.stream())
     torch.cuda.synchronize()
-    if ws is not None:
-        assert ws.pads_untouched(dWs.cpu()), f"{c.name}: a word around the slice workspace changed"
-    return rc, dO.cpu()
-
-
-@functools.lru_cache(maxsize=None)
-def _skinny_problem(case):
-    return R.SkinnyProblem(case)
+    if dWs is not None:
+        assert dWs.pads_untouched(), f"{c.name}: a word around the slice workspace changed"
+    return rc, dO.flat()
 
 
 @pytest.mark.parametrize("case", R.skinny_cases(), ids=lambda c: c.name)
 def test_skinny(case):
     """sp_gemm_skinny, and -- sp_gemm_skinny_applies holds for every case -- sp_conv_igemm on the same guarded operands: both inside the bar (each
     with its own chain); bit equality between the two kernels is not asked"""
-    hip, L = _abi()
+    hip, L = P.abi()
     p, c = _skinny_problem(case), case
     assert L.sp_gemm_skinny_applies(c.M, c.N, c.K, p.lda, p.ldb, p.ldc, c.layout) == 1
     ref, S = p.reference()
     rc, flat = _launch_skinny(p)
     assert rc == 0, rc
-    _judge("skinny", c.name, p.out, flat, ref, S, p.chain, _gemm_legacy(c.K))
+    SUM.judge("skinny", c.name, p.out, flat, ref, S, p.chain, _gemm_legacy(c.K))
     if p.nsplit > 1:
         rc, again = _launch_skinny(p)
-        assert rc == 0 and _same_bits(flat, again), f"{c.name}: two sliced launches differ"
+        assert rc == 0 and P.same_bits(flat, again), f"{c.name}: two sliced launches differ"
     # the same operands through the 128-row tile kernel
-    dA, dB, dO = _up(p.A_buf), _up(p.B_buf), _up(p.out)
-    gb = _vec(p.bias)
-    dBias = _up(gb)
+    dA, dB, dO = P.up(p.A_buf), P.up(p.B_buf), P.up(p.out)
+    dBias = P.operand(p.bias)
     d = hip.ConvDesc(N_img=c.M, Hi=1, Wi=1, Kc=c.K, ldx=p.lda, Ho=1, Wo=1, Nout=c.N, ldc=p.ldc, KH=1, KW=1, stride=1, pad=0, dil=1, mode=c.layout,
                      ldw=p.ldb, alpha=c.alpha, beta=0, relu=int(c.relu), nbatch=1)
-    rc = L.sp_conv_igemm(ctypes.byref(d), _at(dA, p.A_buf), _at(dB, p.B_buf), _at(dBias, gb), _at(dO, p.out), hip.stream())
+    rc = L.sp_conv_igemm(ctypes.byref(d), P.at(dA), P.at(dB), P.at(dBias), P.at(dO), hip.stream())
     torch.cuda.synchronize()
     assert rc == 0, rc
-    _judge("skinny_vs_igemm", c.name, p.out, dO.cpu(), ref, S, R.chain_igemm(c.K, 1), _gemm_legacy(c.K))
+    SUM.judge("skinny_vs_igemm", c.name, p.out, dO.flat(), ref, S, R.chain_igemm(c.K, 1), _gemm_legacy(c.K))
 
 
 @pytest.mark.parametrize("r", R.skinny_refusals(), ids=lambda r: r.name)
 def test_skinny_refusals(r):
     """every call outside the domain of include/scanpaths_amd.h returns its code before anything is launched: the output stays all-sentinel"""
-    hip, L = _abi()
+    hip, L = P.abi()
     p = R.SkinnyProblem(R._SK(r.name, r.M, r.N, r.K, r.layout if r.layout in (0, 1) else 1, 1.0, True, False, r.ldc_pad, 0))
     p.lda, p.ldb = r.K + r.lda_pad, (r.K if r.layout == 0 else r.N) + r.ldb_pad
     p.c = p.c._replace(layout=r.layout)
@@ -203,32 +146,26 @@ def test_skinny_refusals(r):
     assert p.out.all_untouched(flat), f"{r.name}: a refused call wrote to the output"
 
 
-@functools.lru_cache(maxsize=None)
-def _wgrad_problem(case):
-    return R.WgradProblem(case)
-
-
 def _launch_wgrad(p):
-    hip, L = _abi()
+    hip, L = P.abi()
     d = p.desc(hip)
     splits, nbytes = R.wgrad_splits(L, d, p.c.Co, p.ldo)
-    dX, dY, dO = _up(p.X), _up(p.dY), _up(p.out)
-    ws = R.Guarded(1, 1, nbytes // 4, nbytes // 4, fill="sentinel") if nbytes else None          # exactly the queried size, sentinels around it
-    dWs = _up(ws)
-    rc = L.sp_conv_wgrad(ctypes.byref(d), _at(dX, p.X), _at(dY, p.dY), _at(dO, p.out), _at(dWs, ws), hip.stream())
+    dX, dY, dO = P.up(p.X), P.up(p.dY), P.up(p.out)
+    dWs = P.output(nbytes // 4) if nbytes else None          # exactly the queried size, sentinels around it
+    rc = L.sp_conv_wgrad(ctypes.byref(d), P.at(dX), P.at(dY), P.at(dO), P.at(dWs), hip.stream())
     torch.cuda.synchronize()
     assert rc == 0, (p.c.name, rc)
-    if ws is not None:
-        assert ws.pads_untouched(dWs.cpu()), f"{p.c.name}: a word around the slab workspace changed"
-    return splits, dO.cpu()
+    if dWs is not None:
+        assert dWs.pads_untouched(), f"{p.c.name}: a word around the slab workspace changed"
+    return splits, dO.flat()
 
 
 def _run_wgrad(group, p, legacy):
     ref, S = p.reference()
     splits, flat = _launch_wgrad(p)
-    _judge(group, p.c.name + f" (splits {splits})", p.out, flat, ref, S, R.chain_wgrad(p.M, splits), legacy)
+    SUM.judge(group, p.c.name + f" (splits {splits})", p.out, flat, ref, S, R.chain_wgrad(p.M, splits), legacy)
     if splits > 1:
-        assert _same_bits(flat, _launch_wgrad(p)[1]), f"{p.c.name}: two slab launches differ"
+        assert P.same_bits(flat, _launch_wgrad(p)[1]), f"{p.c.name}: two slab launches differ"
     return flat
 
 
@@ -252,7 +189,7 @@ def test_dispatcher_rules_hold_on_both_sides(monkeypatch):
     """functional._igemm takes the skinny kernel exactly where sp_gemm_skinny_applies holds (<= 64 rows, aligned pointers) and split-K exactly where
     tiles <= 64 and nkt >= _KSPLIT_MIN_NKT; forward and both gradients of functional.gemm inside the bar of the kernel that ran"""
     from scanpaths_amd import functional as F
-    hip, L = _abi()
+    hip, L = P.abi()
     calls = []
     real_ig, real_sk = L.sp_conv_igemm, L.sp_gemm_skinny
 
@@ -266,11 +203,11 @@ def test_dispatcher_rules_hold_on_both_sides(monkeypatch):
     monkeypatch.setattr(L, "sp_conv_igemm", spy_ig)
     monkeypatch.setattr(L, "sp_gemm_skinny", spy_sk)
     seen = set()
-    dev = _dev()
+    dev = P.dev()
     for name, M, K, N, layout, bias_off in DISPATCH:
-        s = R.seed_of("dispatch" + name)
-        a, b = R.randn(M, K, seed=s), (R.randn(N, K, seed=s + 1) if layout == "nk" else R.randn(K, N, seed=s + 1))
-        bias, gc = R.randn(N, seed=s + 2), R.randn(M, N, seed=s + 3)
+        s = P.seed_of("dispatch" + name)
+        a, b = P.randn(M, K, seed=s), (P.randn(N, K, seed=s + 1) if layout == "nk" else P.randn(K, N, seed=s + 1))
+        bias, gc = P.randn(N, seed=s + 2), P.randn(M, N, seed=s + 3)
         bm = b.t() if layout == "nk" else b                                                  # [K, N]
         ag, bg = a.to(dev).requires_grad_(True), b.to(dev).requires_grad_(True)
         biasg = torch.zeros(N + 4, device=dev)[1:N + 1].copy_(bias) if bias_off else bias.to(dev)
@@ -286,7 +223,7 @@ def test_dispatcher_rules_hold_on_both_sides(monkeypatch):
             ldw = (K if layout == "nk" else N)
             skinny = (m_ <= 64 and not (has_bias and bias_off) and n_ % 4 == 0
                       and L.sp_gemm_skinny_applies(m_, n_, k_, k_, ldw, n_, mode) == 1)
-            tiles, nkt = R.cdiv(m_, 128) * R.cdiv(n_, 128), R.cdiv(k_, 32)
+            tiles, nkt = P.cdiv(m_, 128) * P.cdiv(n_, 128), P.cdiv(k_, 32)
             split = not skinny and tiles <= 64 and nkt >= F._KSPLIT_MIN_NKT
             ks = max(2, min(nkt // F._KSPLIT_KT, 512 // tiles)) if split else 0
             expect.append(("skinny", 0) if skinny else ("igemm", ks))
@@ -297,15 +234,15 @@ def test_dispatcher_rules_hold_on_both_sides(monkeypatch):
         assert calls == expect, (name, calls, expect)
         assert F.FUSION_COUNTS["skinny_gemm"] == sum(e[0] == "skinny" for e in expect), (name, F.FUSION_COUNTS)
         ref, S = R.reference(a[None], bm[None], 0.5, bias)
-        _judge("dispatch", name + " forward", R.Guarded(1, M, N, N, fill="sentinel"), _as_guarded(out), ref, S, chains[0], _gemm_legacy(K))
+        SUM.judge("dispatch", name + " forward", P.Guarded(1, M, N, N, fill="sentinel"), _as_guarded(out), ref, S, chains[0], _gemm_legacy(K))
         ref, S = R.reference(gc[None], bm.t()[None], 0.5)
-        _judge("dispatch", name + " dA", R.Guarded(1, M, K, K, fill="sentinel"), _as_guarded(ag.grad), ref, S, chains[1], _gemm_legacy(N))
+        SUM.judge("dispatch", name + " dA", P.Guarded(1, M, K, K, fill="sentinel"), _as_guarded(ag.grad), ref, S, chains[1], _gemm_legacy(N))
         # dB = alpha dC^T A ("nk": [N, K]) or alpha A^T dC ("kn": [K, N]) on sp_conv_wgrad
         Co, Ci = (N, K) if layout == "nk" else (K, N)
         splits = R.wgrad_splits(L, F._gemm_wgrad_desc(M, Co, Ci, ldx=Ci, ldy=Co, ldo=Ci, alpha=0.5), Co, Ci)[0]
         lhs, rhs = (gc.t(), a) if layout == "nk" else (a.t(), gc)
         ref, S = R.reference(lhs[None], rhs[None], 0.5)
-        _judge("dispatch", name + f" dB (splits {splits})", R.Guarded(1, Co, Ci, Ci, fill="sentinel"), _as_guarded(bg.grad), ref, S,
+        SUM.judge("dispatch", name + f" dB (splits {splits})", P.Guarded(1, Co, Ci, Ci, fill="sentinel"), _as_guarded(bg.grad), ref, S,
                R.chain_wgrad(M, splits), _gemm_legacy(M))
     assert {("skinny", True), ("skinny", False)} <= seen
     assert ("split", True, "tiles<=64", "nkt>=8") in seen and ("split", False, "tiles<=64", "nkt<8") in seen and \
@@ -313,8 +250,8 @@ def test_dispatcher_rules_hold_on_both_sides(monkeypatch):
 
 
 def _as_guarded(t):
-    """a dense result of the dispatcher in the layout _judge reads: sentinel guards around the tensor's words"""
-    g = torch.full((R.GUARD,), R.SENTINEL, dtype=torch.int32).view(torch.float32)
+    """a dense result of the dispatcher in the layout SUM.judge reads: sentinel guards around the tensor's words"""
+    g = torch.full((P.GUARD,), P.SENTINEL, dtype=torch.int32).view(torch.float32)
     return torch.cat([g, t.detach().cpu().reshape(-1), g])
 
 

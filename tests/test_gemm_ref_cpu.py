@@ -8,11 +8,7 @@ import torch
 import torch.nn.functional as TF
 
 import gemm_ref as R
-
-
-def _abi():
-    from scanpaths_amd import hip
-    return hip, hip.lib()
+import parity as P
 
 
 @functools.lru_cache(maxsize=None)
@@ -21,7 +17,7 @@ def _problems(group):
         return [R.IgemmProblem(c) for c in R.igemm_gemm_cases() + R.igemm_conv_cases()]
     if group == "skinny":
         return [R.SkinnyProblem(c) for c in R.skinny_cases()]
-    hip, L = _abi()
+    hip, L = P.abi()
     ps = [R.WgradProblem(c) for c in R.wgrad_cases()]
     for p in ps:
         p.splits = R.wgrad_splits(L, p.desc(hip), p.c.Co, p.ldo)[0]
@@ -69,8 +65,8 @@ def test_wgrad_restatement_is_torchs_weight_gradient(case):
 
 
 def test_epilogue_restatement():
-    a, b = R.randn(2, 3, 5, seed=1), R.randn(1, 5, 4, seed=2)
-    bias, out0 = R.randn(4, seed=3), R.randn(2, 3, 4, seed=4)
+    a, b = P.randn(2, 3, 5, seed=1), P.randn(1, 5, 4, seed=2)
+    bias, out0 = P.randn(4, seed=3), P.randn(2, 3, 4, seed=4)
     ref, S = R.reference(a, b, -0.5, bias, out0, True)
     want = torch.relu(-0.5 * torch.matmul(a.double(), b.double()) + bias.double() + out0.double())
     assert torch.equal(ref, want)
@@ -81,7 +77,7 @@ def test_epilogue_restatement():
 # ---- the lists reach the branches they were written for ----------------------------------------------------------------
 def test_plans_of_gemm_ref_are_the_librarys():
     """skinny_plan against sp_gemm_skinny_workspace for every case, and sp_gemm_skinny_applies = 1 for every case"""
-    hip, L = _abi()
+    hip, L = P.abi()
     for p in _problems("skinny"):
         c = p.c
         want = p.nsplit * c.M * c.N * 4 if p.nsplit > 1 else 0
@@ -104,7 +100,7 @@ def test_skinny_cases_reach_both_epilogues_and_a_16k_last_slice():
 
 
 def test_skinny_refusal_table_agrees_with_applies():
-    hip, L = _abi()
+    hip, L = P.abi()
     for r in R.skinny_refusals():
         assert L.sp_gemm_skinny_applies(r.M, r.N, r.K, r.K + r.lda_pad, (r.K if r.layout == 0 else r.N) + r.ldb_pad, r.N + r.ldc_pad,
                                         r.layout) == r.applies, r
@@ -132,7 +128,7 @@ def test_wgrad_plan_never_leaves_a_split_empty():
     """rows_per_split is rounded up to 32 rows, so a plan could leave its last split without a row (the kernel would then store a slab of zeros:
     `if (nkt > 0)`).  Up to 20000 rows, at 1, 2 and 4 output tiles, no split count the plan chooses does: it keeps >= 256 rows per split
     (smax = M / 256), and rounding up to 32 moves a boundary by < 32 rows per split.  Were one found, its row count would belong in WG_ROWS."""
-    hip, L = _abi()
+    hip, L = P.abi()
     assert R.empty_split_rows(L, hip) == []
 
 
@@ -175,7 +171,7 @@ def test_the_bar_sees_one_lost_k(group):
             continue
         ref, S = p.reference()
         broken, _ = p.reference(drop=R.last_live_k(p.A))
-        assert ((broken - ref).abs() > R.bar(S, p.chain)).any(), (group, p.c.name, p.chain)
+        assert ((broken - ref).abs() > P.bar(S, p.chain)).any(), (group, p.c.name, p.chain)
         n += 1
     assert n > 20
 

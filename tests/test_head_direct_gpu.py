@@ -4,24 +4,19 @@ tests/head_direct_ref.py (held to torch's fp64 conv and autograd by tests/test_h
 path: full groups of four rows and group boundaries, the XCD site order, odd and > 8 slot counts, the second compaction round (S = 135), C / 4 > 128,
 one-site axes clipped on both sides, the 32-site limit, heads that no row selects, accumulate, padded ldt, dead rows.
 
-Float operands lie between NaN guards, outputs and the workspace (exactly the queried size) between sentinel guards (gemm_ref.Guarded): after each
-launch every word outside the live region is unchanged and every live word finite and inside the ELEMENT-WISE bar gemm_ref.bar(S, chain) (chains:
+Float operands lie between NaN guards, outputs and the workspace (exactly the queried size) between sentinel guards (parity.Guarded): after each
+launch every word outside the live region is unchanged and every live word finite and inside the ELEMENT-WISE bar parity.bar(S, chain) (chains:
 head_direct_ref.chain_*).  The max-norm bars tests/test_ops_gpu.py holds these ops to (2e-5 forward, 3e-5 gradients) stay as a second assertion.
 Every case runs on Gaussian data and on lattice data (small integers times a power of two: every summation order is exact), where the kernel must
 equal the fp64 result exactly (torch.equal in fp64).  sp_drt_direct_fwd and sp_drt_direct_bwd_weight run twice and must be bit-identical.  Each
 comparison prints a PARITY line, the module a summary per group (profiles/head_direct_parity.md)."""
 import functools
-import time
 
-import numpy as np
 import pytest
 import torch
 
-import gemm_ref as G
 import head_direct_ref as R
-import test_gemm_fp32_gpu as FP32
-from test_gemm_fp32_gpu import _abi, _at, _judge, _same_bits, _up
-from test_ops_gpu import _dev
+import parity as P
 
 pytestmark = pytest.mark.gpu
 
@@ -31,52 +26,9 @@ GROUPS = ("head_compose11_fwd", "head_compose11_bwd", "head_compose11_dcb", "hea
 FWD, GRAD = 2e-5, 3e-5            # the max-norm bars of test_direct_head_matches_two_conv_formulation
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _summary():
-    t0 = time.time()
-    yield
-    for group in GROUPS:
-        rows = FP32.SUMMARY.pop(group, None)
-        if rows:
-            q, name, err, b, chain = max(rows)
-            print(f"\nPARITY-SUMMARY {group}: {len(rows)} comparisons, worst err/bar {q:.3f} at {name} (err {err:.2e}, bar {b:.2e}, c {chain})", end="")
-    print(f"\nPARITY-SUMMARY head_direct total {time.time() - t0:.1f} s")
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(case, kind):
-    return R.Problem(case, kind)
-
-
-class In:
-    """a float operand between NaN guards, on the device"""
-    def __init__(self, t):
-        self.g = G.Guarded(1, 1, t.numel(), t.numel(), fill="nan", data=t.float().reshape(-1))
-        self.dev = _up(self.g)
-        self.ptr = _at(self.dev, self.g)
-
-
-class Out:
-    """an output (or the workspace) between sentinel guards; data: what it holds before the launch (accumulate)"""
-    def __init__(self, n, data=None):
-        self.g = G.Guarded(1, 1, n, n, fill="sentinel", data=None if data is None else data.float().reshape(-1))
-        self.dev = _up(self.g)
-        self.ptr = _at(self.dev, self.g)
-
-    def flat(self):
-        return self.dev.cpu()
-
-    def live(self):
-        flat = self.flat()
-        assert self.g.pads_untouched(flat), "a word outside the live output changed"
-        return self.g.live(flat).reshape(-1)
-
-    def untouched(self):
-        return self.g.all_untouched(self.flat())
-
-
-def _ints(a):
-    return None if a is None else torch.as_tensor(np.asarray(a), dtype=torch.int32).contiguous().to(_dev())
+SUM = P.Summary("head_direct", GROUPS)
+_summary = SUM.fixture()
+_problem = functools.lru_cache(maxsize=None)(R.Problem)          # (case, kind) -> operands and restatement, built once
 
 
 def _p(t):
@@ -84,11 +36,9 @@ def _p(t):
 
 
 def _check(group, name, out, ref, S, chain, legacy, lattice):
-    _judge(group, name, out.g, out.flat(), ref.reshape(1, 1, -1), S.reshape(1, 1, -1), chain, legacy)
+    SUM.judge(group, name, out.g, out.flat(), ref.reshape(1, 1, -1), S.reshape(1, 1, -1), chain, legacy)
     if lattice:
-        got = out.live().double()
-        bad = (got != ref.reshape(-1)).nonzero()
-        assert bad.numel() == 0, f"{group} {name}: {bad.shape[0]} words differ from the exact result, first at {bad[0].tolist()}"
+        SUM.exact(group, name, out.live(), ref)
 
 
 def _sync(rc, what):
@@ -100,19 +50,19 @@ def _sync(rc, what):
 # launches
 # ====================================================================================================================
 def _drt_fwd(p, h, W11, cbsum):
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
-    out = Out(c.nsel * c.B * p.geo.S)
-    a, w, cs, hm = In(h), In(W11), In(cbsum), _ints(p.hmap)
+    out = P.output(c.nsel * c.B * p.geo.S)
+    a, w, cs, hm = P.operand(h), P.operand(W11), P.operand(cbsum), P.ints(p.hmap)
     _sync(L.sp_drt_direct_fwd(a.ptr, w.ptr, cs.ptr, _p(hm), c.B, c.Hm, c.Wm, c.C, c.nsel, out.ptr, hip.stream()), "sp_drt_direct_fwd")
     return out
 
 
 def _bwd_data(p, dD, W11, accumulate, dh0, live=None, row_last=None, row_step=0, rowB=0):
-    hip, L = _abi()
+    hip, L = P.abi()
     c, B = p.c, p.c.B
-    out = Out(B * p.geo.P * c.C, dh0)
-    g, w, hm, lv, rl = In(dD), In(W11), _ints(p.hmap), _ints(live), _ints(row_last)
+    out = P.output(B * p.geo.P * c.C, dh0)
+    g, w, hm, lv, rl = P.operand(dD), P.operand(W11), P.ints(p.hmap), P.ints(live), P.ints(row_last)
     _sync(L.sp_drt_direct_bwd_data(g.ptr, w.ptr, _p(hm), B, c.Hm, c.Wm, c.C, c.nsel, accumulate, out.ptr, _p(lv), _p(rl), row_step, rowB, hip.stream()),
           "sp_drt_direct_bwd_data")
     return out
@@ -120,23 +70,23 @@ def _bwd_data(p, dD, W11, accumulate, dh0, live=None, row_last=None, row_step=0,
 
 def _bwd_weight(p, dD, h, live=None, row_last=None, row_step=0, rowB=0):
     """-> (dW11, dcbsum, workspace)"""
-    hip, L = _abi()
+    hip, L = P.abi()
     c, B = p.c, p.c.B
     nbytes = L.sp_drt_direct_bwd_weight_workspace(B, c.Hm, c.Wm, c.C, c.nsel)
     assert nbytes == B * c.nsel * p.geo.ncls * 121 * c.C * 4, nbytes
-    ws, dW, dcs = Out(nbytes // 4), Out(c.nheads * p.geo.ncls * 121 * c.C), Out(c.nheads * p.geo.ncls)
-    g, a, hm, lv, rl = In(dD), In(h), _ints(p.hmap), _ints(live), _ints(row_last)
+    ws, dW, dcs = P.output(nbytes // 4), P.output(c.nheads * p.geo.ncls * 121 * c.C), P.output(c.nheads * p.geo.ncls)
+    g, a, hm, lv, rl = P.operand(dD), P.operand(h), P.ints(p.hmap), P.ints(live), P.ints(row_last)
     _sync(L.sp_drt_direct_bwd_weight(g.ptr, a.ptr, _p(hm), B, c.Hm, c.Wm, c.C, c.nsel, c.nheads, ws.ptr, dW.ptr, dcs.ptr, _p(lv), _p(rl), row_step, rowB,
                                      hip.stream()), "sp_drt_direct_bwd_weight")
-    assert ws.g.pads_untouched(ws.flat()), "a word around the slab workspace changed"
+    assert ws.pads_untouched(), "a word around the slab workspace changed"
     return dW, dcs, ws
 
 
 def _gather_bwd(p, dZ2, nsrc, ldt, row_last=None, row_step=0):
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
-    out = Out(c.B * p.geo.P * ldt)
-    g, hm, rl = In(dZ2), _ints(p.hmap), _ints(row_last)
+    out = P.output(c.B * p.geo.P * ldt)
+    g, hm, rl = P.operand(dZ2), P.ints(p.hmap), P.ints(row_last)
     _sync(L.sp_sal_gather_bwd(g.ptr, c.B, c.Hm, c.Wm, ldt, c.nsel, nsrc, _p(hm), out.ptr, _p(rl), row_step, hip.stream()), "sp_sal_gather_bwd")
     return out
 
@@ -157,15 +107,15 @@ def _cases(f):
 
 @_cases
 def test_compose11(p, c, geo, lat, name):
-    hip, L = _abi()
+    hip, L = P.abi()
     assert L.sp_head_num_classes(c.Hm, c.Wm) == geo.ncls
     (W, cs), (SW, Scs) = R.compose11_fwd(p.G, p.cb, geo)
-    a, b, oW, ocs = In(p.G), In(p.cb), Out(W.numel()), Out(cs.numel())
+    a, b, oW, ocs = P.operand(p.G), P.operand(p.cb), P.output(W.numel()), P.output(cs.numel())
     _sync(L.sp_head_compose11_fwd(a.ptr, b.ptr, c.nheads, c.HC, c.C, c.Hm, c.Wm, oW.ptr, ocs.ptr, hip.stream()), "sp_head_compose11_fwd")
     _check("head_compose11_fwd", name + "-W11", oW, W, SW, R.chain_compose11_fwd(), FWD, lat)
     _check("head_compose11_fwd", name + "-cbsum", ocs, cs, Scs, R.chain_compose11_fwd(), FWD, lat)
     (dG, dcb), (SG, Scb) = R.compose11_bwd(p.dW11, p.dcbsum, geo, c.HC)
-    a, b, oG, ocb = In(p.dW11), In(p.dcbsum), Out(dG.numel()), Out(dcb.numel())
+    a, b, oG, ocb = P.operand(p.dW11), P.operand(p.dcbsum), P.output(dG.numel()), P.output(dcb.numel())
     _sync(L.sp_head_compose11_bwd(a.ptr, b.ptr, c.nheads, c.HC, c.C, c.Hm, c.Wm, oG.ptr, ocb.ptr, hip.stream()), "sp_head_compose11_bwd")
     _check("head_compose11_bwd", name + "-dG", oG, dG, SG, R.chain_compose11_bwd(geo.ncls), GRAD, lat)
     _check("head_compose11_dcb", name, ocb, dcb, Scb, R.chain_dcbsum(), GRAD, lat)          # an fp64 sum rounded once
@@ -174,15 +124,15 @@ def test_compose11(p, c, geo, lat, name):
 @_cases
 def test_sal_gather(p, c, geo, lat, name):
     """ldt = 50 nsrc and 50 nsrc + 14: NaN in the pad columns of T (not read), zeros required in those of dT"""
-    hip, L = _abi()
-    nsrc, hm = c.nheads, _ints(p.hmap)
+    hip, L = P.abi()
+    nsrc, hm = c.nheads, P.ints(p.hmap)
     dZ2 = p.dZ2()
     for ldt in (50 * nsrc, 50 * nsrc + 14):
         T = p.T(nsrc, ldt)
         Z2, S = R.sal_gather_fwd(T, p.hmap, c.Hm, c.Wm, c.nsel)
         Tn = T.clone()
         Tn[:, :, 50 * nsrc:] = float("nan")
-        a, oZ = In(Tn), Out(Z2.numel())
+        a, oZ = P.operand(Tn), P.output(Z2.numel())
         _sync(L.sp_sal_gather_fwd(a.ptr, c.B, c.Hm, c.Wm, ldt, c.nsel, _p(hm), oZ.ptr, hip.stream()), "sp_sal_gather_fwd")
         _check("head_sal_gather_fwd", f"{name}-ldt{ldt}", oZ, Z2, S, R.chain_sal_gather_fwd(), FWD, lat)
         dT, S = R.sal_gather_bwd(dZ2, p.hmap, c.Hm, c.Wm, c.nsel, nsrc, ldt)
@@ -196,7 +146,7 @@ def test_drt_fwd(p, c, geo, lat, name):
     D, S = R.drt_fwd(p.h, p.W11, p.cbsum, p.hmap, geo, c.nsel)
     oD = _drt_fwd(p, p.h, p.W11, p.cbsum)
     _check("head_drt_fwd", name, oD, D, S, R.chain_drt_fwd(geo, c.C), FWD, lat)
-    assert _same_bits(oD.flat(), _drt_fwd(p, p.h, p.W11, p.cbsum).flat()), f"{name}: two sp_drt_direct_fwd launches differ"
+    assert P.same_bits(oD.flat(), _drt_fwd(p, p.h, p.W11, p.cbsum).flat()), f"{name}: two sp_drt_direct_fwd launches differ"
 
 
 @_cases
@@ -215,7 +165,7 @@ def test_drt_bwd_weight(p, c, geo, lat, name):
     _check("head_drt_bwd_weight", name, oW, dW, SW, R.chain_drt_bwd_weight(geo, p.hmap, c.nheads), GRAD, lat)
     _check("head_drt_dcbsum", name, ocs, dcs, Scs, R.chain_dcbsum(), GRAD, lat)
     oW2, ocs2, _ = _bwd_weight(p, p.dD, p.h)
-    assert _same_bits(oW.flat(), oW2.flat()) and _same_bits(ocs.flat(), ocs2.flat()), f"{name}: two sp_drt_direct_bwd_weight launches differ"
+    assert P.same_bits(oW.flat(), oW2.flat()) and P.same_bits(ocs.flat(), ocs2.flat()), f"{name}: two sp_drt_direct_bwd_weight launches differ"
     if c.hmap == "unused":
         k = c.nheads - 1
         assert not oW.live().reshape(c.nheads, -1)[k].any() and not ocs.live().reshape(c.nheads, -1)[k].any(), f"{name}: a head no row selects"
@@ -252,19 +202,19 @@ def test_zero_gradient_contract(name, case, rowB, row_last, row_step, off):
         plain = _bwd_data(p, dD, p.W11, acc, dh0).live()
         out = _bwd_data(p, dD, p.W11, acc, dh0, live, row_last, row_step, rowB)
         flagged = out.live()
-        assert torch.isfinite(flagged).all() and _same_bits(flagged, plain), f"{name} accumulate {acc}: flags changed dh"
+        assert torch.isfinite(flagged).all() and P.same_bits(flagged, plain), f"{name} accumulate {acc}: flags changed dh"
         rows = flagged.reshape(c.B, -1)[dead_rows]
-        assert _same_bits(rows, p.dh0.reshape(c.B, -1)[dead_rows]) if acc else not rows.any(), f"{name} accumulate {acc}: dh of dead rows"
+        assert P.same_bits(rows, p.dh0.reshape(c.B, -1)[dead_rows]) if acc else not rows.any(), f"{name} accumulate {acc}: dh of dead rows"
         ref, S = R.drt_bwd_data(dD, p.W11, p.hmap, geo, c.nsel, dh0=dh0, on=on)
         _check("head_drt_bwd_data", f"{name}-flags-accumulate{acc}", out, ref, S, R.chain_drt_bwd_data(c.nsel, acc), GRAD, False)
     pW, pcs, _ = _bwd_weight(p, dD, p.h)
     fW, fcs, ws = _bwd_weight(p, dD, h_nan, live, row_last, row_step, rowB)
     assert torch.isfinite(fW.live()).all(), f"{name}: h of a dead row was read"
-    assert _same_bits(fW.live(), pW.live()) and _same_bits(fcs.live(), pcs.live()), f"{name}: flags changed dW11 / dcbsum"
+    assert P.same_bits(fW.live(), pW.live()) and P.same_bits(fcs.live(), pcs.live()), f"{name}: flags changed dW11 / dcbsum"
     slabs = ws.live().view(torch.int32).reshape(c.B, c.nsel, -1)
     for b in range(c.B):
         for i in range(c.nsel):
-            assert bool((slabs[b, i] != G.SENTINEL).all()) == bool(on[i, b]), f"{name}: slab of row {b} slot {i}"
+            assert bool((slabs[b, i] != P.SENTINEL).all()) == bool(on[i, b]), f"{name}: slab of row {b} slot {i}"
 
 
 def test_sal_gather_bwd_does_not_read_dead_samples():
@@ -277,11 +227,11 @@ def test_sal_gather_bwd_does_not_read_dead_samples():
     dZn[dead] = float("nan")
     flagged = _gather_bwd(p, dZn, 2, ldt, row_last, 3).live().reshape(c.B, -1)
     assert torch.isfinite(flagged).all() and not flagged[dead].any()
-    assert _same_bits(flagged[[0, 2, 3]], plain[[0, 2, 3]])
+    assert P.same_bits(flagged[[0, 2, 3]], plain[[0, 2, 3]])
 
 
 def test_num_classes_on_every_side():
-    _, L = _abi()
+    _, L = P.abi()
     for side in range(1, 171):
         for Hm, Wm in ((side, 13), (13, side), (side, side)):
             assert L.sp_head_num_classes(Hm, Wm) == R.num_classes(Hm, Wm), (Hm, Wm)
@@ -324,12 +274,12 @@ for _fn, (_args, _ins, _outs, _opt) in _ENTRIES.items():
 
 @pytest.mark.parametrize("fn,row,over,null,rc", REFUSALS, ids=[f"{r[0]}-{r[1]}" for r in REFUSALS])
 def test_head_refusals(fn, row, over, null, rc):
-    hip, L = _abi()
+    hip, L = P.abi()
     args, ins, outs, opt = (s.split() for s in _ENTRIES[fn])
     v = {**_DEF, **over}
     n = 1 << 15                                  # larger than every buffer of the default shape (and of the 4-row one)
-    zeros, izeros = torch.zeros(n, device=_dev()), torch.zeros(n, dtype=torch.int32, device=_dev())
-    bufs = {o: Out(n) for o in outs}
+    zeros, izeros = torch.zeros(n, device=P.dev()), torch.zeros(n, dtype=torch.int32, device=P.dev())
+    bufs = {o: P.output(n) for o in outs}
     call = []
     for a in args:
         if a == null:

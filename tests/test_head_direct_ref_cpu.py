@@ -8,7 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
-import gemm_ref as G
+import parity as P
 import head_direct_ref as R
 
 CASES = R.cases()
@@ -178,7 +178,7 @@ def _entries(p):
 def test_bars_have_teeth(case):
     """one term left out -- the last in-map tap of a window, one site, one (b, i) slab, one class, one slot -- moves some element by more than its bar"""
     for name, ref, S, less, chain, _ in _entries(problem(case)):
-        assert ((ref - less).abs() > G.bar(S, chain)).any(), name
+        assert ((ref - less).abs() > P.bar(S, chain)).any(), name
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: c.name)

@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as TF
 
 import lstm_cell_ref as R
+from parity import stress_bar
 
 GATES = ("input", "forget", "output")
 STREAMS = ["_pos", "_neg"]
@@ -122,13 +123,13 @@ def test_stress_inputs_hold_every_magnitude_and_keep_the_bar_below_1e_4(rows, C)
     worst = 0.0
     for k, base in (("gates", 3e-6), ("c", 3e-6), ("h", 3e-6), ("dpre", 1e-5), ("dc_prev", 1e-5)):
         assert bool(torch.isfinite(r32[k]).all()) and bool(torch.isfinite(r64[k]).all()), k
-        worst = max(worst, R.stress_bar(base, r32[k], r64[k]))
+        worst = max(worst, stress_bar(base, r32[k], r64[k]))
     # the backward as the kernel runs it: from the saved fp32 gates
     for dt in (torch.float32, torch.float64):
         assert all(bool(torch.isfinite(t).all()) for t in R.cell_backward_from_saved(r32["gates"], cp, r32["c"], dh, dc, dtype=dt))
     b32 = R.cell_backward_from_saved(r32["gates"], cp, r32["c"], dh, dc, dtype=torch.float32)
     b64 = R.cell_backward_from_saved(r32["gates"], cp, r32["c"], dh, dc)
-    worst = max(worst, R.stress_bar(1e-5, b32[0], b64[0]), R.stress_bar(1e-5, b32[1], b64[1]))
+    worst = max(worst, stress_bar(1e-5, b32[0], b64[0]), stress_bar(1e-5, b32[1], b64[1]))
     print(f"stress bar rows={rows} C={C}: worst {worst:.2e}")
     assert worst < 1e-4, worst
 

@@ -4,7 +4,7 @@ tests/lstm_cell_ref.py (anchored to the oracle by tests/test_lstm_cell_cpu.py), 
 grid-stride loop behind 2048 blocks, 64-pixel tiles and 256-pixel blocks / chunks less one / exactly / plus one, every tap count of the LDS passes,
 absent optional inputs, dead samples (row_last) whose inputs hold NaN, saturated gates, and the 2xfp16 operand of the gate gradient with its bound.
 
-Bars: those tests/test_ops_gpu.py::test_lstm_cell_and_gate_conv holds these ops to, same metric (_close): 3e-6 for gates / c / h, 1e-5 for every
+Bars: those tests/test_ops_gpu.py::test_lstm_cell_and_gate_conv holds these ops to, same metric (parity.close): 3e-6 for gates / c / h, 1e-5 for every
 gradient; saturation cases max(that bar, 10 x max|ref32 - ref64|) of the restatement (tests/test_lstm_cell_cpu.py keeps that below 1e-4).  The
 planes bar (2^-21 x bound), the exact max|.| words and the bit-equalities are conditions.  Every test prints its worst err / bar
 (profiles/lstm_cell_parity.md)."""
@@ -17,22 +17,13 @@ import torch
 import torch.nn.functional as TF
 
 import lstm_cell_ref as R
-from test_decoder_ops_gpu import _Worst
-from test_ops_gpu import _close, _decode_split, _dev, _rand  # noqa: F401  (_close: the metric _Worst applies)
+from parity import NAN, Worst, abi as _abi, decode_split as _decode_split, dev as _dev, rand as _rand, stress_bar
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-
 
 # ====================================================================================================================
 # the ABI, with every output poisoned and every max|.| word zeroed by the caller
 # ====================================================================================================================
-def _abi():
-    from scanpaths_amd import hip
-    return hip, hip.lib()
-
-
 def _d(t):
     return None if t is None else t.contiguous().to(_dev())
 
@@ -146,7 +137,7 @@ def _plain_backward_ref(rows, C):
 @pytest.mark.parametrize("rows,C", PLAIN_SHAPES)
 def test_pointwise_forward_at_edge_shapes(rows, C):
     """lstm_fwd_kernel: gates, c', h' against fp64; hg / c_prev present or NULL in all four combinations at the two small shapes"""
-    w = _Worst(f"lstm_pointwise_fwd rows={rows} C={C}")
+    w = Worst(f"lstm_pointwise_fwd rows={rows} C={C}")
     combos = list(itertools.product((True, False), repeat=2)) if (rows, C) in SMALL else [(True, True)]
     for has_hg, has_cp in combos:
         (gates, c, h), ref = _plain_state(rows, C, has_hg, has_cp)
@@ -162,7 +153,7 @@ def test_pointwise_backward_at_edge_shapes(rows, C):
     """lstm_bwd_kernel without planes: dpre and dc_prev against fp64 autograd of the restatement fed the kernel's own saved gates / c_out; the two
     max|.| words (zeroed here) equal the maxima of the kernel's own outputs exactly.  At (3, 12) every combination of dh / dc / c_prev present
     or NULL; both cotangents NULL give exact zeros."""
-    w = _Worst(f"lstm_pointwise_bwd rows={rows} C={C}")
+    w = Worst(f"lstm_pointwise_bwd rows={rows} C={C}")
     t = _plain_inputs(rows, C)
     combos = list(itertools.product((True, False), repeat=3)) if (rows, C) == (3, 12) else [(True, True, True)]
     for has_dh, has_dc, has_cp in combos:
@@ -213,7 +204,7 @@ def _rank1_compare(w, xg, hg, cp, sp, wc, tag=""):
 def test_rank1_forward_at_tile_and_block_boundaries(P, C):
     """lstm_rank1_fwd_kernel at B = 3, KP = 20: one pixel, a 64-pixel tile and a 256-pixel block less one / exactly / plus one (the tap staging
     of a partial tile), one and two 64-channel blocks; the max|h| word equals the maximum of the kernel's own h_out"""
-    w = _Worst(f"lstm_rank1_fwd B=3 P={P} C={C} KP=20")
+    w = Worst(f"lstm_rank1_fwd B=3 P={P} C={C} KP=20")
     _rank1_compare(w, *_rank1_inputs(3, P, C, 20))
     w.report()
 
@@ -223,7 +214,7 @@ def test_rank1_forward_at_every_tap_count(KP):
     """(B, P, C) = (1, 65, 64): one tap, one stream, the model's 12, and the documented limit KP = 64 -- 64 x 256 x 4 = 65 536 B of dynamic LDS plus
     16 B static, inside the 160 KiB a single workgroup may declare on gfx950: the launch is legal and the limit of the header stands.  Above it
     the entry point refuses (SP_EINVAL) before any launch."""
-    w = _Worst(f"lstm_rank1_fwd B=1 P=65 C=64 KP={KP}")
+    w = Worst(f"lstm_rank1_fwd B=1 P=65 C=64 KP={KP}")
     ins = _rank1_inputs(1, 65, 64, KP, seed=30)
     _rank1_compare(w, *ins)
     if KP == 64:
@@ -234,7 +225,7 @@ def test_rank1_forward_at_every_tap_count(KP):
 
 
 def test_rank1_forward_without_hg_and_previous_state():
-    w = _Worst("lstm_rank1_fwd B=3 P=65 C=128 hg / c_prev NULL")
+    w = Worst("lstm_rank1_fwd B=3 P=65 C=128 hg / c_prev NULL")
     xg, hg, cp, sp, wc = _rank1_inputs(3, 65, 128, 20, seed=40)
     for has_hg, has_cp in ((False, False), (True, False), (False, True)):
         _rank1_compare(w, xg, hg if has_hg else None, cp if has_cp else None, sp, wc, f" (hg={has_hg} c_prev={has_cp})")
@@ -254,7 +245,7 @@ DWC_CASES = ([(2, P, 192, 256, 20) for P in (1, 3, 15, 16, 17, 255, 256, 257, 51
 def test_rank1_dwc_at_every_loop_boundary(B, P, N3, ld, KP):
     """rank1_dwc_kernel + its fixed-order reduce: dwc[b] = dpre[b][:, :N3]^T x spcol[b] against fp64 bmm.  Columns [N3, ld) of dpre hold NaN and
     the workspace and the result start as NaN: the result must be finite.  Two runs are bit-identical."""
-    w = _Worst(f"rank1_dwc B={B} P={P} N3={N3} ld={ld} KP={KP}")
+    w = Worst(f"rank1_dwc B={B} P={P} N3={N3} ld={ld} KP={KP}")
     dpre, sp = _rand(B, P, ld, seed=50), _rand(B, P, KP, seed=51)
     dpre[..., N3:] = NAN
     out = _dwc(dpre, sp, N3)
@@ -291,7 +282,7 @@ def test_pointwise_backward_skips_dead_samples(B, P, C, last):
     """lstm_bwd_kernel's row_last branch at row_step = 2 ((5, 3, 4): one wave spans all five samples): samples with last < 2 (and last = -1) get
     exact zeros although all five of their inputs hold NaN; the live samples are bit-equal to the dense launch on zero-filled inputs, the max|.|
     words equal the maxima over the live rows, and dpre of the dense launch matches fp64.  rows % rows_per_sample != 0 is SP_EINVAL."""
-    w = _Worst(f"lstm_pointwise_bwd row_last B={B} P={P} C={C}")
+    w = Worst(f"lstm_pointwise_bwd row_last B={B} P={P} C={C}")
     step = 2
     state = _saved_state(B, P, C, seed=60)
     lastd = torch.tensor(last, dtype=torch.int32, device=_dev())
@@ -341,7 +332,7 @@ def test_backward_planes_decode_to_the_fp32_gate_gradient(rows, C):
     """lstm_bwd_kernel with planes: the bound covers max|dpre| of the fp32 output, the scale is the power of two that puts it into [8192, 16384),
     every half is finite, the planes decode to dpre within 2^-21 x bound and the 32 trailing halves (NaN before) are zero -- with max|dh| /
     max|dc| given exactly and as 2x over-estimates, and (small shapes) with dh and its word NULL.  dpre itself against fp64."""
-    w = _Worst(f"lstm_pointwise_bwd planes rows={rows} C={C}")
+    w = Worst(f"lstm_pointwise_bwd planes rows={rows} C={C}")
     t = _plain_inputs(rows, C)
     (gates, c, _), _ = _plain_state(rows, C, True, True)
     dh, dc, cp = _d(t["dh"]), _d(t["dc"]), _d(t["cp"])
@@ -373,7 +364,7 @@ def test_backward_bound_is_attained_and_still_holds(c_bound, cprev_bound):
     t + 1 after the first and the last of 16 steps.  max|dpre| of the kernel reaches the documented value and the reported bound still covers
     it: a bound without its margin, or half of it, fails here."""
     C, rows = 256, 8
-    w = _Worst(f"lstm_pointwise_bwd bound attained c_bound={c_bound:g} cprev_bound={cprev_bound:g}")
+    w = Worst(f"lstm_pointwise_bwd bound attained c_bound={c_bound:g} cprev_bound={cprev_bound:g}")
     worst, runs = (0.0, ""), 0
     for a_dh, a_dc in ((1.0, 1.0), (1.5, 2.0 ** -7), (0.0, 2.0)):
         gates, cp, c, dh, dc = (_d(t) for t in R.bound_attained_inputs(C, c_bound, cprev_bound, a_dh, a_dc))
@@ -433,7 +424,7 @@ def test_saturated_gates_stay_finite_and_within_the_stress_bar(kind, rows, C):
     pointwise forward, the rank-1 forward ((B, P) = (3, 65)) and the backward from the kernel's saved gates: every output finite, parity by
     max(bar, 10 max|ref32 - ref64|).  Records (no assertion) the worst relative error of the stored g gate for 0 < |pre| <= 1e-3, where the
     1 - 2 rcp(1 + exp2(.)) form of sp_tanh cancels."""
-    w = _Worst(f"saturation {kind} rows={rows} C={C}")
+    w = Worst(f"saturation {kind} rows={rows} C={C}")
     xg, cp = R.stress_inputs(rows, C, seed=rows)
     dh, dc = R.randn(rows, C, seed=7), R.randn(rows, C, seed=8)
     sp = wc = None
@@ -448,14 +439,14 @@ def test_saturated_gates_stay_finite_and_within_the_stress_bar(kind, rows, C):
     r64, r32 = R.cell(xg, None, cp, sp, wc), R.cell(xg, None, cp, sp, wc, dtype=torch.float32)
     for got, k in ((gates, "gates"), (c, "c"), (h, "h")):
         assert bool(torch.isfinite(got).all()), k
-        w.close(got, r64[k], R.stress_bar(3e-6, r32[k], r64[k]), k)
+        w.close(got, r64[k], stress_bar(3e-6, r32[k], r64[k]), k)
     g2, c2, cp2 = gates.view(rows, 4 * C), c.view(rows, C), cp.reshape(rows, C)
     res = _bwd(_d(dh), _d(dc), g2, _d(cp2), c2)
     b64 = R.cell_backward_from_saved(g2.cpu(), cp2, c2.cpu(), dh, dc)
     b32 = R.cell_backward_from_saved(g2.cpu(), cp2, c2.cpu(), dh, dc, dtype=torch.float32)
     for got, a, b, k in ((res["dpre"], b32[0], b64[0], "dpre"), (res["dcp"], b32[1], b64[1], "dc_prev")):
         assert bool(torch.isfinite(got).all()), k
-        w.close(got, b, R.stress_bar(1e-5, a, b), k)
+        w.close(got, b, stress_bar(1e-5, a, b), k)
     assert res["dpre_amax"] == _amax(res["dpre"]) and res["dcp_amax"] == _amax(res["dcp"])
     rel, n, at0 = _tanh_small_argument(xg, gates, C)
     print(f"TANH {kind} rows={rows} C={C}: worst relative error of g = sp_tanh(pre) over 0 < |pre| <= 1e-3: {rel:.3e} ({n} entries), |g| at pre = 0: "
@@ -482,7 +473,7 @@ def test_fused_cell_epilogue_at_one_tile_per_sample_and_extreme_aspect_ratios(B,
         pytest.skip("2xfp16 back-end not active")
     C = 32
     assert 9 * S <= KP and (Hm * Wm) % 256 == 0
-    w = _Worst(f"gateconv_lstm B={B} {Hm}x{Wm} C={C} KP={KP} S={S} planes={planes}")
+    w = Worst(f"gateconv_lstm B={B} {Hm}x{Wm} C={C} KP={KP} S={S} planes={planes}")
     h, c = _rand(B, C, Hm, Wm, seed=24), _rand(B, C, Hm, Wm, seed=25)
     xg = _rand(B, 4 * C, Hm, Wm, seed=26)
     wh = _rand(4 * C, C, 3, 3, seed=27, scale=0.1)

@@ -22,18 +22,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import case_inputs, load_golden, max_err, oracle_state
+from helpers import DEV, case_inputs, load_golden, max_err, oracle_state
+from helpers import assert_same_grads as _assert_same_grads, build_model as _build, call_model as _call, param_grads as _grads, \
+    sparsity_case as _sparsity_case
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-
-
-def _build(meta, Hm=30, Wm=40):
-    from scanpaths_amd.models.scanpath_model import ScanpathModel
-    from scanpaths_amd.procedural import fill_module
-    m = ScanpathModel(meta["task"], convLSTM_length=meta["T"], map_width=Wm, map_height=Hm, arch=meta["arch"])
-    fill_module(m, seed=meta["weight_seed"], family=meta.get("weight_family", "default"))
-    return m.to(DEV)
 
 
 # Tests whose ground the bench-path and full-batch tests cover with a stricter setup (same 320x512 kernel path, T = 16, tame family,
@@ -188,15 +181,6 @@ def _record_grads(rows):
         json.dump(sorted(have.values(), key=keyf), open(path, "w"), indent=0)
     except OSError:
         pass
-
-
-def _call(model, meta, b):
-    img = b["images"].to(DEV)
-    if meta["task"] == "AiR":
-        return model(img, b["attention_maps"].to(DEV), b["performances"].to(DEV) if model.training else None)
-    if meta["task"] == "OSIE":
-        return model(img)
-    return model(img, b["attention_maps"].to(DEV), b["tasks"].to(DEV))
 
 
 CHAOS_CUTOFF = 1e-3     # chaotic cases are compared while the reference's own fp32 drift is below 0.1 % of an output's scale
@@ -691,18 +675,6 @@ def test_bench_path_at_320x512_T16_matches_oracle_on_every_step(monkeypatch, req
 
 
 
-def _sparsity_case(task, T=8, NB=5, seed=4, lengths=(1, 4, 8, 2, 0)):
-    from scanpaths_amd.synth import make_batch
-    meta = dict(task=task, arch="resnet18", T=T, weight_seed=seed, weight_family="tame")
-    b = {k: v.to(DEV) for k, v in make_batch(task, NB, 320, 512, T, seed=seed).items()}
-    am, dm = torch.zeros(NB, T, device=DEV), torch.zeros(NB, T, device=DEV)
-    for i, L in enumerate(lengths):                                # last loss step per sample: L - 1 (none for L = 0)
-        am[i, :L] = 1
-        dm[i, :max(L - 1, 0)] = 1
-    b["action_masks"], b["duration_masks"] = am, dm
-    return meta, b
-
-
 def _reference_two_call_loss(pred, b):
     """the reference's own sequence, AiR/train.py:192-197: two separate loss calls, summed by autograd"""
     from scanpaths_amd.models.loss import CrossEntropyLoss, MLPLogNormalDistribution
@@ -710,16 +682,6 @@ def _reference_two_call_loss(pred, b):
     la = CrossEntropyLoss(z, b["scanpaths"], b["action_masks"])
     ld = MLPLogNormalDistribution(pred["log_normal_mu"], pred["log_normal_sigma2"], b["durations"], b["duration_masks"])
     return la + 1.0 * ld
-
-
-def _grads(model):
-    return {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
-
-
-def _assert_same_grads(a, b_):
-    assert a.keys() == b_.keys()
-    diff = [k for k in a if not torch.equal(a[k], b_[k])]
-    assert not diff, diff[:8]
 
 
 @pytest.mark.parametrize("loss_form", ["fused", "two_calls"])

@@ -7,27 +7,10 @@ import pytest
 import torch
 import torch.nn.functional as TF
 
+from parity import close as _close, decode_split as _decode_split, dev as _dev, rand as _rand
 from scanpaths_amd.notes import note, notes
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = np.random.Generator(np.random.PCG64(seed + sum(shape)))
-    return torch.from_numpy(g.standard_normal(shape).astype(np.float32) * scale)
-
-
-def _close(a, b, tol, what=""):
-    a = a.detach().cpu().double()
-    b = b.detach().cpu().double()
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    scale = max(1.0, b.abs().max().item())
-    err = (a - b).abs().max().item()
-    assert err <= tol * scale, f"{what}: max err {err:.3e} (scale {scale:.3g}, tol {tol:g})"
 
 
 CONV_CASES = [
@@ -904,15 +887,6 @@ def test_fused_amax_hints_equal_the_separate_pass():
     h, c = F.lstm_cell_rank1(xg, None, None, spcol, wc)
     a = F.split_op(h); b = F.split_op(h.detach().clone())
     assert notes(h).amax is not None and torch.equal(a.buf, b.buf)
-
-
-def _decode_split(op, shape):
-    """fp32 value of a 2xfp16 split operand [rows][K/16][2][16]"""
-    n = 1
-    for d in shape:
-        n *= d
-    planes = op.buf[:2 * n].view(-1, 2, 16).float()
-    return ((planes[:, 0] + planes[:, 1]) / float(op.scale[0])).reshape(shape)
 
 
 @pytest.mark.parametrize("relu", [True, False])

@@ -10,77 +10,39 @@ max-norm bar of tests/test_ops_gpu.py; lattice data equals R_planes exactly (tor
 workspace untouched and agrees with sp_rank1_grads_applies.  Each comparison prints a PARITY line, the module a summary per group
 (profiles/rank1_grads_parity.md)."""
 import functools
-import time
 
 import numpy as np
 import pytest
 import torch
 
-import gemm_ref as G
+import parity as P
 import rank1_grads_ref as R
-import test_gemm_fp32_gpu as FP32
-from test_conv_f16x2_gpu import Raw
-from test_gemm_fp32_gpu import _abi, _at, _same_bits, _up
-from test_ops_gpu import _dev
 
 pytestmark = pytest.mark.gpu
 
-GROUPS = ("rank1_dsp", "rank1_dwc")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _summary():
-    t0 = time.time()
-    yield
-    for group in GROUPS:
-        rows = FP32.SUMMARY.pop(group, None)
-        if rows:
-            q, name, err, b, chain = max(rows)
-            print(f"\nPARITY-SUMMARY {group}: {len(rows)} comparisons, worst err/bar {q:.3f} at {name} (err {err:.2e}, bar {b:.2e}, c {chain})", end="")
-    print(f"\nPARITY-SUMMARY rank1 total {time.time() - t0:.1f} s")
-
-
-@functools.lru_cache(maxsize=None)
-def _problem(case):
-    return R.Problem(case)
-
-
-def _u16(a):
-    return torch.from_numpy(np.ascontiguousarray(a).view(np.int16)).to(_dev())
-
-
-def _f32(a):
-    return torch.from_numpy(np.array(a, dtype=np.float32).reshape(-1)).to(_dev())
+SUM = P.Summary("rank1", ("rank1_dsp", "rank1_dwc"))
+_summary = SUM.fixture()
+_problem = functools.lru_cache(maxsize=None)(R.Problem)          # case -> operands and restatement, built once
 
 
 def _launch(p, planes, flags):
     """one launch on fresh buffers -> (dsp [B, P, KP], dwc [B, N3, KP]) on the host, guards and workspace bounds checked"""
-    hip, L = _abi()
+    hip, L = P.abi()
     c = p.c
-    Y, W, sy, sw = _u16(planes), _u16(p.Wp), _f32([p.sy]), _f32(p.sw)
-    taps = G.Guarded(1, 1, p.taps.size, p.taps.size, fill="nan", data=torch.from_numpy(p.taps))
-    dT = _up(taps)
-    dsp, dwc = Raw(4 * c.B * c.P * c.KP), Raw(4 * c.B * c.N3 * c.KP)
+    Y, W, sy, sw = P.u16(planes), P.u16(p.Wp), P.f32([p.sy]), P.f32(p.sw)
+    dT = P.operand(torch.from_numpy(p.taps))
+    dsp, dwc = P.output(c.B * c.P * c.KP), P.output(c.B * c.N3 * c.KP)
     nbytes = L.sp_rank1_grads_workspace(c.B, c.P, c.N3, c.KP)
     assert nbytes == 4 * c.B * p.chunks * (c.N3 * c.KP + 1), nbytes
-    ws = Raw(nbytes)
-    rl = torch.from_numpy(p.row_last).to(_dev()) if flags else None
+    ws = P.raw(nbytes)
+    rl = torch.from_numpy(p.row_last).to(P.dev()) if flags else None
     assert L.sp_rank1_grads_applies(c.B, c.P, c.N3, c.KP, c.ldy) == 1
-    rc = L.sp_rank1_grads_f16x2(Y.data_ptr(), sy.data_ptr(), c.ldy, W.data_ptr(), sw.data_ptr(), _at(dT, taps), c.B, c.P, c.N3, c.KP, dsp.ptr, dwc.ptr,
+    rc = L.sp_rank1_grads_f16x2(Y.data_ptr(), sy.data_ptr(), c.ldy, W.data_ptr(), sw.data_ptr(), dT.ptr, c.B, c.P, c.N3, c.KP, dsp.ptr, dwc.ptr,
                                 ws.ptr, None if rl is None else rl.data_ptr(), p.row_step, hip.stream())
     torch.cuda.synchronize()
     assert rc == 0, (c.name, rc)
-    ws.read()
-    f = lambda raw, *shape: torch.from_numpy(raw.read().view(np.float32).copy()).reshape(*shape)
-    return f(dsp, c.B, c.P, c.KP), f(dwc, c.B, c.N3, c.KP)
-
-
-def _judge_planes(group, name, got, ref, S, chain, true, rep):
-    q, i, err, b = G.worst(got, ref, S, chain)
-    FP32.SUMMARY.setdefault(group, []).append((q, name, err, b, chain))
-    print(f"PARITY {group} {name}: err/bar {q:.3f} (err {err:.2e}, bar {b:.2e}, c {chain}, element {i})")
-    assert q <= 1.0, f"{group} {name}: err {err:.3e} > bar {b:.3e} at element {i} (c = {chain})"
-    assert ((got.double() - true).abs() <= rep + G.bar(S, chain)).all(), f"{group} {name}: outside the representation bound of the true product"
+    ws.live()
+    return dsp.live().reshape(c.B, c.P, c.KP), dwc.live().reshape(c.B, c.N3, c.KP)
 
 
 @pytest.mark.parametrize("case", R.cases(), ids=lambda c: c.name)
@@ -89,7 +51,8 @@ def test_rank1_grads(case):
     dsp, dwc = _launch(p, p.Yp, False)
     for group, got, (ref, S), chain, true, rep in (("rank1_dsp", dsp, p.dsp_planes(), p.chain_dsp, p.dsp_true(), p.dsp_rep()),
                                                    ("rank1_dwc", dwc, p.dwc_planes(), p.chain_dwc, p.dwc_true(), p.dwc_rep())):
-        _judge_planes(group, c.name, got, ref, S, chain, true, rep)
+        SUM.judge_values(group, c.name, got, ref, S, chain)
+        assert ((got.double() - true).abs() <= rep + P.bar(S, chain)).all(), f"{group} {c.name}: outside the representation bound of the true product"
         # the max-norm bar of test_rank1_grads_kernel_gives_both_gradients_of_the_rank1_gate_term, where the group's own operands are Gaussian
         # (the taps enter dwc alone: under every kind but lattice and rows dsp is a product of Gaussian dpre and wc)
         if c.kind == "gauss" or (group == "rank1_dsp" and c.kind not in ("lattice", "rows")):
@@ -98,27 +61,26 @@ def test_rank1_grads(case):
             assert e <= 4e-6, (group, c.name, e)
         if c.kind == "lattice":
             assert max(p.exact_spans()) <= 2.0 ** 24
-            bad = (got.double() != ref).nonzero()
-            assert bad.numel() == 0, f"{group} {c.name}: {bad.shape[0]} words differ from the exact result, first at {bad[0].tolist()}"
+            SUM.exact(group, c.name, got, ref)
         if c.kind == "zero-all" and group == "rank1_dwc":
             assert not got.any()
     d2, w2 = _launch(p, p.Yp, False)
-    assert _same_bits(dsp, d2) and _same_bits(dwc, w2), f"{c.name}: two launches differ"
+    assert P.same_bits(dsp, d2) and P.same_bits(dwc, w2), f"{c.name}: two launches differ"
     if p.dead:
         d3, w3 = _launch(p, p.planes_with_dead_rows_nan(), True)
         live = [b for b in range(c.B) if b not in p.dead]
         assert torch.isfinite(d3).all() and torch.isfinite(w3).all(), f"{c.name}: a dead sample's rows were read"
         assert not d3[p.dead].any() and not w3[p.dead].any(), f"{c.name}: a dead sample's gradients are not zeros"
-        assert _same_bits(d3[live], dsp[live]) and _same_bits(w3[live], dwc[live]), f"{c.name}: live samples differ from the dense launch"
+        assert P.same_bits(d3[live], dsp[live]) and P.same_bits(w3[live], dwc[live]), f"{c.name}: live samples differ from the dense launch"
 
 
 @pytest.mark.parametrize("r", R.refusals(), ids=lambda r: r.name)
 def test_rank1_refusals(r):
-    hip, L = _abi()
+    hip, L = P.abi()
     assert L.sp_rank1_grads_applies(r.B, r.P, r.N3, r.KP, r.ldy) == r.applies, r.name
     n = 1 << 16                                     # every buffer is large enough for the shape a refusal row names (B = 65536 is refused first)
-    Y, W, sy, sw, taps = _u16(np.zeros(2 * n, np.uint16)), _u16(np.zeros(2 * n, np.uint16)), _f32([1.0]), _f32(np.ones(64)), _f32(np.zeros(n))
-    dsp, dwc, ws = Raw(4 * 4096), Raw(4 * 8192), Raw(4 * 16384)
+    Y, W, sy, sw, taps = P.u16(np.zeros(2 * n, np.uint16)), P.u16(np.zeros(2 * n, np.uint16)), P.f32([1.0]), P.f32(np.ones(64)), P.f32(np.zeros(n))
+    dsp, dwc, ws = P.raw(4 * 4096), P.raw(4 * 8192), P.raw(4 * 16384)
     ptrs = {"dpre_planes": Y.data_ptr() + r.offY, "dpre_scale": sy.data_ptr(), "wcT_planes": W.data_ptr() + r.offW, "wcT_row_scale": sw.data_ptr(),
             "spcol": taps.data_ptr(), "dsp": dsp.ptr, "dwc": dwc.ptr, "workspace": ws.ptr + r.offWs}
     if r.null:

@@ -7,7 +7,7 @@ import pytest
 import torch
 
 import f16x2_ref as X
-import gemm_ref as G
+import parity as P
 import rank1_grads_ref as R
 
 CASES = R.cases()
@@ -81,13 +81,13 @@ def test_bars_have_teeth(case):
     p, c = problem(case), case
     ref, S = p.dsp_planes()
     less, _ = p.dsp_planes(drop_group=c.N3 // 16 - 1)
-    assert ((ref - less).abs() > G.bar(S, p.chain_dsp)).any(), "dsp"
+    assert ((ref - less).abs() > P.bar(S, p.chain_dsp)).any(), "dsp"
     if c.kind == "zero-all":                # every tap is zero: dwc is zero whatever is left out (the GPU test asserts the exact zeros)
         assert not p.dwc_planes()[0].any()
         return
     ref, S = p.dwc_planes()
     less, _ = p.dwc_planes(drop_pixel=p.teeth_pixel())
-    assert ((ref - less).abs() > G.bar(S, p.chain_dwc)).any(), "dwc"
+    assert ((ref - less).abs() > P.bar(S, p.chain_dwc)).any(), "dwc"
 
 
 @pytest.mark.parametrize("case", [c for c in CASES if c.kind == "lattice"], ids=lambda c: c.name)

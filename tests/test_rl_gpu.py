@@ -28,7 +28,7 @@ def test_log_action_and_log_duration_match_reference():
 
 
 def test_reward_glue_with_the_hip_scanmatch_matches_reference():
-    from test_scanmatch_oracle import check_rl_glue
+    from helpers import check_rl_glue
     from scanpaths_amd.utils.evaltools.scanmatch import ScanMatch
     cfg = dict(Xres=320, Yres=240, Xbin=16, Ybin=12, Offset=(0, 0), Threshold=3.5)
     check_rl_glue(ScanMatch(TempBin=50, **cfg), ScanMatch(**cfg))               # bit-exact, batched on the device
@@ -72,7 +72,7 @@ def test_rl_step_end_to_end():
     from scanpaths_amd.rl import rl_step
     from scanpaths_amd.synth import make_batch
     from scanpaths_amd.utils.evaltools.scanmatch import ScanMatch
-    from test_scanmatch_oracle import rl_case
+    from helpers import rl_case
     T, N = 4, 2
     m = baseline(convLSTM_length=T)
     fill_module(m, 6)
@@ -101,7 +101,7 @@ def test_rl_step_redraws_samples_with_non_finite_or_overlong_durations():
     from scanpaths_amd.rl import rl_step
     from scanpaths_amd.synth import make_batch
     from scanpaths_amd.utils.evaltools.scanmatch import ScanMatch
-    from test_scanmatch_oracle import rl_case
+    from helpers import rl_case
 
     class Spiky(Sampling):
         """every first draw of a head carries one absurd duration"""
@@ -135,7 +135,7 @@ def test_eval_mode_backward_matches_oracle(request):
     20x the fp32 oracle's own error or 1e-4 of the largest gradient norm (the bars of tests/test_model_gpu.py)."""
     from helpers import RL_EVAL_CASE, rl_eval_objective_weights, start_rl_eval_oracle
     from scanpaths_amd.synth import make_batch
-    from test_model_gpu import _build
+    from helpers import build_model as _build
     c = RL_EVAL_CASE
     T = c["T"]
     meta = dict(task="AiR", arch="resnet50", T=T, weight_seed=c["seed"])

@@ -248,7 +248,8 @@ def _expected_kld_steps(z, boxes, qm, dm):
 def test_attention_losses_on_the_step_maps_reach_the_backward_skip(monkeypatch):
     from scanpaths_amd import functional as F
     from scanpaths_amd.models.loss import CC, KLD_question_aligment, supervised_loss
-    from test_model_gpu import _assert_same_grads, _build, _call, _grads, _sparsity_case
+    from helpers import assert_same_grads as _assert_same_grads, build_model as _build, call_model as _call, param_grads as _grads, \
+        sparsity_case as _sparsity_case
     if F.SPLIT_SCHEME != "f16x2" or not F.USE_BF16X3 or F.THROUGHPUT_MODE:      # the backend test_model_gpu's sparsity tests need
         pytest.skip("2xfp16 back-end not active")
     T, Hm, Wm, M = 8, 40, 64, 3

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+from helpers import check_rl_glue, same
 from oracle import scanmatch_oracle as SO
 
 GOLD = np.load(os.path.join(os.path.dirname(__file__), "golden", "scanmatch.npz"))
@@ -18,12 +19,6 @@ def unrag(name):
 def fixes(name):
     cat, off = GOLD[name], GOLD[name + "_off"]
     return [cat[3 * off[i]:3 * off[i + 1]].reshape(-1, 3) for i in range(len(off) - 1)]
-
-
-def same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    assert np.array_equal(a, b, equal_nan=True), np.nanmax(np.abs(a - b))
 
 
 def test_known_answers_of_the_reference_self_check():
@@ -135,10 +130,6 @@ def test_sed_stde_random_pairs_bit_exact():
 
 
 # ---- RL reward glue: host grouping logic against the reference, with an oracle-backed scorer -----------------
-GOLD3 = np.load(os.path.join(os.path.dirname(__file__), "golden", "rl.npz"))
-_DT = {"names": ("start_x", "start_y", "duration"), "formats": ("f8", "f8", "f8")}
-
-
 class OracleScanMatch:
     """the reference's ScanMatch call surface on top of oracle/scanmatch_oracle.py (tests only)"""
     def __init__(self, tempbin):
@@ -153,39 +144,6 @@ class OracleScanMatch:
         with warnings.catch_warnings():
             warnings.simplefilter("ignore")
             return SO.nw_score(a, b, self.S, 0.0), None, None
-
-
-def rl_case():
-    def unflat(fix, lens):
-        out, o = [], 0
-        for n in lens:
-            fv = np.zeros(int(n), dtype=_DT)
-            fv["start_x"], fv["start_y"], fv["duration"] = fix[o:o + n, 0], fix[o:o + n, 1], fix[o:o + n, 2]
-            out.append(fv)
-            o += int(n)
-        return out
-    flat = unflat(GOLD3["gt_fix"], GOLD3["gt_len"])
-    gt, perf, o = [], [], 0
-    for c in GOLD3["gt_count"]:
-        gt.append(flat[o:o + int(c)])
-        perf.append([bool(v) for v in GOLD3["perf"][o:o + int(c)]])
-        o += int(c)
-    return gt, perf, unflat(GOLD3["pred_fix"], GOLD3["pred_len"])
-
-
-def check_rl_glue(wd, wod):
-    from scanpaths_amd.utils.evaluation import (gtpairs_eval_scanmatch_performance_related,
-                                                pairs_eval_scanmatch_performance_related)
-    gt, perf, pred = rl_case()
-    for given, tag in ((True, "good"), (False, "poor")):
-        s, d, acc = pairs_eval_scanmatch_performance_related(gt, pred, wd, wod, perf, given)
-        same(s, GOLD3[f"pairs_{tag}_same"])
-        same(d, GOLD3[f"pairs_{tag}_diff"])
-        assert int(acc) == int(GOLD3[f"pairs_{tag}_accept"])
-    g, p, dd = gtpairs_eval_scanmatch_performance_related(gt, wd, wod, perf)
-    same(g, GOLD3["gtpairs_good"])
-    same(p, GOLD3["gtpairs_poor"])
-    same(dd, GOLD3["gtpairs_diff"])
 
 
 def test_rl_reward_glue_matches_reference():
