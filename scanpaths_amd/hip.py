@@ -73,6 +73,35 @@ def lib() -> C.CDLL:
     return _lib
 
 
+# The second library (include/scanpaths_amd_stats.h): the descriptive statistics that came after the main library's
+# entry points were pinned.  Bound from its own header by the same rules; SIGNATURES, ABI_VERSION and lib() know nothing of it.
+STATS_HEADER_PATH = os.path.join(os.path.dirname(_abi.HEADER_PATH), "scanpaths_amd_stats.h")
+STATS_LIB_PATH = os.path.join(_HERE, "libscanpaths_amd_stats.so")
+_STATS_DEFINES, _, STATS_SIGNATURES = _abi.load(STATS_HEADER_PATH)
+STATS_ABI_VERSION = _STATS_DEFINES["SP_STATS_ABI_VERSION"]
+
+_stats_lib: Optional[C.CDLL] = None
+
+
+def stats_lib() -> C.CDLL:
+    """Load libscanpaths_amd_stats.so (once), every entry point typed from its header.  A missing file or another ABI version raises."""
+    global _stats_lib
+    if _stats_lib is None:
+        if not os.path.exists(STATS_LIB_PATH):
+            raise RuntimeError(
+                f"{STATS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(make -C scanpaths_amd/csrc; hipcc --offload-arch=gfx950).  scanpaths_amd has no CPU or eager fallback.")
+        cdll = C.CDLL(STATS_LIB_PATH)
+        for name, (restype, argtypes) in STATS_SIGNATURES.items():
+            fn = getattr(cdll, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        if cdll.sp_stats_abi_version() != STATS_ABI_VERSION:
+            raise RuntimeError(f"{STATS_LIB_PATH}: ABI version {cdll.sp_stats_abi_version()}, this binding expects {STATS_ABI_VERSION} "
+                               "(SP_STATS_ABI_VERSION in include/scanpaths_amd_stats.h): rebuild with `make -C scanpaths_amd/csrc`")
+        _stats_lib = cdll
+    return _stats_lib
+
+
 class HipError(RuntimeError):
     pass
 

@@ -190,8 +190,24 @@ def run_turn_statistics_loop(model, loader: Iterable[dict], *, min_length, max_s
                             map_shape=map_shape)
 
 
+@torch.no_grad()
+def run_recurrence_statistics_loop(model, loader: Iterable[dict], *, min_length, max_steps, radius, human_table=None,
+                                   ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None) -> Tuple[dict, List[dict]]:
+    """The model's own recurrence table over a loader, exactly and without sampling
+    (utils.evaluation.recurrence_statistics_model_evaluation): per batch ONE eval-mode forward, ONE sp_stats_recurrence_expectation call
+    and ONE small device->host copy (the batch's table; the distributions stay on the device).  loader, "tasks", "performances" and the
+    keys as in run_saccade_statistics_loop.  min_length is the sampler's; it, max_steps (at most 64) and radius (pixels) have no
+    defaults; human_table (optional, utils.evaluation.recurrence_statistics_human_evaluation's "human_table_sum"): for
+    "REC_difference", "L1_by_lag" and "JSD_lag".  map_shape defaults to (30, 40) for 1201 actions only.
+    Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.RecurrenceStatisticsTable."""
+    from .utils.evaluation import RecurrenceStatisticsTable, recurrence_statistics_model_evaluation
+    table = RecurrenceStatisticsTable(max_steps)
+    return _statistics_loop(model, loader, ablate_attention_info, lambda means: table, human_table, recurrence_statistics_model_evaluation,
+                            min_length=min_length, max_steps=max_steps, radius=radius, frame_size=frame_size, map_shape=map_shape)
+
+
 def _statistics_loop(model, loader, ablate_attention_info, make_table, human, evaluate, **kw):
-    """the two loops above: evaluate(predict, keys, performances=..., **kw) per batch, merged by make_table(the first batch's means)
+    """the loops above: evaluate(predict, keys, performances=..., **kw) per batch, merged by make_table(the first batch's means)
     and read against human; a loader without a batch is an error"""
     table, per_batch = None, []
     for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):

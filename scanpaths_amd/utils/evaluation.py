@@ -1104,6 +1104,7 @@ def _group_labels(index, groups):
 # a statistic: evaltools.<name>_statistics, the entry names of its array and of what a scanpath or row adds, the expectation's result key
 _Statistic = namedtuple("_Statistic", "name array unit expected")
 _SACCADES, _TURNS = _Statistic("saccade", "lattice", "saccades", "E"), _Statistic("turn", "table", "pairs", "M")
+_RECURRENCE = _Statistic("recurrence", "table", "points", "E")
 
 
 def _tool(stat, what):
@@ -1137,9 +1138,11 @@ def _by_group(entries, labels, groups, label_of) -> dict:
     return means
 
 
-def _scanpath_statistics(stat, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, binning, *args, **kw):
+def _scanpath_statistics(stat, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, binning, *args,
+                         per_path=None, **kw):
     """(means, per_key) of scanpaths that exist: humans (side 0) and predictions of all groups in ONE counts(paths, side * NL + label,
-    2 NL, *args, **kw) launch; args and kw are checked"""
+    2 NL, *args, **kw) launch; args and kw are checked.  per_path (optional): the counts' result -> {name: float64 [S]}, scores of
+    every scanpath; per_key[name] / ["human_" + name] = the mean over the key's scanpaths with a value (_pool)"""
     gt_keys, predict_keys, index, _ = _keyed(gt_fix_vectors, gt_keys, predict_fix_vectors, predict_keys, image_keys)
     labels, label_of_key = _group_labels(index, groups)
     NL = max(len(labels), 1)
@@ -1161,9 +1164,12 @@ def _scanpath_statistics(stat, gt_fix_vectors, predict_fix_vectors, gt_keys, pre
         return _derived(stat, out, binning)
 
     per_key = {"keys": list(index)}
+    scores = per_path(res) if per_path is not None else {}
     for prefix, s in sides:
         for name, v in ((stat.unit, units), ("dropped", drop)):
             per_key[prefix + name] = np.bincount(key_of[side == s], weights=v[side == s], minlength=len(index)).astype(np.int64)
+        for name, v in scores.items():
+            per_key[prefix + name] = _pool(v[side == s], key_of[side == s], len(index))[0]
     return _by_group(entries, labels, groups, path_label), per_key
 
 
@@ -1350,6 +1356,87 @@ class TurnStatisticsTable(_StatisticsTable):
         super().__init__()
         self.n_directions = check_directions(n_directions, MAX_DIRECTIONS)
         self._shape = (self.n_directions + 1, self.n_directions + 1)
+
+    def result(self, human_table=None) -> dict:
+        return self._result(human_table)
+
+
+# ---- recurrence (evaltools/recurrence_statistics.py, csrc/scanrecur.hip in libscanpaths_amd_stats.so) ----------------------
+def _recurrence_scores(res) -> dict:
+    """the four measures of every scanpath of a recurrence_counts result, float64 [S] each"""
+    from .evaltools.recurrence_statistics import recurrence_measures
+    return recurrence_measures(res["rqa"])
+
+
+def recurrence_statistics_evaluation(gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, *, frame_size, map_shape, max_steps, radius,
+                                     min_line, groups=None, image_keys=None):
+    """How often a scanpath comes back to a place it has already looked at, and after how many fixations (Anderson et al. 2013, the
+    auto-recurrence form on action-map cells; Klein 2000 for the reading by lag): the recurrence table, for predicted scanpaths and for
+    the human ones, keyed and grouped as turn_statistics_evaluation keys and groups them.  frame_size = (height, width), map_shape =
+    (Hm, Wm), max_steps (at most 64), radius (pixels) and min_line (>= 2) have no defaults.  Humans and predictions of all groups are
+    counted in ONE launch (evaltools.recurrence_statistics.recurrence_counts).
+    Returns (means, per_key).  means["human_table_sum"] / ["table_sum"] int64 [max_steps, max_steps] (exact; [s, t] recurrent pairs,
+    [t, s] pairs, [t, t] fixations), ["human_points_sum"] / ["points_sum"], ["human_scanpaths_count"] / ["scanpaths_count"],
+    ["human_fixations_dropped"] / ["fixations_dropped"] -- what RecurrenceStatisticsTable merges -- ["human_summary"] / ["summary"]
+    (evaltools.recurrence_statistics.recurrence_summary) and, against the human side, ["REC_difference"], ["L1_by_lag"] and ["JSD_lag"].
+    With groups, means["by_group"][label] holds the same entries for the keys of that label.  per_key: "keys" and, per key in
+    first-appearance order of gt_keys, the recurrent points counted and the fixations dropped ("human_points", "human_dropped",
+    "points", "dropped", int64 [G]) and float64 [G] columns "REC", "DET", "LAM", "CORM" / "human_REC", .. = the mean over the key's
+    scanpaths with a defined value (evaltools.recurrence_statistics.recurrence_measures; NaN for a key without one) -- no table per
+    key."""
+    from .evaltools.recurrence_statistics import check_min_line, check_radius, check_table_steps
+    max_steps, map_shape, _ = check_table_steps(max_steps), check_map_shape(map_shape), check_frame(frame_size)
+    radius, min_line = check_radius(radius), check_min_line(min_line)
+    return _scanpath_statistics(_RECURRENCE, gt_fix_vectors, predict_fix_vectors, gt_keys, predict_keys, groups, image_keys, {},
+                                frame_size, map_shape, per_path=_recurrence_scores, max_steps=max_steps, radius=radius, min_line=min_line)
+
+
+def recurrence_statistics_human_evaluation(gt_fix_vectors, gt_keys, *, frame_size, map_shape, max_steps, radius, min_line, groups=None,
+                                           image_keys=None):
+    """The human row of recurrence_statistics_evaluation alone: the "human_" entries; means["human_table_sum"] is the human_table of
+    recurrence_statistics_model_evaluation and of RecurrenceStatisticsTable.result."""
+    return recurrence_statistics_evaluation(gt_fix_vectors, None, gt_keys, None, frame_size=frame_size, map_shape=map_shape,
+                                            max_steps=max_steps, radius=radius, min_line=min_line, groups=groups, image_keys=image_keys)
+
+
+def recurrence_statistics_model_evaluation(predict, keys, *, min_length, max_steps, radius, performances=None, frame_size=(240, 320),
+                                           map_shape=None, groups=None, human_table=None):
+    """The model's own recurrence table of ONE batch, exactly and without sampling
+    (evaltools.recurrence_statistics.recurrence_expectation): predict, keys, performances and groups as in
+    turn_statistics_model_evaluation (the heads are assigned per subject in the same way).  min_length (the sampler's), max_steps (at
+    most 64) and radius (pixels) are required; frame_size gives the radius its cells.  One expectation call and one copy back for the
+    batch; an entry whose row is bad (a step without mass) adds nothing and is counted.  DET and LAM are line statistics without a
+    closed form: they come from samples through recurrence_statistics_evaluation.
+    Returns (means, per_key): means["table_sum"] float64 [max_steps, max_steps] = the expected counts summed over the entries,
+    ["points_sum"] the expected recurrent points as the kernel's closed form gives them, ["rows_count"] / ["rows_bad"] the entries that
+    count / were bad -- what RecurrenceStatisticsTable merges -- ["summary"] and, when human_table is given, ["REC_difference"],
+    ["L1_by_lag"] and ["JSD_lag"] against it; with groups, means["by_group"][label] the same per label (human_table: one table for the
+    pooled entries, or a dict label -> table with the pooled one under None).  per_key: "keys" and "points" float64 [G], the expected
+    recurrent points per entry of the key (NaN for a key without a good entry)."""
+    from .evaltools.recurrence_statistics import check_radius, check_table, check_table_steps
+    max_steps, min_length, radius = check_table_steps(max_steps), check_min_length(min_length), check_radius(radius)
+    check_frame(frame_size)
+    for h in (human_table.values() if isinstance(human_table, dict) else () if human_table is None else (human_table,)):
+        if check_table(h).shape != (max_steps, max_steps):
+            raise ValueError(f"human_table of shape {np.shape(h)}: [{max_steps}, {max_steps}] is required")
+    return _model_statistics(_RECURRENCE, predict, keys, performances, groups, map_shape, human_table, {}, min_length=min_length,
+                             max_steps=max_steps, radius=radius, frame_size=frame_size)
+
+
+class RecurrenceStatisticsTable(_StatisticsTable):
+    """The pooled results of the recurrence-statistics calls over several batches: add(means) sums every "_sum", "_count", "_bad" and
+    "_dropped" entry (also inside "by_group"); result(human_table=None) derives the summaries and the three comparison numbers from the
+    SUMMED tables, as one call on the union of the batches gives them.  The comparison is against "human_table_sum" when the table
+    holds one, else against human_table (one table for the pooled entries, or a dict label -> table with the pooled one under None).
+    Integer tables (scanpaths that exist) merge exactly; expectations (the model's closed form) are float64 sums of non-negative terms
+    and merge to rounding: the batches' tables are added in the order of add, one call adds its rows in row order."""
+    _stat = _RECURRENCE
+
+    def __init__(self, max_steps):
+        from .evaltools.recurrence_statistics import check_table_steps
+        super().__init__()
+        self.max_steps = check_table_steps(max_steps)
+        self._shape = (self.max_steps, self.max_steps)
 
     def result(self, human_table=None) -> dict:
         return self._result(human_table)
