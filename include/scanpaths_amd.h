@@ -275,7 +275,8 @@ int sp_bn_bwd_split(const float* dy, const float* x, const unsigned long long* m
 
 /* MaxPool2d(3, stride 2, pad 0, ceil_mode=True), NHWC.  models/resnet.py:104.  argmax (nullable in the forward pass): the window position
  * (ky*3 + kx) of the first maximum, one byte per output element; the backward pass reads it instead of x and y and makes no value
- * comparisons.  C % 4 == 0. */
+ * comparisons.  ATen's rule, `(val > max) || isnan(val)`: a NaN in a window makes its output NaN, the position is the window's last NaN's, and
+ * the gradient goes there; a window holding only -inf gives -inf at position 0.  C % 4 == 0. */
 int sp_maxpool3s2_fwd(const float* x, int N, int H, int W, int C, float* y, unsigned char* argmax /* nullable */, int Ho, int Wo,
                       void* stream);
 int sp_maxpool3s2_bwd(const float* dy, const unsigned char* argmax, int N, int H, int W, int C, float* dx, int Ho, int Wo, void* stream);

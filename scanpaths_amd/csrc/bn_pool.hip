@@ -697,7 +697,8 @@ __global__ __launch_bounds__(256) void rowsum_bwd_kernel(const float* dout, int6
 }
 
 // ---------------------------------------------------------------- maxpool 3x3 s2 ceil, NHWC
-// argmax rule = first maximum in row-major window order (strict >), as ATen's CPU max_pool2d.
+// argmax rule = ATen's max_pool2d, `(val > max) || isnan(val)`: the first maximum in row-major window order (strict >); a NaN in the
+// window makes the output NaN at the position of the window's LAST NaN (nothing compares greater than a NaN, a later NaN replaces it).
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* x, int N, int H, int W, int C, float* y, int Ho,
                                                           int Wo, unsigned char* amx) {
     const int C4 = C / 4;
@@ -718,10 +719,10 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const float* x, int N,
                 if (ix >= W) break;
                 const float4 a = *reinterpret_cast<const float4*>(x + (((int64_t)n * H + iy) * W + ix) * C + c4 * 4);
                 const unsigned char q = (unsigned char)(ky * 3 + kx);
-                if (a.x > m.x) { m.x = a.x; am.x = q; }
-                if (a.y > m.y) { m.y = a.y; am.y = q; }
-                if (a.z > m.z) { m.z = a.z; am.z = q; }
-                if (a.w > m.w) { m.w = a.w; am.w = q; }
+                if (a.x > m.x || a.x != a.x) { m.x = a.x; am.x = q; }
+                if (a.y > m.y || a.y != a.y) { m.y = a.y; am.y = q; }
+                if (a.z > m.z || a.z != a.z) { m.z = a.z; am.z = q; }
+                if (a.w > m.w || a.w != a.w) { m.w = a.w; am.w = q; }
             }
         }
         reinterpret_cast<float4*>(y)[i] = m;
