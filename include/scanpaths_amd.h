@@ -86,11 +86,15 @@ int sp_conv_igemm(const sp_conv_desc* d, const float* X, const float* W, const f
 
 /* fp32-faithful variant on the bf16 matrix pipe: every operand pre-split into three bf16 planes x = x1+x2+x3
  * (sp_split3_bf16), six v_mfma_f32_32x32x16_bf16 products per fragment pair, hi/lo fp32 accumulators -> ~2^-24 relative
- * product error at 2.67x the fp32 MFMA rate.  Same descriptor as sp_conv_igemm (nbatch must be 1, Kc % 32 == 0); the
+ * product error at 2.67x the fp32 MFMA rate.  Same descriptor as sp_conv_igemm (nbatch must be 1, Kc % 16 == 0); the
  * weight operand is ALWAYS [Nout][K] rows (K contiguous): for mode 1 pass the operand made by sp_split3_bf16_wT.
  * ldx must equal Kc (dense NHWC source). */
 /* "split-3 interleaved" operand: x fp32 [rows][K] (K % 16 == 0) -> bf16 [rows][K/16][3][16] (96 contiguous bytes per row
- * per 16-k group; 6 bytes per element) followed by a 64-byte zero block (out must hold 6*n + 64 bytes) */
+ * per 16-k group; 6 bytes per element) followed by a 64-byte zero block (out must hold 6*n + 64 bytes).
+ * x1 = bf16(x), x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), each rounded to nearest even, the residuals exact in fp32: for a
+ * normal fp32 x whose planes do not underflow (|x| >= 2^-100 is enough) x1 + x2 + x3 == x EXACTLY.  An infinite or NaN x gives
+ * the planes (x, NaN, NaN), a finite x that rounds past the largest bf16 (+-inf, -+inf, NaN): the GEMMs then produce NaN,
+ * never a finite wrong value. */
 int sp_split3_bf16(const float* x, int64_t n, void* out, void* stream);
 /* w [Co][taps][Ci] fp32 -> rows ci, k = (tap, co):  bf16 [Ci][taps*Co/16][3][16]  (K-contiguous B operand of dgrad) */
 int sp_split3_bf16_wT(const float* w, int Co, int taps, int Ci, void* out, void* stream);
@@ -123,7 +127,9 @@ int64_t sp_conv_wgrad_workspace(const sp_wgrad_desc* d);
 int sp_conv_wgrad(const sp_wgrad_desc* d, const float* X, const float* dY, float* dW, void* workspace, void* stream);
 
 /* weight gradient on the same 3xbf16-split scheme (K = pixels; fragments by ds_read_b64_tr_b16).  X / dY are split-3
- * operands of the dense NHWC tensors; needs Ci % 128 == 0, Co % 16 == 0, nbatch == 1, ldx == Ci, ldy == Co. */
+ * operands of the dense NHWC tensors; needs Ci % 128 == 0, Co % 16 == 0, nbatch == 1, ldx == Ci, ldy == Co.  Output maps of
+ * ANY size >= 1 pixel are supported, the pure-GEMM form Ho = Wo = 1 (N_img = rows) included: a 16-pixel K-tile may cross any
+ * number of images.  workspace: exactly splits * Co * ldo * 4 bytes for more than one split of the pixels, else 0. */
 int64_t sp_conv_wgrad_bf16x3_workspace(const sp_wgrad_desc* d);
 int sp_conv_wgrad_bf16x3(const sp_wgrad_desc* d, const void* Xsplit, const void* dYsplit, float* dW, void* workspace,
                          void* stream);

@@ -413,6 +413,7 @@ __global__ __launch_bounds__(512, 2) void w3_kernel(W3Args p) {
         b_x[j] = rem - b_y[j] * p.Wo;
     }
     const int y_adv = 16 / p.Wo, x_adv = 16 - y_adv * p.Wo;      // advancing 16 output pixels = y_adv rows + x_adv columns
+    const bool tiny_map = HoWo < 16;                              // a K-tile of 16 pixels can then cross several images
     const uint32_t xrow = (uint32_t)(6 * p.Ci);
     int ld_kt = 0;
     auto issue_tile = [&](int stage) {
@@ -439,7 +440,9 @@ __global__ __launch_bounds__(512, 2) void w3_kernel(W3Args p) {
             b_x[j] += x_adv;
             b_y[j] += y_adv;
             if (b_x[j] >= p.Wo) { b_x[j] -= p.Wo; ++b_y[j]; }
-            if (b_y[j] >= p.Ho) { b_y[j] -= p.Ho; ++b_b[j]; }
+            if (b_y[j] >= p.Ho) { b_y[j] -= p.Ho; ++b_b[j]; }      // maps of >= 16 pixels cross at most one image boundary per K-tile
+            if (tiny_map)                                            // scalar condition: pure-GEMM uses of the kernel (Ho*Wo < 16)
+                while (b_y[j] >= p.Ho) { b_y[j] -= p.Ho; ++b_b[j]; }
         }
         ++ld_kt;
     };

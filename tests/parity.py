@@ -1,5 +1,5 @@
-"""What the fp64 parity modules share (tests/test_gemm_fp32_gpu.py, test_conv_f16x2_gpu.py, test_head_direct_gpu.py, test_rank1_grads_gpu.py,
-test_lstm_cell_gpu.py, test_decoder_ops_gpu.py, test_pool_sum_gpu.py, their *_ref.py restatements and tests/test_ops_gpu.py): the element-wise bar and its constants,
+"""What the fp64 parity modules share (tests/test_gemm_fp32_gpu.py, test_conv_f16x2_gpu.py, test_conv_bf16x3_gpu.py, test_head_direct_gpu.py,
+test_rank1_grads_gpu.py, test_lstm_cell_gpu.py, test_decoder_ops_gpu.py, test_pool_sum_gpu.py, their *_ref.py restatements and tests/test_ops_gpu.py): the element-wise bar and its constants,
 seeded data, guarded buffers on the host and on a device, the ctypes ABI, the max-norm metric, and the per-module record of PARITY figures.  A plain
 module: pytest collects and registers nothing here, and no module keeps state in another.  tests/test_parity_harness_cpu.py holds the checks
 below to their own failure cases on CPU buffers.  THE BAR (element-wise):  |got - ref| <= c 2^-24 S + 2^-149  with S the contraction over

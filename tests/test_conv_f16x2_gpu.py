@@ -9,8 +9,8 @@ must be unchanged after the launch, workspaces are exactly the queried size.  Ev
 the ELEMENT-WISE derived bar against R_planes (f16x2_ref: chain_*), the max-norm bars of tests/test_ops_gpu.py against R_true on top -- and on
 LATTICE data, where every summation order is exact and the kernel must equal R_planes exactly (torch.equal in fp64: bit for bit up to the sign of
 a zero).  Some cases add heavy-tailed data.  Each comparison prints a PARITY line, the module a summary per group (profiles/conv_f16x2_parity.md).
-Out of scope here: sp_gateconv_lstm_f16x2 (tests/test_lstm_cell_gpu.py), sp_rank1_grads_f16x2 (tests/test_rank1_grads_gpu.py), the bf16x3 kernels,
-the timing-library variants."""
+Out of scope here: sp_gateconv_lstm_f16x2 (tests/test_lstm_cell_gpu.py), sp_rank1_grads_f16x2 (tests/test_rank1_grads_gpu.py), the bf16x3 kernels
+(tests/test_conv_bf16x3_gpu.py), the timing-library variants."""
 import ctypes
 import functools
 
