@@ -1,5 +1,5 @@
 // What the scanpath scorer kernels share (scanmetrics.hip, scandist.hip, seqscore.hip, scansimplify.hip, scanlik.hip, scankde.hip,
-// scansearch.hip, scansaccade.hip, scanturn.hip, scanboot.hip and, in the stats library, scanrecur.hip) -- the device-side counterpart of
+// scansearch.hip, scansaccade.hip, scanturn.hip, scanboot.hip and, in the stats and the model library, scanrecur.hip and scanexpect.hip) -- the device-side counterpart of
 // utils/evaltools/_batch.py and _args.py: the fixation and the cell limit, the float64 arithmetic rule, the pixel rule that turns a
 // fixation into a map cell, the prologue of a kernel that scores scanpaths or pairs of them in the layout rows [total][ncol] | start
 // int64 [K] | count int32 [K] | pairs int32 [P][2], with the guard against a count the kernel cannot hold, the two wave reductions,
@@ -66,7 +66,7 @@ __device__ __forceinline__ double wave_max_d(double v) {      // b > a ? b : a, 
     return v;
 }
 
-// ---- the displacement lattice and the model's step distributions (scansaccade.hip, scanturn.hip, scansearch.hip) -------------------------
+// ---- the displacement lattice and the model's step distributions (scansaccade.hip, scanturn.hip, scansearch.hip, scanrecur.hip, scanexpect.hip) -------------------------
 // launcher checks: a frame of positive finite sizes; a map of Hm x Wm >= 1 x 1 and at most MAXCELLS cells
 static inline bool scan_frame_ok(double frame_w, double frame_h) {
     return frame_w > 0 && frame_w < INFINITY && frame_h > 0 && frame_h < INFINITY;

@@ -83,23 +83,49 @@ STATS_ABI_VERSION = _STATS_DEFINES["SP_STATS_ABI_VERSION"]
 _stats_lib: Optional[C.CDLL] = None
 
 
+def _load_side_library(path, signatures, version_entry, version, define, header) -> C.CDLL:
+    """a library beside the main one: every entry point typed from its header; a missing file or another ABI version raises"""
+    if not os.path.exists(path):
+        raise RuntimeError(
+            f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            "(make -C scanpaths_amd/csrc; hipcc --offload-arch=gfx950).  scanpaths_amd has no CPU or eager fallback.")
+    cdll = C.CDLL(path)
+    for name, (restype, argtypes) in signatures.items():
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    found = getattr(cdll, version_entry)()
+    if found != version:
+        raise RuntimeError(f"{path}: ABI version {found}, this binding expects {version} "
+                           f"({define} in include/{header}): rebuild with `make -C scanpaths_amd/csrc`")
+    return cdll
+
+
 def stats_lib() -> C.CDLL:
     """Load libscanpaths_amd_stats.so (once), every entry point typed from its header.  A missing file or another ABI version raises."""
     global _stats_lib
     if _stats_lib is None:
-        if not os.path.exists(STATS_LIB_PATH):
-            raise RuntimeError(
-                f"{STATS_LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                "(make -C scanpaths_amd/csrc; hipcc --offload-arch=gfx950).  scanpaths_amd has no CPU or eager fallback.")
-        cdll = C.CDLL(STATS_LIB_PATH)
-        for name, (restype, argtypes) in STATS_SIGNATURES.items():
-            fn = getattr(cdll, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        if cdll.sp_stats_abi_version() != STATS_ABI_VERSION:
-            raise RuntimeError(f"{STATS_LIB_PATH}: ABI version {cdll.sp_stats_abi_version()}, this binding expects {STATS_ABI_VERSION} "
-                               "(SP_STATS_ABI_VERSION in include/scanpaths_amd_stats.h): rebuild with `make -C scanpaths_amd/csrc`")
-        _stats_lib = cdll
+        _stats_lib = _load_side_library(STATS_LIB_PATH, STATS_SIGNATURES, "sp_stats_abi_version", STATS_ABI_VERSION,
+                                        "SP_STATS_ABI_VERSION", "scanpaths_amd_stats.h")
     return _stats_lib
+
+
+# The third library (include/scanpaths_amd_model.h, DESIGN.md §26): the model's statistics in closed form.  The stats library's exports
+# are pinned as the main library's are; this one is where the next closed-form statistic goes, with its version bumped.
+MODEL_HEADER_PATH = os.path.join(os.path.dirname(_abi.HEADER_PATH), "scanpaths_amd_model.h")
+MODEL_LIB_PATH = os.path.join(_HERE, "libscanpaths_amd_model.so")
+_MODEL_DEFINES, _, MODEL_SIGNATURES = _abi.load(MODEL_HEADER_PATH)
+MODEL_ABI_VERSION = _MODEL_DEFINES["SP_MODEL_ABI_VERSION"]
+
+_model_lib: Optional[C.CDLL] = None
+
+
+def model_lib() -> C.CDLL:
+    """Load libscanpaths_amd_model.so (once), every entry point typed from its header.  A missing file or another ABI version raises."""
+    global _model_lib
+    if _model_lib is None:
+        _model_lib = _load_side_library(MODEL_LIB_PATH, MODEL_SIGNATURES, "sp_model_abi_version", MODEL_ABI_VERSION,
+                                        "SP_MODEL_ABI_VERSION", "scanpaths_amd_model.h")
+    return _model_lib
 
 
 class HipError(RuntimeError):

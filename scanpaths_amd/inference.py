@@ -206,6 +206,36 @@ def run_recurrence_statistics_loop(model, loader: Iterable[dict], *, min_length,
                             min_length=min_length, max_steps=max_steps, radius=radius, frame_size=frame_size, map_shape=map_shape)
 
 
+@torch.no_grad()
+def run_saliency_loop(model, loader: Iterable[dict], *, sigma, min_length, max_steps, pred_weight="count", extra_metrics=(),
+                      ablate_attention_info: bool = False, frame_size=(240, 320), map_shape=None, **kw) -> Tuple[dict, List[dict]]:
+    """The saliency scores (AUC_Judd, NSS, KLdiv and the extras "CC", "SIM") of the model's own fixation density over a loader, exactly
+    and without sampling (utils.evaluation.saliency_model_evaluation): per batch ONE eval-mode forward, ONE
+    sp_model_fixation_expectation call and the scoring launches -- no sampler call, no scanpath upload for the model's side.  loader
+    yields run_test_loop's batches: "fix_vectors" is the human side, the key of a sample is its question id, "tasks" is passed to the
+    model when the batch has it, "performances" is read when the model has the two AiR heads.  sigma (pixels), min_length (the
+    sampler's) and max_steps (at most 64) have no defaults; pred_weight "count" or "duration"; **kw goes on (output_shape, mode,
+    truncate).  "sAUC" and "IG" need fixations from OTHER images and a batch is not the dataset: they are refused here -- call
+    utils.evaluation.saliency_model_evaluation once over the whole set for them.
+    Returns (means, per_key of every batch): means = the batches merged by utils.evaluation.SaliencyModelTable."""
+    from .utils.evaluation import SaliencyModelTable, saliency_model_evaluation
+    other_images = [m for m in extra_metrics if m in ("sAUC", "IG")]
+    if other_images:
+        raise ValueError(f"extra_metrics {other_images}: the shuffled AUC's negatives and the information gain's baseline come from the "
+                         "OTHER images, and a batch is not the dataset; call utils.evaluation.saliency_model_evaluation over the whole "
+                         "set")
+    table, per_batch = SaliencyModelTable(), []
+    for batch, predict in _forward_batches(model, loader, ablate_attention_info, with_tasks=True):
+        means, per_key = saliency_model_evaluation(predict, batch["fix_vectors"], batch["question_ids"], _performances(batch, predict),
+                                                   sigma=sigma, min_length=min_length, max_steps=max_steps, pred_weight=pred_weight,
+                                                   frame_size=frame_size, map_shape=map_shape, extra_metrics=extra_metrics, **kw)
+        table.add(means)
+        per_batch.append(per_key)
+    if not per_batch:
+        raise ValueError("the loader yielded no batch")
+    return table.result(), per_batch
+
+
 def _statistics_loop(model, loader, ablate_attention_info, make_table, human, evaluate, **kw):
     """the loops above: evaluate(predict, keys, performances=..., **kw) per batch, merged by make_table(the first batch's means)
     and read against human; a loader without a batch is an error"""

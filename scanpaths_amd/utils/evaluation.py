@@ -14,10 +14,10 @@
   each (a question id, an image name) and returns (means, per_key), per_key in first-appearance order of the keys.  _keyed / _key_index
   check the keys; _model_pairs / _ceiling_pairs / _pair_tables serve the pair measures (saliency_*, scanpath_distance_*,
   sequence_score_*); the model-side calls that read the model's distributions instead of samples (likelihood_*, search_efficiency_model_*,
-  saccade_statistics_model_*, turn_statistics_model_*) get their entries from _head_entries; _pool is the mean per key with its pooled sum and count, _key_means
+  saccade_statistics_model_*, turn_statistics_model_*, recurrence_statistics_model_*, saliency_model_*) get their entries from _head_entries; _pool is the mean per key with its pooled sum and count, _key_means
   the mean over keys.
 
-  Tables: LikelihoodTable, SearchEfficiencyTable, SaccadeStatisticsTable, TurnStatisticsTable merge the means of several batches (_SumTable holds the merge).
+  Tables: LikelihoodTable, SearchEfficiencyTable, SaccadeStatisticsTable, TurnStatisticsTable, RecurrenceStatisticsTable, SaliencyModelTable merge the means of several batches (_SumTable holds the merge).
 
   Bootstrap: bootstrap_evaluation / bootstrap_comparison / bootstrap_information_gain_explained put intervals on any per_key table."""
 from __future__ import annotations
@@ -1440,6 +1440,94 @@ class RecurrenceStatisticsTable(_StatisticsTable):
 
     def result(self, human_table=None) -> dict:
         return self._result(human_table)
+
+
+# ---- saliency scores of the model's own fixation density, in closed form (evaltools/saliency_maps.py, csrc/scanexpect.hip) --
+def saliency_model_evaluation(predict, fix_vectors, keys, performances=None, image_keys=None, *, sigma, min_length, max_steps,
+                              pred_weight="count", frame_size=(240, 320), map_shape=None, extra_metrics=(), **kw):
+    """saliency_evaluation's scores of ONE batch with the model's side read exactly, without sampling: the predicted map of a key is
+    the expected fixation map of the sampler's scanpaths (evaltools.saliency_maps.expected_fixation_maps), what the map of
+    prediction="scanpaths" converges to as repeat_num grows.  The batch layout is likelihood_evaluation's: predict = the model's
+    eval-mode output on the device, fix_vectors[i] = the list of the subjects' fixation vectors of sample i, the human side of key
+    keys[i].  One model row per subject (_head_entries): a head read by k subjects counts k times; with performances the "good_" /
+    "poor_" heads are read as training assigns them.  sigma (pixels of the output map), min_length (the sampler's) and max_steps (at
+    most 64) have no defaults.  pred_weight "count", or "duration": every step weighs its mean duration
+    (evaltools.saliency_maps.expected_durations of log_normal_mu / log_normal_sigma2); "binary" is refused: the binary map of several
+    samples is a union, not an expectation.  image_keys[i]: the image of sample i, for "sAUC" and "IG" (whose pools and baselines are
+    the OTHER images of THIS call: pass the whole set); extra_metrics and **kw (output_shape, mode, truncate, uniform_mix,
+    baseline_sigma) as in saliency_evaluation.  One expectation call and the scoring launches; no sampler call.
+    Returns (means, per_key) in saliency_evaluation's shape, so the bootstrap functions read per_key unchanged: means[metric] /
+    [metric + "_nan"], and for SaliencyModelTable [metric + "_sum"] / [metric + "_count"] over the keys with a value, ["rows_count"] /
+    ["rows_bad"] = the model rows that count / had a step without mass (they add nothing), ["fixations_sum"] = the expected fixations
+    of the rows that count; per_key also holds "fixations" float64 [G]: the key's expected fixations per row (NaN without a good row)."""
+    from .evaltools.saliency_maps import expected_durations, expected_fixation_maps, scanpath_saliency
+    if pred_weight == "binary":
+        raise ValueError("pred_weight 'binary' has no closed form here: the binary map of several samples is a union over samples, not "
+                         "an expectation; 'count' or 'duration'")
+    if pred_weight not in ("count", "duration"):
+        raise ValueError(f"pred_weight {pred_weight!r}: 'count' or 'duration'")
+    from .evaltools._batch import MAX_FIXATIONS
+    min_length, max_steps = check_min_length(min_length), check_steps(max_steps)
+    if max_steps > MAX_FIXATIONS:
+        raise ValueError(f"max_steps {max_steps}: at most {MAX_FIXATIONS} steps count")
+    check_frame(frame_size)
+    keys = list(keys)
+    N = len(keys)
+    if len(fix_vectors) != N:
+        raise ValueError("one key per sample is required")
+    if performances is not None and (len(performances) != N or any(len(p) != len(f) for p, f in zip(performances, fix_vectors))):
+        raise ValueError("one performance per subject of every sample is required")
+    if image_keys is not None and len(image_keys) != N:
+        raise ValueError("one image key per sample is required")
+    if "prediction" in kw or "pred_maps" in kw or "num_groups" in kw:
+        raise ValueError("prediction, pred_maps and num_groups are this function's to set")
+    duration = pred_weight == "duration"
+    subjects = [len(s) for s in fix_vectors]
+    index, rows, key_of, _, both = _head_entries(predict, keys, performances, subjects, ("all_actions_prob",) + (
+        ("log_normal_mu", "log_normal_sigma2") if duration else ()))
+    _, images = _key_index(keys, image_keys)
+    if extra_metrics or images is not None:
+        kw = dict(kw, extra_metrics=extra_metrics, image_groups=images)
+    G = len(index)
+    probs = both("all_actions_prob")
+    weight = expected_durations(both("log_normal_mu"), both("log_normal_sigma2"))[rows] if duration else None
+    import torch
+    res = expected_fixation_maps(probs.index_select(0, torch.as_tensor(rows, dtype=torch.int64, device=probs.device)), key_of, max(G, 1),
+                                 min_length=min_length, max_steps=max_steps, frame_size=frame_size, output_shape=kw.get("output_shape"),
+                                 map_shape=map_shape, step_weight=weight)
+    scores = scanpath_saliency([fv for s in fix_vectors for fv in s], key_of, [], [], frame_size, sigma, num_groups=G,
+                               prediction="maps", pred_maps=res["maps"][:G], **kw)
+    metrics = ("AUC_Judd", "NSS", "KLdiv") + tuple(extra_metrics)
+    per_key = {"keys": list(index)}
+    per_key.update({k: v.cpu().numpy() for k, v in scores.items()})
+    good = res["bad"] == 0
+    n_good = np.bincount(key_of[good], minlength=G)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        per_key["fixations"] = np.where(n_good > 0, np.bincount(key_of[good], weights=res["fixations"][good], minlength=G)
+                                        / np.maximum(n_good, 1), np.nan)
+    means = _key_means(per_key, metrics)
+    for m in metrics:
+        ok = ~np.isnan(per_key[m])
+        means[m + "_sum"], means[m + "_count"] = float(per_key[m][ok].sum()), int(ok.sum())
+    means.update({"rows_count": int(good.sum()), "rows_bad": int((~good).sum()), "fixations_sum": float(res["fixations"][good].sum())})
+    return means, per_key
+
+
+class SaliencyModelTable(_SumTable):
+    """The means of saliency_model_evaluation over several batches: add(means) sums every "_sum", "_count", "_nan" and "_bad" entry;
+    result()[metric] = the metric's sum / count over all keys of all batches -- the mean over keys that one call on their union gives
+    for the metrics that need no other image (a key that appears in two batches counts in each) -- and result()["fixations_per_row"]
+    = "fixations_sum" / "rows_count"."""
+    _suffixes = ("_sum", "_count", "_nan", "_bad")
+
+    def result(self) -> dict:
+        out, nan = dict(self.parts), float("nan")
+        for k, count in self.parts.items():
+            if k.endswith("_count") and k[:-len("_count")] + "_sum" in self.parts:
+                out[k[:-len("_count")]] = self.parts[k[:-len("_count")] + "_sum"] / count if count else nan
+        if "rows_count" in out:
+            out["fixations_per_row"] = out["fixations_sum"] / out["rows_count"] if out["rows_count"] else nan
+        return out
 
 
 # ---- bootstrap intervals and paired comparisons for every keyed table (evaltools/bootstrap.py, csrc/scanboot.hip; DESIGN.md §23) ----------
